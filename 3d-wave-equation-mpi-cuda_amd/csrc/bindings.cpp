@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include <pybind11/functional.h>
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 
 #include <chrono>
@@ -388,12 +389,12 @@ PYBIND11_MODULE(_wave3d_C, m) {
                 d["rank"] = b.rank;
                 d["off"] = std::vector<int>{b.off[0], b.off[1], b.off[2]};
                 d["ext"] = std::vector<int>{b.ext[0], b.ext[1], b.ext[2]};
-                d["data"] = b.data;
+                d["data"] = py::array_t<double>(py::ssize_t(b.data.size()), b.data.data());  // a copy
                 out.append(d);
             }
             return out;
         }, py::arg("layer"),
-           "Owned blocks (k fastest) of layer K or K-1 after a solve (print_layer analogue).");
+           "Owned blocks (k fastest, float64 arrays) of layer K or K-1 after a solve (print_layer analogue).");
 
     m.def("run", &run, py::arg("args"), py::arg("backend") = "hip",
           py::arg("transport") = nullptr, py::arg("write") = true, py::arg("root") = true,

@@ -24,7 +24,14 @@ the transport and the ranks RCCL itself reports (ncclCommCount), and whether the
 matches the golden. Data: the analytic initial condition on a synthetic grid (the
 reference's own test problem).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the `--steps` solves and prints the JSON line; `--full`
+adds what takes a run of its own (fp32: the fp64 L-inf of the same N, K and decomposition).
+`--dump-outputs DIR` writes what the last timed solve returned as DIR/<name>.npy (float64):
+`max_abs` and `max_rel`, the per-layer error tables (K+1 values each), and `u_final`, layer K
+of the field (`u_final.r<rank>` per block with several ranks) or, for more than 4M nodes, a
+fixed seeded sample of it. The problem is analytic, so the same arguments give the same inputs.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -37,6 +44,8 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+DUMP_SAMPLES = 4_000_000  # nodes of layer K that --dump-outputs keeps in all (32 MB of float64)
+DUMP_SEED = 20240512
 METRIC = "Mpoints/sec (whole node) + L∞ error vs analytic, N={N}³ {dtype}"  # BASELINE.json at N=512
 
 
@@ -66,8 +75,8 @@ def main() -> int:
                          "bit; fma = coef/h^2 folded into fused multiply-adds (same scheme, same L-inf abs to "
                          "9 digits at the headline config, profiles/math_fma_r3.txt); auto = fma on the GPU")
     ap.add_argument("--fp64-ref", default="auto", choices=["auto", "on", "off"],
-                    help="fp32 runs: after timing, solve the same N/K/decomposition in fp64 and report "
-                         "its L-inf as linf_fp64_ref (BASELINE.md §4 config 5); auto = on for fp32")
+                    help="with --full, fp32 runs: after timing, solve the same N/K/decomposition in fp64 and "
+                         "report its L-inf as linf_fp64_ref (BASELINE.md §4 config 5); auto = on for fp32")
     ap.add_argument("--kernel", default="auto")
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--overlap", default="auto", choices=["auto", "on", "off", "pipe"],
@@ -84,6 +93,12 @@ def main() -> int:
                          "bandwidth (the 8-GPU rehearsal on one GPU with an xGMI-like link cost)")
     ap.add_argument("--launch-timeout", type=float, default=1000.0,
                     help="self-launch (--gpus N without torchrun): kill every rank after this many s")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (the fp64 reference solve of "
+                         "an fp32 run, --fp64-ref)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed solve computed as DIR/<name>.npy (float64): max_abs, "
+                         "max_rel (per layer) and u_final (layer K, a seeded sample above 4M nodes)")
     a = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -267,13 +282,16 @@ def main() -> int:
         "timers_ms": {k: round(res[k], 4) for k in ("loop_ms", "exchange_ms", "comm_ms", "error_ms", "total_ms")},
         "baseline_mpts": base,
     }
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, sess, res, rank, n_gpus)
     # explicit teardown while HIP and the process group are alive: the session (which keeps the
     # transport alive) first, then the transport (ncclCommDestroy), then the torch group
     del sess
     import gc
     gc.collect()
     want_ref = a.fp64_ref == "on" or (a.dtype == "fp32" and a.fp64_ref == "auto" and not a.fill_hbm)
-    if want_ref:
+    if a.full and want_ref:
+        # --full only (a second solve, not part of the headline figure):
         # the fp64 L-inf of the same N, K and decomposition (config 5 compares
         # against its own fp64 run), after the timed region and after the fp32 session is freed.
         # auto skips it with --fill-hbm (N is sized to the fp32 footprint, fp64 needs twice that)
@@ -314,6 +332,25 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(path: str, sess, res: dict, rank: int, n_gpus: int) -> None:
+    """--dump-outputs: the arrays of the last timed solve as float64 .npy files. The error tables
+    are the job's (after the cross-rank MAX), so rank 0 writes them; every rank writes its own
+    blocks of layer K, above DUMP_SAMPLES nodes in all the nodes at indices drawn once from a
+    fixed seed (block-local, k fastest), the same for every run and build."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    if rank == 0:
+        np.save(os.path.join(path, "max_abs.npy"), np.asarray(res["max_abs"], dtype=np.float64))
+        np.save(os.path.join(path, "max_rel.npy"), np.asarray(res["max_rel"], dtype=np.float64))
+    budget = DUMP_SAMPLES // n_gpus
+    for b in sess.field(res["timesteps"]):
+        u = np.asarray(b.pop("data"), dtype=np.float64)
+        if u.size > budget:
+            u = u[np.random.default_rng(DUMP_SEED + b["rank"]).integers(0, u.size, budget)]
+        np.save(os.path.join(path, "u_final.npy" if n_gpus == 1 else f"u_final.r{b['rank']}.npy"), u)
 
 
 def _free_port() -> int:

@@ -173,8 +173,9 @@ def test_bench_gpu_fp32_two_ranks_staged(scheme, linf):
     """fp32 --math exact runs the three-layer sweep (tb3, 3-deep halos) through the multi-process bench path:
     2 processes on one MI355X, staged transport, N=512 on 2x1x1 slabs, K=100 (stable): the fp32
     L-inf of the single-GPU run (leapfrog 4.47035e-06, profiles/fp32_accuracy_r2.txt; the fp32
-    default, the increment form, 1.3113e-06), and the fp64 L-inf of the same run (the golden)."""
-    r = _bench(["--steps", "1", "--warmup", "0", "--dtype", "fp32", "--transport", "staged",
+    default, the increment form, 1.3113e-06), and with --full the fp64 L-inf of the same run (the
+    golden)."""
+    r = _bench(["--steps", "1", "--warmup", "0", "--dtype", "fp32", "--transport", "staged", "--full",
                 "--shared-device", "--overlap", "on", "--scheme", scheme, "--math", "exact"], nproc=2, timeout=600)
     assert r["dtype"] == "fp32" and r["n_gpus"] == 2 and r["config"]["dims"] == [2, 1, 1]
     # fp32 exact: three layers per sweep (tb3) for both schemes
@@ -191,6 +192,89 @@ def test_bench_named_config_cpu128():
     assert r["config"]["N"] == 128 and r["config"]["timesteps"] == 20
     assert r["config"]["baseline_config"] == "cpu128"
     assert f"{r['linf_abs']:.6g}" == "8.81051e-06" and r["linf_ok"] is True
+
+
+CPU32 = ["--backend", "cpu", "--N", "32", "--timesteps", "20", "--steps", "2", "--warmup", "0"]
+
+
+def _dump(d):
+    import numpy as np
+
+    out = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    assert all(v.dtype == np.float64 for v in out.values())
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    return out
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes the last timed solve's arrays as float64 .npy files: the per-layer
+    error tables (K+1 values, the last one the JSON's linf_abs) and the whole layer K of a small
+    grid, zero on the first-kind faces in y; the same arguments give the same files again."""
+    import numpy as np
+
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    r = _bench(CPU32 + ["--dump-outputs", a])
+    _check(r, 1, 2, 0)
+    _bench(CPU32 + ["--dump-outputs", b])
+    da, db = _dump(a), _dump(b)
+    assert set(da) == {"max_abs", "max_rel", "u_final"} == set(db)
+    assert da["max_abs"].shape == da["max_rel"].shape == (21,) and da["max_abs"][-1] == r["linf_abs"]
+    u = da["u_final"].reshape(33, 33, 33)
+    assert np.abs(u).max() > 0.1 and np.all(u[:, 0, :] == 0) and np.all(u[:, -1, :] == 0)
+    assert all(np.array_equal(da[k], db[k]) for k in da)
+
+
+def test_bench_dump_outputs_samples_a_large_field(tmp_path):
+    """Above 4M nodes (N=160: 161^3 = 4.17M) u_final is a sample of 4M nodes at indices fixed by
+    the seed: the same nodes in every run."""
+    import numpy as np
+
+    ext = ["--backend", "cpu", "--N", "160", "--timesteps", "2", "--steps", "1", "--warmup", "0", "--dump-outputs"]
+    _bench(ext + [str(tmp_path / "a")])
+    _bench(ext + [str(tmp_path / "b")])
+    da, db = _dump(str(tmp_path / "a")), _dump(str(tmp_path / "b"))
+    assert da["u_final"].shape == (4_000_000,) and da["max_abs"].shape == (3,)
+    assert np.abs(da["u_final"]).max() > 0.1 and np.array_equal(da["u_final"], db["u_final"])
+
+
+def test_bench_dump_outputs_two_ranks(tmp_path):
+    """Two self-launched ranks: rank 0 writes the job's error tables, each rank its block of layer K."""
+    d = str(tmp_path / "d")
+    r = _bench(CPU32 + ["--dump-outputs", d], nproc=2, self_launch=True)
+    out = _dump(d)
+    assert set(out) == {"max_abs", "max_rel", "u_final.r0", "u_final.r1"}
+    assert out["max_abs"][-1] == r["linf_abs"]
+    assert out["u_final.r0"].size + out["u_final.r1"].size == 33 ** 3
+
+
+def test_bench_full_gates_the_fp64_reference_solve():
+    """A plain fp32 run only times its solves; --full adds the fp64 L-inf of the same run."""
+    plain = _bench(CPU32 + ["--dtype", "fp32"])
+    full = _bench(CPU32 + ["--dtype", "fp32", "--full"])
+    assert "linf_fp64_ref" not in plain and plain["dtype"] == "fp32"
+    assert f"{full['linf_fp64_ref']:.6g}" == "0.000175963"  # golden N=32 K=20
+    assert full["linf_abs"] == plain["linf_abs"]
+    assert "linf_fp64_ref" not in _bench(CPU32 + ["--full"])  # fp64: nothing to add
+
+
+@pytest.mark.gpu
+def test_bench_gpu_dump_outputs_matches_cpu_backend(tmp_path):
+    """The HIP path's dump against the CPU backend's at N=64, K=20, --math exact (the same
+    operation order): the fields agree to 1e-12 (values O(1), fp64 rounding 1e-16 per operation
+    over 20 layers; a wrong node is off by the scheme's 1e-5 or more) and the tables' last entry
+    is the JSON's linf_abs."""
+    import numpy as np
+
+    ext = ["--N", "64", "--timesteps", "20", "--steps", "2", "--warmup", "1", "--math", "exact", "--dump-outputs"]
+    g, c = str(tmp_path / "g"), str(tmp_path / "c")
+    r = _bench(ext + [g])
+    _check(r, 1, 2, 1)
+    _bench(["--backend", "cpu"] + ext + [c])
+    dg, dc = _dump(g), _dump(c)
+    assert dg["u_final"].shape == dc["u_final"].shape == (65 ** 3,)
+    assert np.abs(dg["u_final"] - dc["u_final"]).max() <= 1e-12
+    assert dg["max_abs"].shape == (21,) and dg["max_abs"][-1] == r["linf_abs"]
+    assert np.abs(dg["max_abs"] - dc["max_abs"]).max() <= 1e-12
 
 
 def test_bench_self_launch_cpu_two_ranks():
