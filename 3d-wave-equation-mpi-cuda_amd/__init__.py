@@ -24,6 +24,10 @@ def __getattr__(name):
         from .models import wave
 
         return getattr(wave, name)
+    if name in ("MediumProblem", "MediumSolver", "MediumResult", "ricker"):
+        from .models import medium
+
+        return getattr(medium, name)
     if name == "presets":
         from .models import presets
 

@@ -18,6 +18,7 @@
 
 #include "checkpoint.hpp"
 #include "hip_kernels.hpp"
+#include "hip_medium.hpp"
 #include "problem.hpp"
 #include "rccl_transport.hpp"
 #include "sizing.hpp"
@@ -324,6 +325,32 @@ void k_zero_faces(uintptr_t u, const std::vector<i64>& g, int mask, uintptr_t st
     launch_zero_faces<T>(P<T>(u), gview(g), mask, (hipStream_t)stream);
 }
 
+// Heterogeneous-medium step (k_march_m): m = c^2 tau^2 per node, h2 = (hx2, hy2, hz2); the grid
+// view carries explicit strides (dense tensors or the padded views of ops.kernels.alloc_level).
+template <class T>
+void k_step_medium(bool first, uintptr_t u1, uintptr_t u2, uintptr_t m, uintptr_t u, const std::vector<i64>& g,
+                   const std::vector<std::vector<int>>& boxes, int ei0, int ei1, const std::vector<int>& wrap,
+                   const std::vector<double>& h2, uintptr_t err, int chunk, uintptr_t stream, int variant) {
+    std::vector<Box> bx;
+    for (auto& b : boxes) bx.push_back(tobox(b));
+    W3D_REQUIRE(h2.size() == 3, "h2 = (hx2, hy2, hz2)");
+    const double h[3] = {h2[0], h2[1], h2[2]};
+    launch_step_medium<T>(first, P<T>(u1), P<T>(u2), P<T>(m), P<T>(u), gview(g), bx.data(), int(bx.size()), ei0,
+                          ei1, towrap(wrap), h, P<u64>(err), chunk, (hipStream_t)stream, variant);
+}
+
+// nodes: device int32 [n][3] of (i, j, k); g / out: n device values
+template <class T>
+void k_inject(uintptr_t u, uintptr_t m, const std::vector<i64>& g, uintptr_t nodes, uintptr_t vals, int n,
+              const std::vector<int>& wrap, uintptr_t stream) {
+    launch_inject<T>(P<T>(u), P<T>(m), gview(g), P<int>(nodes), P<T>(vals), n, towrap(wrap), (hipStream_t)stream);
+}
+
+template <class T>
+void k_record(uintptr_t u, const std::vector<i64>& g, uintptr_t nodes, uintptr_t out, int n, uintptr_t stream) {
+    launch_record<T>(P<T>(u), gview(g), P<int>(nodes), P<T>(out), n, (hipStream_t)stream);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_wave3d_C, m) {
@@ -528,6 +555,13 @@ PYBIND11_MODULE(_wave3d_C, m) {
     m.def("tb_supported", [](int depth, int rows, int waves, bool fm) {
         return depth == 3 && tb3_supported(rows, waves, fm);
     }, py::arg("depth"), py::arg("rows"), py::arg("waves"), py::arg("fm") = false);
+    m.def("k_step_medium_f64", &k_step_medium<double>);
+    m.def("k_step_medium_f32", &k_step_medium<float>);
+    m.def("k_inject_f64", &k_inject<double>);
+    m.def("k_inject_f32", &k_inject<float>);
+    m.def("k_record_f64", &k_record<double>);
+    m.def("k_record_f32", &k_record<float>);
+    m.def("medium_variant", &medium_variant);
     m.def("k_init_f64", &k_init<double>);
     m.def("k_init_f32", &k_init<float>);
     m.def("k_faces_f64", &k_faces<double>);

@@ -1,0 +1,398 @@
+// Heterogeneous-medium kernels: the 2.5-D marching step with a per-node coefficient field,
+// point-source injection and receiver sampling (interface: hip_medium.hpp).
+//
+//  * k_march_m: k_march's design (hip_kernels.hip) — a 256-thread workgroup owns a (4R) x 64
+//    tile of the (j,k) plane and marches along i, u^{n-1} rolling through four register slots,
+//    the current plane staged in a double-buffered LDS tile (one barrier per plane), u^{n-2}
+//    prefetched one plane ahead, non-temporal stores with the periodic self-wrap fused in — plus
+//    a fourth stream: m = c^2 tau^2 at the lane's own nodes, prefetched one plane ahead in a
+//    two-slot register ring like u^{n-2} (no LDS: only the centre node's m enters the update).
+//    No analytic tables and no fused halo packing; the per-step statistic is max |u|.
+//  * k_inject / k_record: one thread per source entry / receiver.
+//
+// FP contraction is off (-ffp-contract=off + the pragmas in stencil_math.hpp): every operation
+// is rounded on its own in the order of ops/reference.py step_medium, so fp64 results are
+// bitwise those of the PyTorch oracle, and a uniform m == coef gives k_march's bits.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+
+#include <algorithm>
+
+#include "device_common.hpp"
+#include "hip_medium.hpp"
+
+namespace wave3d {
+namespace {
+
+template <class T>
+struct MediumParams {
+    int xcd;  // XCD-aware tile order (xcd_swizzle)
+    const T* u1;
+    const T* u2;
+    const T* m;
+    T* u;
+    i64 si;
+    int sj;
+    int poff;        // see GridView::poff
+    int jmax, kmax;  // largest valid j / k index in storage
+    int nbox;
+    BoxLaunch box[kMaxBoxes];
+    int ei0, ei1;
+    int w_lo[2], w_hi[2], w_sh[2];  // wrap_ranges
+    T hx2, hy2, hz2;
+    T yx2, yy2, yz2;  // RN(1/h^2) in T for the correctly rounded constant division
+    u64* err;
+};
+
+// R = rows (j) per lane; the workgroup tile is (4R) x 64. NTM = non-temporal loads of m.
+// Register slots as in k_march: u1(x) -> (x - ib + 1) & 3; u2(x), m(x), halo(x) and the LDS
+// buffer -> (x - ib) & 1; the i loop is unrolled by 4 with the phase as a constant.
+template <class T, bool FIRST, int R, bool NTM>
+__global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
+    constexpr int kTJ = kWaves * R;
+    constexpr unsigned ES = sizeof(T);
+    __shared__ T lds[2][kTJ + 2][kLW];
+
+    const int bid = xcd_swizzle(blockIdx.x, gridDim.x, p.xcd);
+    const int b = find_box(p, bid);
+    const BoxLaunch B = p.box[b];
+    int local = bid - B.block_begin;
+    const int tk = local % B.tiles_k;
+    local /= B.tiles_k;
+    const int tj = local % B.tiles_j;
+    const int ci = local / B.tiles_j;
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int kb = B.kbase + tk * kTK;
+    const int k = kb + lane;
+    const int jt = B.j0 + tj * kTJ;
+    const int ib = B.i0 + ci * B.chunk;
+    const int ie = min(B.i1, ib + B.chunk - 1);
+
+    const bool kload = k <= p.kmax;
+    const bool kin = k >= B.k0 && k <= B.k1;
+    const i64 si = p.si;
+    const unsigned pbytes = unsigned(si) * ES;
+    // byte offset of (j,k) in a plane block (kOOB = masked: loads give 0, stores dropped)
+    auto boff = [&](int j, int kk, bool ok) { return ok ? unsigned(j * p.sj + kk + p.poff) * ES : kOOB; };
+    auto prs = [&](const T* base, int i) { return plane_rsrc(base + (i64(i) * si - p.poff), pbytes); };
+
+    unsigned oa[R], ou2[R], os[R];
+    bool valid[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int j = jt + w * R + r;
+        valid[r] = kin && j <= B.j1;
+        oa[r] = boff(j, k, kload && j <= p.jmax);
+        ou2[r] = boff(j, k, !FIRST && valid[r]);
+        os[r] = boff(j, k, valid[r]);  // stores, and the loads of m
+    }
+
+    // halo role of this lane: one LDS cell per plane
+    int hrow = 0, hcol = 0;
+    unsigned hoff = kOOB;
+    bool hon = false;
+    if (w == 0) {  // row jt-1
+        hon = true;
+        hoff = boff(jt - 1, k, kload);
+        hrow = 0;
+        hcol = 1 + lane;
+    } else if (w == kWaves - 1) {  // row jt+TJ
+        const int j = jt + kTJ;
+        hon = true;
+        hoff = boff(j, k, kload && j <= p.jmax);
+        hrow = kTJ + 1;
+        hcol = 1 + lane;
+    } else if (w == 1) {  // columns kb-1 (lanes 0..TJ-1) and kb+64 (lanes 32..32+TJ-1)
+        const int side = lane >> 5, rr = lane & 31;
+        const int j = jt + rr;
+        const int kk = side ? kb + kTK : kb - 1;
+        hon = rr < kTJ;
+        hoff = boff(j, kk, hon && j <= p.jmax && kk <= p.kmax);
+        hrow = 1 + rr;
+        hcol = side ? kTK + 1 : 0;
+    }
+    constexpr int kMAux = NTM ? 2 : 0;  // non-temporal m (read once per step)
+    constexpr int kStAux = 2;           // non-temporal stores (write-once stream)
+
+    T u1[4][R], u2[2][R], mm[2][R];
+    T hv[2];
+    {
+        const auto r0 = prs(p.u1, ib - 1), r1 = prs(p.u1, ib), r2 = prs(p.u1, ib + 1);
+        const auto q0 = prs(p.u2, ib), m0 = prs(p.m, ib);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            u1[0][r] = bld<T>(r0, oa[r]);
+            u1[1][r] = bld<T>(r1, oa[r]);
+            u1[2][r] = bld<T>(r2, oa[r]);
+            u1[3][r] = T(0);
+            u2[0][r] = FIRST ? T(0) : bld<T>(q0, ou2[r]);
+            u2[1][r] = T(0);
+            mm[0][r] = bld<T, kMAux>(m0, os[r]);
+            mm[1][r] = T(0);
+        }
+        hv[0] = bld<T>(r1, hoff);
+        hv[1] = T(0);
+    }
+    const T hx2 = p.hx2, hy2 = p.hy2, hz2 = p.hz2;
+    const T yx2 = p.yx2, yy2 = p.yy2, yz2 = p.yz2;
+
+    T ma = T(kErrInit);
+    T chk = T(0);  // sum of the values (commit_errors: nonfinite flag)
+
+    auto plane = [&](auto phase, const int i) {
+        constexpr int P = decltype(phase)::value;
+        constexpr int S0 = P & 3, S1 = (P + 1) & 3, S2 = (P + 2) & 3, S3 = (P + 3) & 3;
+        constexpr int H0 = P & 1, H1 = (P + 1) & 1;
+        // prefetch u1(i+2) (own rows), u1(i+1) (halo), u2(i+1), m(i+1); 0-record descriptors on
+        // the last plane (loads return 0 without touching memory)
+        {
+            const bool more = i < ie;
+            const unsigned nb = more ? pbytes : 0u;
+            const int d2 = more ? 2 : 0, d1 = more ? 1 : 0;
+            const auto rN = plane_rsrc(p.u1 + (i64(i + d2) * si - p.poff), nb);
+            const auto rH = plane_rsrc(p.u1 + (i64(i + d1) * si - p.poff), nb);
+            const auto rU = plane_rsrc(p.u2 + (i64(i + d1) * si - p.poff), nb);
+            const auto rM = plane_rsrc(p.m + (i64(i + d1) * si - p.poff), nb);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                u1[S3][r] = bld<T>(rN, oa[r]);
+                if (!FIRST) u2[H1][r] = bld<T>(rU, ou2[r]);
+                mm[H1][r] = bld<T, kMAux>(rM, os[r]);
+            }
+            hv[H1] = bld<T>(rH, hoff);
+        }
+
+        // stage plane i
+#pragma unroll
+        for (int r = 0; r < R; ++r) lds[H0][1 + w * R + r][1 + lane] = u1[S1][r];
+        if (hon) lds[H0][hrow][hcol] = hv[H0];
+        __syncthreads();
+
+        const bool erow = i >= p.ei0 && i <= p.ei1;
+        T vv[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int lr = 1 + w * R + r;
+            const T c = u1[S1][r];
+            const T jm = r == 0 ? lds[H0][lr - 1][1 + lane] : u1[S1][r - 1];
+            const T jp = r == R - 1 ? lds[H0][lr + 1][1 + lane] : u1[S1][r + 1];
+            const T km = lds[H0][lr][lane];
+            const T kp = lds[H0][lr][lane + 2];
+            const T lap = laplace7_cr(c, u1[S0][r], u1[S2][r], jm, jp, km, kp, hx2, hy2, hz2, yx2, yy2, yz2);
+            if constexpr (FIRST) {
+#pragma clang fp contract(off)
+                const T half_m = T(0.5) * mm[H0][r];  // exact
+                vv[r] = taylor_first(c, lap, half_m);
+            } else {
+                vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]);
+            }
+        }
+        // stores: own plane + fused periodic wrap (buffer stores, masked lanes dropped)
+        {
+            const auto rs = prs(p.u, i);
+#pragma unroll
+            for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rs, os[r]);
+#pragma unroll
+            for (int g = 0; g < 2; ++g)
+                if (i >= p.w_lo[g] && i <= p.w_hi[g]) {
+                    const auto rw = prs(p.u, i + p.w_sh[g]);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
+                }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (!valid[r]) continue;
+            chk += vv[r];
+            if (erow) ma = max_abs(ma, vv[r]);
+        }
+    };
+
+    for (int i = ib;;) {
+        plane(Ph<0>{}, i);
+        if (++i > ie) break;
+        plane(Ph<1>{}, i);
+        if (++i > ie) break;
+        plane(Ph<2>{}, i);
+        if (++i > ie) break;
+        plane(Ph<3>{}, i);
+        if (++i > ie) break;
+    }
+    // slot 1 keeps its initial key: atomicMax with that same key
+    commit_errors(ma, T(kErrInit), chk, p.err);
+}
+
+struct NodeGrid {
+    i64 si;
+    int sj;
+    int nx, ny, nz;  // storage extents: indices 0 .. n-1 exist
+};
+
+__device__ __forceinline__ bool node_offset(const NodeGrid& g, const int* nodes, int e, int& i, i64& row) {
+    i = nodes[3 * e];
+    const int j = nodes[3 * e + 1], k = nodes[3 * e + 2];
+    row = i64(j) * g.sj + k;
+    // the host validates the lists; a node outside the storage is skipped, never dereferenced
+    return i >= 0 && i < g.nx && j >= 0 && j < g.ny && k >= 0 && k < g.nz;
+}
+
+template <class T>
+__global__ void k_inject(T* u, const T* m, NodeGrid gr, const int* nodes, const T* g, int n, Wrap wrap) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    int i;
+    i64 row;
+    if (!node_offset(gr, nodes, e, i, row)) return;
+    const i64 o = i64(i) * gr.si + row;
+    const T add = m[o] * g[e];
+    const T v = u[o] + add;
+    u[o] = v;
+#pragma unroll
+    for (int q = 0; q < kMaxWrap; ++q)
+        if (wrap.src[q] >= 1 && i == wrap.src[q] && wrap.dst[q] >= 0 && wrap.dst[q] < gr.nx)
+            u[i64(wrap.dst[q]) * gr.si + row] = v;
+}
+
+template <class T>
+__global__ void k_record(const T* u, NodeGrid gr, const int* nodes, T* out, int n) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    int i;
+    i64 row;
+    if (!node_offset(gr, nodes, e, i, row)) return;
+    out[e] = u[i64(i) * gr.si + row];
+}
+
+NodeGrid node_grid(const GridView& gv) {
+    W3D_REQUIRE(gv.G == 1 && gv.poff == 0, "medium kernels: one ghost layer");
+    return NodeGrid{gv.si, gv.sj, gv.X + 2, gv.Y + 2, gv.Z + 2};
+}
+
+template <class T, bool FIRST>
+void (*march_m_kernel(int variant))(const MediumParams<T>) {
+    constexpr int RD = 4;  // march_rows_per_thread()
+    switch (variant & 3) {
+        case 1: return k_march_m<T, FIRST, RD, true>;
+        case 2: return k_march_m<T, FIRST, 2, false>;
+        case 3: return k_march_m<T, FIRST, 2, true>;
+        default: return k_march_m<T, FIRST, RD, false>;
+    }
+}
+
+}  // namespace
+
+int medium_variant() {
+    static const int v = [] {
+        const char* e = std::getenv("WAVE3D_MEDIUM_VARIANT");
+        const std::string s = e ? e : "";
+        if (s == "plain") return 0;
+        if (s == "r2") return 2;
+        if (s == "r2nt") return 3;
+        W3D_REQUIRE(s.empty() || s == "nt", "WAVE3D_MEDIUM_VARIANT must be nt, plain, r2 or r2nt, not " + s);
+        // non-temporal m loads, 4 rows per lane: the fastest of the four on MI355X at N = 512
+        // (profiles/medium_march.txt)
+        return 1;
+    }();
+    return v;
+}
+
+template <class T>
+void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
+                        const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
+                        const double h2[3], u64* err, int chunk, hipStream_t s, int variant) {
+    W3D_REQUIRE(nbox >= 1 && nbox <= kMaxBoxes, "bad box count");
+    W3D_REQUIRE(march_rows_per_thread() == 4, "k_march_m is instantiated for 4 rows per lane");
+    W3D_REQUIRE(gv.si > 0 && gv.si * i64(sizeof(T)) < (1ll << 31), "plane larger than a buffer descriptor's range");
+    W3D_REQUIRE(gv.sj >= gv.Z + 2 * gv.G && gv.si >= i64(gv.Y + 2 * gv.G) * gv.sj, "strides smaller than the grid");
+    if (variant < 0) variant = medium_variant();
+    MediumParams<T> p{};
+    p.xcd = xcd_swizzle_enabled();
+    p.u1 = u1;
+    p.u2 = u2;
+    p.m = m;
+    p.u = u;
+    p.si = gv.si;
+    p.sj = gv.sj;
+    p.poff = gv.poff;
+    p.jmax = gv.jmax();
+    p.kmax = gv.kmax();
+    p.ei0 = ei0;
+    p.ei1 = ei1;
+    for (int q = 0; q < kMaxWrap; ++q)
+        W3D_REQUIRE(wrap.src[q] < 1 || (wrap.src[q] <= gv.X && wrap.dst[q] >= 1 - gv.G && wrap.dst[q] <= gv.X + gv.G),
+                    "wrap plane outside the grid");
+    wrap_ranges(wrap, p.w_lo, p.w_hi, p.w_sh);
+    p.hx2 = T(h2[0]);
+    p.hy2 = T(h2[1]);
+    p.hz2 = T(h2[2]);
+    p.yx2 = T(1) / T(h2[0]);
+    p.yy2 = T(1) / T(h2[1]);
+    p.yz2 = T(1) / T(h2[2]);
+    p.err = err;
+    const int tj_rows = kWaves * ((variant & 2) ? 2 : 4);
+    int btiles[kMaxBoxes], bplanes[kMaxBoxes], nbt = 0;
+    for (int q = 0; q < nbox; ++q) {
+        const Box& bx = boxes[q];
+        if (bx.empty()) continue;
+        btiles[nbt] = ((bx.k1 - 1) / kTK - (bx.k0 - 1) / kTK + 1) * cdiv(bx.j1 - bx.j0 + 1, tj_rows);
+        bplanes[nbt++] = bx.i1 - bx.i0 + 1;
+    }
+    // launch_step's march path: 32-plane work items, shorter on small grids
+    const int achunk = auto_chunk_boxes(32, btiles, bplanes, nbt);
+    int nb = 0, total = 0;
+    for (int q = 0; q < nbox; ++q) {
+        const Box& bx = boxes[q];
+        if (bx.empty()) continue;
+        W3D_REQUIRE(bx.i0 >= 1 && bx.i1 <= gv.X && bx.j0 >= 1 && bx.j1 <= gv.Y && bx.k0 >= 1 && bx.k1 <= gv.Z,
+                    "step box outside the owned region");
+        BoxLaunch& L = p.box[nb];
+        L.i0 = bx.i0, L.i1 = bx.i1, L.j0 = bx.j0, L.j1 = bx.j1, L.k0 = bx.k0, L.k1 = bx.k1;
+        const int t0 = (bx.k0 - 1) / kTK, t1 = (bx.k1 - 1) / kTK;
+        L.kbase = 1 + t0 * kTK;
+        L.tiles_k = t1 - t0 + 1;
+        L.tiles_j = cdiv(bx.j1 - bx.j0 + 1, tj_rows);
+        const int planes = bx.i1 - bx.i0 + 1;
+        int ch = std::min(chunk > 0 ? chunk : achunk, planes);
+        ch = cdiv(planes, cdiv(planes, ch));  // equal work items (no short tail chunk)
+        L.chunk = ch;
+        L.block_begin = total;
+        total += L.tiles_k * L.tiles_j * cdiv(planes, ch);
+        ++nb;
+    }
+    p.nbox = nb;
+    if (nb == 0) return;
+    void (*kern)(const MediumParams<T>) = first ? march_m_kernel<T, true>(variant) : march_m_kernel<T, false>(variant);
+    hipLaunchKernelGGL(kern, dim3(total), dim3(kThreads), 0, s, p);
+    HIP_OK(hipGetLastError());
+}
+
+template <class T>
+void launch_inject(T* u, const T* m, const GridView& gv, const int* nodes, const T* g, int n,
+                   const Wrap& wrap, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_inject<T>, dim3(cdiv(n, 64)), dim3(64), 0, s, u, m, node_grid(gv), nodes, g, n, wrap);
+    HIP_OK(hipGetLastError());
+}
+
+template <class T>
+void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int n, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_record<T>, dim3(cdiv(n, 64)), dim3(64), 0, s, u, node_grid(gv), nodes, out, n);
+    HIP_OK(hipGetLastError());
+}
+
+#define W3D_MEDIUM_INST(T)                                                                              \
+    template void launch_step_medium<T>(bool, const T*, const T*, const T*, T*, const GridView&,       \
+                                        const Box*, int, int, int, const Wrap&, const double[3], u64*, \
+                                        int, hipStream_t, int);                                        \
+    template void launch_inject<T>(T*, const T*, const GridView&, const int*, const T*, int,           \
+                                   const Wrap&, hipStream_t);                                          \
+    template void launch_record<T>(const T*, const GridView&, const int*, T*, int, hipStream_t);
+W3D_MEDIUM_INST(double)
+W3D_MEDIUM_INST(float)
+
+}  // namespace wave3d

@@ -1,0 +1,38 @@
+// Heterogeneous-medium kernels (hip_medium.hip): u_tt = c(x,y,z)^2 (lap u + f) on the box, grid
+// and boundary conditions of the constant-speed solver, with point sources and receivers.
+//
+// The per-node coefficient field m = c^2 tau^2 is stored like a time level (GridView, one ghost
+// layer); a step reads u^{n-1}, u^{n-2} and m once and writes u^n once: 32 B per node in fp64.
+#pragma once
+
+#include "hip_kernels.hpp"
+
+namespace wave3d {
+
+// One time layer n >= 1 over `nbox` boxes: u = (2 u1 - u2) + m lap(u1), or on the Taylor start
+// (`first`) u = u1 + (0.5 m) lap(u1), rounded operation by operation in that order (a uniform
+// m == coef reproduces launch_step's march kernel bit for bit). h2 = (hx*hx, hy*hy, hz*hz).
+// err[0] = key of max |u| over the planes [ei0, ei1] (NaN ignored), err[1] untouched,
+// err[2] = non-finite flag. variant: -1 = WAVE3D_MEDIUM_VARIANT or the default; bit 0 =
+// non-temporal loads of m, bit 1 = 2 rows per lane instead of march_rows_per_thread().
+template <class T>
+void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
+                        const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
+                        const double h2[3], u64* err, int chunk, hipStream_t s, int variant = -1);
+
+// Point sources: u(node[e]) += m(node[e]) * g[e] for e < n (the product rounded, then the add);
+// an entry on a wrap source plane is also copied to its ghost plane. nodes = n x (i, j, k),
+// logical indices; no two entries may name the same node (the caller checks).
+template <class T>
+void launch_inject(T* u, const T* m, const GridView& gv, const int* nodes, const T* g, int n,
+                   const Wrap& wrap, hipStream_t s);
+
+// Receivers: out[r] = u(node[r]) for r < n.
+template <class T>
+void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int n, hipStream_t s);
+
+// default variant of launch_step_medium: 1 ("nt"), or env WAVE3D_MEDIUM_VARIANT = "plain" (0),
+// "r2" (2), "r2nt" (3) for ablation
+int medium_variant();
+
+}  // namespace wave3d

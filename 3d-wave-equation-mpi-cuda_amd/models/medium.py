@@ -1,0 +1,238 @@
+"""Variable-speed medium front-end: ``(1/c^2) u_tt = lap u + f`` with point sources and receivers.
+
+``MediumProblem`` describes the box, the grid and the squared wave speed c^2(x, y, z) on the
+constant-speed solver's grid (``N+1`` nodes per axis, periodic in x with planes 0 and N both
+stencil points, Dirichlet 0 on the y/z faces, zero initial velocity); ``MediumSolver`` runs it on
+one GPU through the HIP kernels of ``csrc/hip_medium.hip`` or on the PyTorch oracle
+(``ops.reference.solve_medium``).
+"""
+from __future__ import annotations
+
+import math
+import warnings
+from dataclasses import dataclass, field
+from typing import Any
+
+import torch
+
+from .wave import CFL_LIMIT, PI_REF
+
+_DTYPES = {"fp64": torch.float64, "fp32": torch.float32}
+
+
+class MediumProblem:
+    """N intervals per axis, ``speed2`` = c^2 as a float or an ``(N+1)^3`` array/tensor."""
+
+    def __init__(self, N: int, speed2, Lx: Any = "pi", Ly: Any = "pi", Lz: Any = "pi", T: float = 1.0,
+                 timesteps: int = 20, dtype: str = "fp64", pi: str = "ref", strict_cfl: bool = True):
+        if dtype not in _DTYPES:
+            raise ValueError(f"dtype must be fp64 or fp32, not {dtype!r}")
+        if N < 2 or timesteps < 1:
+            raise ValueError(f"need N >= 2 and timesteps >= 1, not N={N} timesteps={timesteps}")
+        self.N, self.Lx, self.Ly, self.Lz = int(N), Lx, Ly, Lz
+        self.T, self.timesteps, self.dtype, self.pi = float(T), int(timesteps), dtype, pi
+        s = torch.as_tensor(speed2, dtype=torch.float64).cpu()
+        n1 = self.N + 1
+        if s.dim() != 0 and tuple(s.shape) != (n1, n1, n1):
+            raise ValueError(f"speed2 must be a scalar or have shape {(n1, n1, n1)}, not {tuple(s.shape)}")
+        bad = ~(torch.isfinite(s) & (s > 0))
+        if bool(bad.any()):
+            v = s[bad].flatten()[0].item() if s.dim() else s.item()
+            raise ValueError(f"speed2 must be finite and > 0, found {v}")
+        if s.dim() != 0 and not torch.equal(s[0], s[self.N]):
+            j, k = (int(x) for x in (s[0] != s[self.N]).nonzero()[0])
+            raise ValueError(f"speed2 must be periodic in x: speed2[0,{j},{k}] = {s[0, j, k].item()} but "
+                             f"speed2[{self.N},{j},{k}] = {s[self.N, j, k].item()}")
+        self.speed2 = s
+        self.max_speed2 = float(s.max())
+        if self.courant > CFL_LIMIT:
+            msg = (f"Courant number {self.courant:.4g} exceeds the stability limit {CFL_LIMIT:.4g}: "
+                   f"needs timesteps >= {self.min_stable_timesteps()}")
+            if strict_cfl:
+                raise ValueError(msg)
+            warnings.warn(msg, RuntimeWarning, stacklevel=2)
+
+    def _pi(self) -> float:
+        return PI_REF if self.pi == "ref" else math.pi
+
+    def lengths(self) -> tuple[float, float, float]:
+        p = self._pi()
+        return tuple(p if v == "pi" else float(v) for v in (self.Lx, self.Ly, self.Lz))
+
+    @property
+    def tau(self) -> float:
+        return self.T / self.timesteps
+
+    @property
+    def courant(self) -> float:
+        return math.sqrt(self.max_speed2) * self.tau / (min(self.lengths()) / self.N)
+
+    def stable(self) -> bool:
+        return self.courant <= CFL_LIMIT
+
+    def min_stable_timesteps(self) -> int:
+        return math.ceil(math.sqrt(self.max_speed2) * self.T * self.N / (min(self.lengths()) * CFL_LIMIT))
+
+    @property
+    def points(self) -> int:
+        return (self.N + 1) ** 3
+
+    @property
+    def torch_dtype(self):
+        return _DTYPES[self.dtype]
+
+
+def ricker(f0: float, t0: float, K: int, tau: float) -> torch.Tensor:
+    """Ricker wavelet (1 - 2a) exp(-a), a = (pi f0 (t - t0))^2, at t_n = n tau for n = 0..K-1."""
+    t = torch.arange(K, dtype=torch.float64) * tau
+    a = (math.pi * f0 * (t - t0)) ** 2
+    return (1 - 2 * a) * torch.exp(-a)
+
+
+@dataclass
+class MediumResult:
+    traces: torch.Tensor     # [K+1, R], row 0 = the initial field
+    u_final: torch.Tensor    # (N+1)^3
+    max_abs_u: list          # [K+1]: max |u| over the stencil nodes, before the step's source term
+    courant: float
+    total_ms: float
+    mpts_per_s: float
+    aborted: bool = False
+    abort_layer: int = -1
+    abort_reason: str = ""
+    extra: dict = field(default_factory=dict)
+
+
+class MediumSolver:
+    """Run a :class:`MediumProblem` from rest.
+
+    backend     "hip" (MI355X kernels, one GPU) or "cpu" (the PyTorch oracle)
+    u0          initial field, ``(N+1)^3`` (default 0); used as given, face values included
+    sources     global (i, j, k) nodes off the Dirichlet faces, all distinct (planes 0 and N are
+                the same periodic plane)
+    wavelet     ``[timesteps, len(sources)]``: f_s(t_n), n = 0..K-1 (see :func:`ricker`)
+    receivers   global (i, j, k) nodes
+    check_every >0 ("hip"): read the non-finite flag every that many steps and stop early
+    variant     ablation only: k_march_m variant ("nt", "plain", "r2", "r2nt"; ops.kernels.step_medium)
+    """
+
+    def __init__(self, problem: MediumProblem, backend: str = "hip", *, u0=None, sources=(), wavelet=None,
+                 receivers=(), check_every: int = 0, device: int | None = None, variant: str | None = None):
+        if backend not in ("hip", "cpu"):
+            raise ValueError(f"unknown backend {backend!r}")
+        N, K = problem.N, problem.timesteps
+        self.problem, self.backend, self.check_every, self.device = problem, backend, int(check_every), device
+        self.variant = variant
+        self.sources = [tuple(int(v) for v in s) for s in sources]
+        self.receivers = [tuple(int(v) for v in r) for r in receivers]
+        seen = set()
+        for s in self.sources:
+            if len(s) != 3 or not all(0 <= v <= N for v in s):
+                raise ValueError(f"source {s} outside the grid 0..{N}")
+            if s[1] in (0, N) or s[2] in (0, N):
+                raise ValueError(f"source {s} lies on a Dirichlet face")
+            key = (s[0] % N, s[1], s[2])  # planes 0 and N are one plane
+            if key in seen:
+                raise ValueError(f"source {s} given more than once")
+            seen.add(key)
+        for r in self.receivers:
+            if len(r) != 3 or not all(0 <= v <= N for v in r):
+                raise ValueError(f"receiver {r} outside the grid 0..{N}")
+        if self.sources:
+            if wavelet is None:
+                raise ValueError("sources need a wavelet of shape [timesteps, len(sources)]")
+            w = torch.as_tensor(wavelet, dtype=torch.float64)
+            if tuple(w.shape) != (K, len(self.sources)):
+                raise ValueError(f"wavelet must have shape {(K, len(self.sources))} (timesteps x sources), "
+                                 f"not {tuple(w.shape)}")
+            self.wavelet = w
+        else:
+            self.wavelet = None
+        if u0 is not None:
+            u0 = torch.as_tensor(u0)
+            if tuple(u0.shape) != (N + 1, N + 1, N + 1):
+                raise ValueError(f"u0 must have shape {(N + 1,) * 3}, not {tuple(u0.shape)}")
+        self.u0 = u0
+
+    def run(self) -> MediumResult:
+        return self._run_cpu() if self.backend == "cpu" else self._run_hip()
+
+    def _result(self, traces, u_final, mx, ms, **kw) -> MediumResult:
+        p = self.problem
+        rate = p.points * (len(mx) - 1) / (ms * 1e3) if ms > 0 else 0.0  # Mpoints/s over the layers done
+        return MediumResult(traces=traces, u_final=u_final, max_abs_u=mx, courant=p.courant, total_ms=ms,
+                            mpts_per_s=rate, **kw)
+
+    def _run_cpu(self) -> MediumResult:
+        import time
+
+        from ..ops import reference
+
+        p = self.problem
+        t0 = time.perf_counter()
+        tr, uf, mx = reference.solve_medium(p.N, p.timesteps, p.speed2, u0=self.u0, sources=self.sources,
+                                            wavelet=self.wavelet, receivers=self.receivers,
+                                            L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype)
+        return self._result(tr, uf, mx, (time.perf_counter() - t0) * 1e3)
+
+    def _run_hip(self) -> MediumResult:
+        from ..ops import kernels, reference
+
+        p = self.problem
+        N, K, dt = p.N, p.timesteps, p.torch_dtype
+        if not torch.cuda.is_available():
+            raise RuntimeError("the hip backend needs a HIP device")
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else self.device)
+        c = reference.tables(N, K, (p.Lx, p.Ly, p.Lz), p.T, p.pi)[4]
+        h2 = (c["hx2"], c["hy2"], c["hz2"])
+        with torch.cuda.device(dev):
+            lv = [kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(3)]
+            m = kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev)
+            m.copy_(reference.medium_coefficient(p.speed2, c["tau"], N, dt))
+            if self.u0 is not None:
+                lv[0][1:N + 2] = self.u0.to(dt).to(dev)
+                lv[0][0] = lv[0][N]
+                lv[0][N + 2] = lv[0][2]
+            ent = reference.source_entries(self.sources, N)
+            g = reference.source_table(self.wavelet, K, len(self.sources), c["hx"], c["hy"], c["hz"], dt)
+            g = g[:, [s for _, s in ent]].contiguous().to(dev)  # one column per storage node
+            src = kernels.source_nodes([nd for nd, _ in ent], lv[0])
+            rec = kernels.receiver_nodes([(i + 1, j, k) for i, j, k in self.receivers], lv[0])
+            traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
+            stat = kernels.new_err(K + 1, device=dev)
+            box = (1, N + 1, 1, N - 1, 1, N - 1)
+            wrap = (N, 0, 2, N + 2)
+            mx0 = reference.max_abs_field(lv[0][1:N + 2, 1:N, 1:N])
+            kernels.record(lv[0], rec, traces[0])
+            abort = {}
+            done = K
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            for n in range(1, K + 1):
+                u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
+                if n == 3:  # level 0 comes round: the faces of the given u0 become Dirichlet zeros
+                    u[:, 0, :] = 0
+                    u[:, N, :] = 0
+                    u[:, :, 0] = 0
+                    u[:, :, N] = 0
+                kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=stat[3 * n:3 * n + 3],
+                                    stat_i=(1, N + 1), wrap=wrap, variant=self.variant)
+                kernels.inject(u, m, src, g[n - 1], wrap)
+                kernels.record(u, rec, traces[n])
+                if self.check_every > 0 and n % self.check_every == 0:
+                    flags = stat[2:3 * n + 3:3].cpu()  # one read-back: the flags of layers 0..n
+                    if bool((flags != 0).any()):
+                        abort = dict(aborted=True, abort_layer=int((flags != 0).nonzero()[0]),
+                                     abort_reason="non-finite values")
+                        done = n
+                        break
+            ev1.record()
+            ev1.synchronize()
+            ms = ev0.elapsed_time(ev1)
+            dec = kernels.decode_err(stat)  # the one read-back of the statistics
+            mx = [mx0] + [dec[n][0] for n in range(1, done + 1)]
+            extra = {}
+            if not abort and any(d[2] for d in dec[1:]):  # ran to the end, but not on finite values
+                extra["nonfinite_layer"] = next(n for n in range(1, K + 1) if dec[n][2])
+            uf = lv[done % 3][1:N + 2].cpu()
+            return self._result(traces.cpu(), uf, mx, ms, extra=extra, **abort)

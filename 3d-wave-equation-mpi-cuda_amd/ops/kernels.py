@@ -4,7 +4,8 @@ Tensors are dense ``[nx][ny][nz]`` (k contiguous, one ghost layer) on the curren
 device; they are passed to the native kernels as raw pointers on torch's current stream.
 Shapes are validated here *before* any launch (the kernels index with the boxes given).
 The solver itself uses an aligned, padded layout (``csrc/hip_kernels.hpp``); these entry
-points use pitch = nz, which the kernels accept as well.
+points use pitch = nz, which the kernels accept as well; the medium ops (``step_medium``,
+``inject``, ``record``) also take views in that padded layout (``alloc_level``).
 """
 from __future__ import annotations
 
@@ -231,3 +232,161 @@ def tb3_sweep(A, B, D, E, boxes, *, first: bool, cdom, err_i, tx, ty, tz, coefs_
        ty.data_ptr(), tz.data_ptr(), [float(c) for c in coefs_c], [float(c) for c in coefs_d],
        [float(c) for c in coefs_e], err_c.data_ptr(), err_d.data_ptr(), err_e.data_ptr(),
        int(chunk), _stream())
+
+
+# ---- heterogeneous medium (csrc/hip_medium.hip) -----------------------------------------
+
+def alloc_level(nx: int, ny: int, nz: int, dtype, device=None) -> torch.Tensor:
+    """A zeroed ``[nx][ny][nz]`` level in the solver's aligned layout (``csrc/hip_kernels.hpp``):
+    a view into a padded allocation whose row pitch is a multiple of 128 B and whose elements
+    ``(., ., k=1)`` are 128-B aligned, so every 64-lane k-tile (k = 1 + 64 t) is whole cache lines."""
+    if min(nx, ny, nz) < 3:
+        raise ValueError("grid needs at least one owned node plus ghosts per axis")
+    es = torch.empty((), dtype=dtype).element_size()
+    line = 128 // es
+    sj = -(-nz // line) * line
+    si = ny * sj
+    off = line - 1  # the k = 0 column sits in front of the aligned k = 1
+    buf = torch.zeros(off + nx * si, dtype=dtype, device=device or "cuda")
+    if buf.data_ptr() % 128:
+        raise RuntimeError("allocator returned a buffer that is not 128-B aligned")
+    return buf.as_strided((nx, ny, nz), (si, sj, 1), off)
+
+
+def _check_grid_strided(*ts: torch.Tensor) -> list[int]:
+    """Grids that are dense or padded views (last stride 1), all with the same strides."""
+    u = ts[0]
+    for t in ts:
+        if not t.is_cuda:
+            raise ValueError("wave3d kernels need HIP device tensors")
+        if t.dim() != 3:
+            raise ValueError("grids must be 3-D [nx][ny][nz] tensors")
+        if t.shape != u.shape or t.dtype != u.dtype or t.device != u.device:
+            raise ValueError("grid shapes/dtypes/devices differ")
+        if t.stride() != u.stride():
+            raise ValueError(f"grid strides differ: {t.stride()} vs {u.stride()}")
+    nx, ny, nz = u.shape
+    if min(nx, ny, nz) < 3:
+        raise ValueError("grid needs at least one owned node plus ghosts per axis")
+    si, sj, sk = u.stride()
+    if sk != 1 or sj < nz or si < ny * sj:
+        raise ValueError(f"grid strides {u.stride()}: k must be contiguous, rows and planes must not overlap")
+    if si * u.element_size() >= 1 << 31:
+        raise ValueError("a plane must be smaller than 2 GiB")
+    _sfx(u)
+    return [nx, ny, nz, sj, si]
+
+
+def _check_wrap(wrap, gv) -> list[int]:
+    if wrap is None:
+        return []
+    w = [int(v) for v in wrap]
+    if len(w) % 2 or len(w) > 16:
+        raise ValueError("wrap = (src, dst, ...) pairs, at most 8")
+    for q in range(0, len(w), 2):
+        if w[q] >= 0 and not (0 <= w[q + 1] < gv[0] and 1 <= w[q] <= gv[0] - 2):
+            raise ValueError(f"bad wrap planes {w[q]} -> {w[q + 1]}")
+    return w
+
+
+class NodeList:
+    """Validated (i, j, k) nodes of a grid, uploaded once (int32 ``[n][3]`` on the device)."""
+
+    def __init__(self, nodes, shape, device, *, owned: bool, distinct: bool):
+        nx, ny, nz = shape
+        lst = [tuple(int(v) for v in nd) for nd in nodes]
+        lo, hi = (1, 2) if owned else (0, 1)
+        for nd in lst:
+            if len(nd) != 3 or not all(lo <= v <= n - hi for v, n in zip(nd, (nx, ny, nz))):
+                raise ValueError(f"node {nd} outside the {'owned region' if owned else 'storage'} of a "
+                                 f"{nx}x{ny}x{nz} grid")
+        if distinct and len(set(lst)) != len(lst):
+            dup = sorted(nd for nd in set(lst) if lst.count(nd) > 1)
+            raise ValueError(f"node {dup[0]} named more than once")
+        self.shape, self.nodes, self.owned, self.distinct = (nx, ny, nz), lst, owned, distinct
+        self.dev = torch.tensor(lst, dtype=torch.int32).reshape(len(lst), 3).to(device)
+
+    def __len__(self):
+        return len(self.nodes)
+
+
+def _node_list(nodes, u, *, owned: bool, distinct: bool) -> NodeList:
+    if isinstance(nodes, NodeList):
+        if nodes.shape != tuple(u.shape) or nodes.dev.device != u.device:
+            raise ValueError("node list was built for another grid")
+        if (owned and not nodes.owned) or (distinct and not nodes.distinct):
+            raise ValueError("node list was not validated for this use")
+        return nodes
+    return NodeList(nodes, u.shape, u.device, owned=owned, distinct=distinct)
+
+
+def source_nodes(nodes, u) -> NodeList:
+    """Nodes for :func:`inject`: inside the owned region of ``u`` and distinct."""
+    return NodeList(nodes, u.shape, u.device, owned=True, distinct=True)
+
+
+def receiver_nodes(nodes, u) -> NodeList:
+    """Nodes for :func:`record`: anywhere in the storage of ``u``."""
+    return NodeList(nodes, u.shape, u.device, owned=False, distinct=False)
+
+
+_MEDIUM_VARIANTS = {None: -1, "plain": 0, "nt": 1, "r2": 2, "r2nt": 3}
+
+
+def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None, chunk: int = 0,
+                variant: str | None = None) -> None:
+    """One layer of ``u_tt = c^2 (lap u + f)`` over ``boxes``: ``u = (2 u1 - u2) + m lap(u1)``, on
+    the Taylor start (``first``) ``u = u1 + (0.5 m) lap(u1)``, with ``m = c^2 tau^2`` per node.
+
+    The grids are dense ``[nx][ny][nz]`` tensors or :func:`alloc_level` views with identical
+    strides. h2 = (hx2, hy2, hz2); stat = >= 3 int64 slots (``new_err()``): slot 0 receives the
+    key of max |u| over the planes stat_i = (ei0, ei1), slot 2 the non-finite flag; wrap as in
+    :func:`step`. ``variant`` (ablation; the results are the same bit for bit): "nt" non-temporal
+    loads of m with 4 rows per lane (the default, None), "plain" ordinary loads of m, "r2" / "r2nt"
+    the same with 2 rows per lane.
+    """
+    gv = _check_grid_strided(u1, u2, m, u)
+    if isinstance(boxes[0], int):
+        boxes = [boxes]
+    if not 1 <= len(boxes) <= 7:
+        raise ValueError("1..7 boxes per launch")
+    bl = [_check_box(b, gv) for b in boxes]
+    if len(h2) != 3 or not all(float(v) > 0 for v in h2):
+        raise ValueError("h2 = (hx2, hy2, hz2), all > 0")
+    if stat.dtype != torch.int64 or stat.numel() < 3 or not stat.is_cuda or not stat.is_contiguous():
+        raise ValueError("stat must be >= 3 contiguous int64 device slots (new_err())")
+    w = _check_wrap(wrap, gv)
+    if variant not in _MEDIUM_VARIANTS:
+        raise ValueError(f"unknown variant {variant!r}")
+    fn = getattr(_C(), "k_step_medium_" + _sfx(u))
+    fn(bool(first), u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, bl, int(stat_i[0]),
+       int(stat_i[1]), w, [float(v) for v in h2], stat.data_ptr(), int(chunk), _stream(),
+       _MEDIUM_VARIANTS[variant])
+
+
+def inject(u, m, nodes, g, wrap=None) -> None:
+    """Point sources: ``u[node_s] += m[node_s] * g[s]`` (the product rounded, then the add); a node
+    on a wrap source plane is also copied to its ghost plane. ``nodes``: (i, j, k) tuples inside
+    the owned region, all distinct, or a :func:`source_nodes` list; ``g``: one value per node."""
+    gv = _check_grid_strided(u, m)
+    nl = _node_list(nodes, u, owned=True, distinct=True)
+    if not g.is_cuda or g.device != u.device or g.dtype != u.dtype or not g.is_contiguous() or g.numel() < len(nl):
+        raise ValueError(f"g must be a contiguous {u.dtype} device tensor of >= {len(nl)} values")
+    w = _check_wrap(wrap, gv)
+    if len(nl) == 0:
+        return
+    getattr(_C(), "k_inject_" + _sfx(u))(u.data_ptr(), m.data_ptr(), gv, nl.dev.data_ptr(), g.data_ptr(),
+                                        len(nl), w, _stream())
+
+
+def record(u, nodes, out) -> None:
+    """Receivers: ``out[r] = u[node_r]``. ``nodes``: (i, j, k) tuples anywhere in the storage, or a
+    :func:`receiver_nodes` list."""
+    gv = _check_grid_strided(u)
+    nl = _node_list(nodes, u, owned=False, distinct=False)
+    if (not out.is_cuda or out.device != u.device or out.dtype != u.dtype or not out.is_contiguous()
+            or out.numel() < len(nl)):
+        raise ValueError(f"out must be a contiguous {u.dtype} device tensor of >= {len(nl)} values")
+    if len(nl) == 0:
+        return
+    getattr(_C(), "k_record_" + _sfx(u))(u.data_ptr(), gv, nl.dev.data_ptr(), out.data_ptr(), len(nl), _stream())

@@ -175,3 +175,114 @@ def chained_layers(A, B, nlayers: int, *, first: bool, mask, hx2, hy2, hz2, coef
         out.append(v)
         prev2, prev1 = prev1, v
     return out
+
+
+# ---- heterogeneous medium: u_tt = c^2 (lap u + f) -----------------------------------------
+
+def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2) -> torch.Tensor:
+    """Layer update on ``box`` with the per-node coefficient ``m = c^2 tau^2``: the Taylor start
+    ``c + (0.5 m) lap`` or ``(2c - u2) + m lap``; returns the updated box values."""
+    i0, i1, j0, j1, k0, k1 = box
+    lap = laplace7(u1, hx2, hy2, hz2)[i0 - 1:i1, j0 - 1:j1, k0 - 1:k1]
+    c = u1[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
+    mb = m[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
+    if first:
+        return c + (0.5 * mb) * lap
+    return (2 * c - u2[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]) + mb * lap
+
+
+def max_abs_field(u: torch.Tensor, init: float = -100.0) -> float:
+    """max |u| with the NaN-ignoring rule of ``max_errors``."""
+    a = u.abs()
+    neg = torch.tensor(-math.inf, dtype=u.dtype, device=u.device)
+    return max(torch.where(torch.isnan(a), neg, a).max().item() if a.numel() else -math.inf, init)
+
+
+def medium_coefficient(speed2, tau: float, N: int, dtype) -> torch.Tensor:
+    """m = ((speed2 * tau) * tau), left to right in float64, then cast: ``[N+3][N+1][N+1]`` in
+    ``solve()``'s storage (x ghosts filled periodically)."""
+    s = torch.as_tensor(speed2, dtype=torch.float64)
+    if s.dim() == 0:
+        s = s.expand(N + 1, N + 1, N + 1)
+    if tuple(s.shape) != (N + 1, N + 1, N + 1):
+        raise ValueError(f"speed2 must be a scalar or have shape {(N + 1,) * 3}, not {tuple(s.shape)}")
+    m = torch.zeros(N + 3, N + 1, N + 1, dtype=dtype)
+    m[1:N + 2] = ((s * tau) * tau).to(dtype)
+    m[0] = m[N]
+    m[N + 2] = m[2]
+    return m
+
+
+def source_table(wavelet, K: int, S: int, hx: float, hy: float, hz: float, dtype) -> torch.Tensor:
+    """g[n-1, s] = f_s(t_{n-1}) / (hx*hy*hz) in float64, row 0 halved (Taylor start), then cast."""
+    if S == 0:
+        return torch.zeros(K, 0, dtype=dtype)
+    if wavelet is None:
+        raise ValueError("sources need a wavelet of shape [K, S]")
+    w = torch.as_tensor(wavelet, dtype=torch.float64)
+    if tuple(w.shape) != (K, S):
+        raise ValueError(f"wavelet must have shape {(K, S)} (timesteps x sources), not {tuple(w.shape)}")
+    g = w / (hx * hy * hz)
+    if K > 0:
+        g[0] = g[0] * 0.5
+    return g.to(dtype)
+
+
+def source_entries(sources, N: int) -> list[tuple[tuple[int, int, int], int]]:
+    """Storage nodes of the sources, ((local i, j, k), column of the source table): local =
+    global + 1 in x; a source on the periodic plane 0 or N acts on both planes."""
+    out = []
+    for s, (i, j, k) in enumerate(sources):
+        for gi in ((0, N) if i in (0, N) else (i,)):
+            out.append(((gi + 1, j, k), s))
+    return out
+
+
+def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, receivers=(),
+                 L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, device="cpu"):
+    """Whole single-domain solve of ``(1/c^2) u_tt = lap u + f`` from rest in PyTorch, in
+    ``solve()``'s storage (x ghosts, local = global + 1).
+
+    speed2: c^2, a scalar or ``(N+1)^3``; u0: the initial field (``(N+1)^3``, default 0), used as
+    given, face values included; sources / receivers: global (i, j, k) nodes; wavelet ``[K, S]``:
+    f_s at t_n = n tau, n = 0..K-1. Step n adds ``m[x_s] * g[n-1, s]`` after the stencil and before
+    the periodic wrap. Returns (traces ``[K+1, R]`` with row 0 the initial field, u_K ``(N+1)^3``,
+    max |u| per layer ``[K+1]``: over the stencil nodes, of the step's result before its source term).
+    """
+    c = tables(N, K, L, T, pi)[4]
+    m = medium_coefficient(speed2, c["tau"], N, dtype).to(device)
+    ent = source_entries(sources, N)
+    g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype).to(device)
+    lv = [torch.zeros(N + 3, N + 1, N + 1, dtype=dtype, device=device) for _ in range(3)]
+
+    def wrap(u):
+        u[0] = u[N]
+        u[N + 2] = u[2]
+
+    if u0 is not None:
+        u0 = torch.as_tensor(u0)
+        if tuple(u0.shape) != (N + 1, N + 1, N + 1):
+            raise ValueError(f"u0 must have shape {(N + 1,) * 3}, not {tuple(u0.shape)}")
+        lv[0][1:N + 2] = u0.to(dtype).to(device)
+        wrap(lv[0])
+    rec = [(i + 1, j, k) for i, j, k in receivers]
+    traces = torch.zeros(K + 1, len(rec), dtype=dtype, device=device)
+
+    def sample(n, u):
+        for r, nd in enumerate(rec):
+            traces[n, r] = u[nd]
+
+    sample(0, lv[0])
+    box = (1, N + 1, 1, N - 1, 1, N - 1)
+    mx = [max_abs_field(lv[0][1:N + 2, 1:N, 1:N])]
+    for n in range(1, K + 1):
+        u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
+        u.zero_()
+        vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"])
+        mx.append(max_abs_field(vals))
+        u[1:N + 2, 1:N, 1:N] = vals
+        for nd, s in ent:
+            u[nd] = u[nd] + m[nd] * g[n - 1, s]
+        wrap(u)
+        sample(n, u)
+    return traces, lv[K % 3][1:N + 2].clone(), mx

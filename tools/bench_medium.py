@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Throughput of the variable-speed medium step (k_march_m) beside its yardstick, k_march.
+
+    python tools/bench_medium.py [--N 512] [--steps 100] [--dtypes fp64,fp32]
+                                 [--variants default,plain,r2,r2nt] [--repeat 3] [--no-yardstick]
+
+For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
+and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
+the variants alternating inside each repeat. The yardstick is the constant-speed solver with
+`--kernel march --math exact` at the same N and steps in the same process. Effective bandwidth
+counts the bytes the algorithm needs: u1, u2, m read and u written once per node (32 B in fp64,
+16 B in fp32) for the medium step, 24 B / 12 B for the yardstick. Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def smooth_speed2(N: int, lo: float, hi: float, seed: int = 7):
+    """Random 9^3 control values, trilinearly interpolated to (N+1)^3, periodic in x."""
+    import torch
+    import torch.nn.functional as F
+
+    g = torch.Generator().manual_seed(seed)
+    ctl = torch.rand(1, 1, 9, 9, 9, generator=g, dtype=torch.float64)
+    ctl[:, :, -1] = ctl[:, :, 0]
+    s = F.interpolate(ctl, size=(N + 1,) * 3, mode="trilinear", align_corners=True)[0, 0]
+    s = lo + (hi - lo) * s
+    s[N] = s[0]
+    return s.contiguous()
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--N", type=int, default=512)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--dtypes", default="fp64,fp32")
+    ap.add_argument("--variants", default="default")
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--no-yardstick", action="store_true")
+    a = ap.parse_args(argv)
+
+    import math
+
+    import torch
+
+    import wave3d
+
+    if not torch.cuda.is_available():
+        print("bench_medium: no HIP device (timings are only taken on the GPU)", file=sys.stderr)
+        return 2
+    N, K = a.N, a.steps
+    variants = a.variants.split(",")
+    # speed2 <= hi keeps the Courant number at 0.9 of the limit 1/sqrt(3) for T = 1
+    h = 3.1415926535 / N
+    hi = (0.9 / math.sqrt(3) * h * K) ** 2
+    speed2 = smooth_speed2(N, 0.5 * hi, hi)
+    nodes = float(N + 1) ** 3
+    out = {"N": N, "steps": K, "device": torch.cuda.get_device_name(0), "runs": []}
+    for dtype in a.dtypes.split(","):
+        es = 8 if dtype == "fp64" else 4
+        prob = wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype)
+        w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
+        mid = N // 2
+
+        def solver(v):
+            return wave3d.MediumSolver(prob, "hip", sources=[(mid, mid, mid)], wavelet=w,
+                                       receivers=[(mid // 2, mid, mid)], variant=None if v == "default" else v)
+
+        ms = {v: [] for v in variants}
+        for v in variants:
+            solver(v).run()  # warm-up
+        for _ in range(a.repeat):
+            for v in variants:
+                r = solver(v).run()
+                assert not r.aborted and math.isfinite(max(r.max_abs_u)), "the benchmark run diverged"
+                ms[v].append(r.total_ms)
+                print(f"bench_medium: {dtype} {v}: {r.total_ms:.2f} ms", file=sys.stderr, flush=True)
+        for v in variants:
+            best = min(ms[v])
+            out["runs"].append({"kernel": "k_march_m", "variant": v, "dtype": dtype, "courant": round(prob.courant, 4),
+                                "loop_ms": [round(t, 3) for t in ms[v]], "ms_per_step": round(best / K, 4),
+                                "mpts_per_s": round(nodes * K / best / 1e3, 1), "bytes_per_node": 4 * es,
+                                "eff_tb_per_s": round(4 * es * nodes * K / (best * 1e-3) / 1e12, 3)})
+        if not a.no_yardstick:
+            yp = wave3d.WaveProblem(N, timesteps=K, dtype=dtype)
+            r = wave3d.WaveSolver(yp, "hip", kernel="march", device=0).run(repeat=a.repeat, warmup=1)
+            mp = r.mpts_per_s_best
+            out["runs"].append({"kernel": "k_march", "variant": r.kernel, "dtype": dtype,
+                                "solve_ms": [round(t, 3) for t in r.solve_ms],
+                                "ms_per_step": round(nodes / mp / 1e3, 4), "mpts_per_s": round(mp, 1),
+                                "bytes_per_node": 3 * es, "eff_tb_per_s": round(3 * es * mp * 1e6 / 1e12, 3)})
+    for d in (x for x in out["runs"] if x["kernel"] == "k_march_m"):
+        y = [x for x in out["runs"] if x["kernel"] == "k_march" and x["dtype"] == d["dtype"]]
+        if y:
+            d["bw_vs_k_march"] = round(d["eff_tb_per_s"] / y[0]["eff_tb_per_s"], 3)
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
