@@ -24,7 +24,7 @@ def __getattr__(name):
         from .models import wave
 
         return getattr(wave, name)
-    if name in ("MediumProblem", "MediumSolver", "MediumResult", "ricker"):
+    if name in ("MediumProblem", "MediumSolver", "MediumResult", "ricker", "sponge_taper"):
         from .models import medium
 
         return getattr(medium, name)

@@ -8,6 +8,9 @@
 //    a fourth stream: m = c^2 tau^2 at the lane's own nodes, prefetched one plane ahead in a
 //    two-slot register ring like u^{n-2} (no LDS: only the centre node's m enters the update).
 //    No analytic tables and no fused halo packing; the per-step statistic is max |u|.
+//    TAPER: the damped leapfrog of an absorbing sponge, u = G ((2 u1 - G u2) + m lap) with the
+//    separable G = gx[i] (gy[j] gz[k]): gy gz is one register per lane row, formed before the
+//    march, gx[i] a wave-uniform scalar load fetched one plane ahead. No further stream.
 //  * k_inject / k_record: one thread per source entry / receiver.
 //
 // FP contraction is off (-ffp-contract=off + the pragmas in stencil_math.hpp): every operation
@@ -43,12 +46,14 @@ struct MediumParams {
     T hx2, hy2, hz2;
     T yx2, yy2, yz2;  // RN(1/h^2) in T for the correctly rounded constant division
     u64* err;
+    const T *gx, *gy, *gz;  // TAPER: sponge factors per axis, storage indexing (X+2, Y+2, Z+2 values)
 };
 
 // R = rows (j) per lane; the workgroup tile is (4R) x 64. NTM = non-temporal loads of m.
 // Register slots as in k_march: u1(x) -> (x - ib + 1) & 3; u2(x), m(x), halo(x) and the LDS
 // buffer -> (x - ib) & 1; the i loop is unrolled by 4 with the phase as a constant.
-template <class T, bool FIRST, int R, bool NTM>
+// TAPER = false compiles to the undamped kernel (every use of the tables is `if constexpr`).
+template <class T, bool FIRST, int R, bool NTM, bool TAPER>
 __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
     constexpr int kTJ = kWaves * R;
     constexpr unsigned ES = sizeof(T);
@@ -139,6 +144,19 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
     const T hx2 = p.hx2, hy2 = p.hy2, hz2 = p.hz2;
     const T yx2 = p.yx2, yy2 = p.yy2, yz2 = p.yz2;
 
+    // sponge: gyz[r] = gy[j] gz[k] (rounded) of the lane's rows; lanes and rows past the grid read
+    // the last table entry (their stores are masked). gxn = gx of the next plane to compute:
+    // i + 1 <= X + 1 is always inside the table.
+    T gyz[TAPER ? R : 1];
+    T gxn = T(1);
+    if constexpr (TAPER) {
+#pragma clang fp contract(off)
+        const T gzk = p.gz[min(k, p.kmax)];
+#pragma unroll
+        for (int r = 0; r < R; ++r) gyz[r] = ldconst(p.gy, min(jt + w * R + r, p.jmax)) * gzk;
+        gxn = ldconst(p.gx, ib);
+    }
+
     T ma = T(kErrInit);
     T chk = T(0);  // sum of the values (commit_errors: nonfinite flag)
 
@@ -172,6 +190,8 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
         __syncthreads();
 
         const bool erow = i >= p.ei0 && i <= p.ei1;
+        const T gxi = gxn;
+        if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
         T vv[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -186,6 +206,11 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
 #pragma clang fp contract(off)
                 const T half_m = T(0.5) * mm[H0][r];  // exact
                 vv[r] = taylor_first(c, lap, half_m);
+                if constexpr (TAPER) vv[r] = (gxi * gyz[r]) * vv[r];
+            } else if constexpr (TAPER) {
+#pragma clang fp contract(off)
+                const T g = gxi * gyz[r];
+                vv[r] = g * leapfrog(c, g * u2[H0][r], lap, mm[H0][r]);
             } else {
                 vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]);
             }
@@ -272,14 +297,14 @@ NodeGrid node_grid(const GridView& gv) {
     return NodeGrid{gv.si, gv.sj, gv.X + 2, gv.Y + 2, gv.Z + 2};
 }
 
-template <class T, bool FIRST>
+template <class T, bool FIRST, bool TAPER>
 void (*march_m_kernel(int variant))(const MediumParams<T>) {
     constexpr int RD = 4;  // march_rows_per_thread()
     switch (variant & 3) {
-        case 1: return k_march_m<T, FIRST, RD, true>;
-        case 2: return k_march_m<T, FIRST, 2, false>;
-        case 3: return k_march_m<T, FIRST, 2, true>;
-        default: return k_march_m<T, FIRST, RD, false>;
+        case 1: return k_march_m<T, FIRST, RD, true, TAPER>;
+        case 2: return k_march_m<T, FIRST, 2, false, TAPER>;
+        case 3: return k_march_m<T, FIRST, 2, true, TAPER>;
+        default: return k_march_m<T, FIRST, RD, false, TAPER>;
     }
 }
 
@@ -303,7 +328,11 @@ int medium_variant() {
 template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
-                        const double h2[3], u64* err, int chunk, hipStream_t s, int variant) {
+                        const double h2[3], u64* err, int chunk, hipStream_t s, int variant, const T* gx,
+                        const T* gy, const T* gz) {
+    const bool taper = gx || gy || gz;
+    W3D_REQUIRE(!taper || (gx && gy && gz), "the sponge needs all three tables");
+    W3D_REQUIRE(!taper || gv.G == 1, "sponge tables: one ghost layer");
     W3D_REQUIRE(nbox >= 1 && nbox <= kMaxBoxes, "bad box count");
     W3D_REQUIRE(march_rows_per_thread() == 4, "k_march_m is instantiated for 4 rows per lane");
     W3D_REQUIRE(gv.si > 0 && gv.si * i64(sizeof(T)) < (1ll << 31), "plane larger than a buffer descriptor's range");
@@ -333,6 +362,9 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     p.yy2 = T(1) / T(h2[1]);
     p.yz2 = T(1) / T(h2[2]);
     p.err = err;
+    p.gx = gx;
+    p.gy = gy;
+    p.gz = gz;
     const int tj_rows = kWaves * ((variant & 2) ? 2 : 4);
     int btiles[kMaxBoxes], bplanes[kMaxBoxes], nbt = 0;
     for (int q = 0; q < nbox; ++q) {
@@ -365,7 +397,9 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     }
     p.nbox = nb;
     if (nb == 0) return;
-    void (*kern)(const MediumParams<T>) = first ? march_m_kernel<T, true>(variant) : march_m_kernel<T, false>(variant);
+    void (*kern)(const MediumParams<T>) =
+        taper ? (first ? march_m_kernel<T, true, true>(variant) : march_m_kernel<T, false, true>(variant))
+              : (first ? march_m_kernel<T, true, false>(variant) : march_m_kernel<T, false, false>(variant));
     hipLaunchKernelGGL(kern, dim3(total), dim3(kThreads), 0, s, p);
     HIP_OK(hipGetLastError());
 }
@@ -388,7 +422,7 @@ void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int
 #define W3D_MEDIUM_INST(T)                                                                              \
     template void launch_step_medium<T>(bool, const T*, const T*, const T*, T*, const GridView&,       \
                                         const Box*, int, int, int, const Wrap&, const double[3], u64*, \
-                                        int, hipStream_t, int);                                        \
+                                        int, hipStream_t, int, const T*, const T*, const T*);          \
     template void launch_inject<T>(T*, const T*, const GridView&, const int*, const T*, int,           \
                                    const Wrap&, hipStream_t);                                          \
     template void launch_record<T>(const T*, const GridView&, const int*, T*, int, hipStream_t);

@@ -15,10 +15,17 @@ namespace wave3d {
 // err[0] = key of max |u| over the planes [ei0, ei1] (NaN ignored), err[1] untouched,
 // err[2] = non-finite flag. variant: -1 = WAVE3D_MEDIUM_VARIANT or the default; bit 0 =
 // non-temporal loads of m, bit 1 = 2 rows per lane instead of march_rows_per_thread().
+//
+// Absorbing sponge (gx, gy, gz all non-null; all null = none, the kernels above): device tables of
+// X+2, Y+2, Z+2 factors in (0, 1] in storage indexing (gv.G == 1), G = gx[i] (gy[j] gz[k]) with
+// each product rounded, and the damped leapfrog u = G ((2 u1 - G u2) + m lap(u1)), on the Taylor
+// start u = G (u1 + (0.5 m) lap(u1)). Tables of ones give the undamped bits; err as above, of the
+// damped values.
 template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
-                        const double h2[3], u64* err, int chunk, hipStream_t s, int variant = -1);
+                        const double h2[3], u64* err, int chunk, hipStream_t s, int variant = -1,
+                        const T* gx = nullptr, const T* gy = nullptr, const T* gz = nullptr);
 
 // Point sources: u(node[e]) += m(node[e]) * g[e] for e < n (the product rounded, then the add);
 // an entry on a wrap source plane is also copied to its ghost plane. nodes = n x (i, j, k),

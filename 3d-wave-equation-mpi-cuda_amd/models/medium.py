@@ -89,6 +89,39 @@ def ricker(f0: float, t0: float, K: int, tau: float) -> torch.Tensor:
     return (1 - 2 * a) * torch.exp(-a)
 
 
+def sponge_taper(problem: MediumProblem, width: int, sigma_max: float | None = None, power: float = 2,
+                 reflection: float = 0.02, axes: str = "xyz"):
+    """Per-axis factors ``(gx, gy, gz)`` of an absorbing sponge layer for :class:`MediumSolver`.
+
+    ``g[q] = exp(-sigma_max ((width - d) / width)^power tau)`` with d = min(q, N - q) nodes from the
+    nearer end of the axis, 1 where d >= width; axes not named in ``axes`` are ones. Without
+    ``sigma_max`` the damping follows from the two-way travel through the layer at the fastest
+    speed for a nominal ``reflection``: ``(power + 1) c_max ln(1 / reflection) / (2 width h_min)``.
+    Each is a float64 tensor of N+1 values in global indexing; the profile is symmetric, so
+    ``gx[0] == gx[N]`` on the periodic axis.
+    """
+    N = problem.N
+    width = int(width)
+    if width < 1:
+        raise ValueError(f"sponge width must be >= 1 node, not {width}")
+    if 2 * width > N:
+        raise ValueError(f"two sponge layers of {width} nodes do not fit in N = {N} intervals")
+    if not 0 < reflection < 1:
+        raise ValueError(f"reflection must lie in (0, 1), not {reflection}")
+    if not set(axes) <= set("xyz"):
+        raise ValueError(f"axes must name x, y, z, not {axes!r}")
+    if sigma_max is None:
+        h_min = min(problem.lengths()) / N
+        sigma_max = (power + 1) * math.sqrt(problem.max_speed2) * math.log(1 / reflection) / (2 * width * h_min)
+    if not (math.isfinite(sigma_max) and sigma_max >= 0):
+        raise ValueError(f"sigma_max must be finite and >= 0, not {sigma_max}")
+    q = torch.arange(N + 1, dtype=torch.float64)
+    d = torch.minimum(q, N - q)
+    g = torch.exp(-sigma_max * ((width - d) / width).clamp(min=0) ** power * problem.tau)
+    g[d >= width] = 1.0
+    return tuple(g.clone() if a in axes else torch.ones(N + 1, dtype=torch.float64) for a in "xyz")
+
+
 @dataclass
 class MediumResult:
     traces: torch.Tensor     # [K+1, R], row 0 = the initial field
@@ -114,10 +147,15 @@ class MediumSolver:
     receivers   global (i, j, k) nodes
     check_every >0 ("hip"): read the non-finite flag every that many steps and stop early
     variant     ablation only: k_march_m variant ("nt", "plain", "r2", "r2nt"; ops.kernels.step_medium)
+    taper       absorbing sponge: ``(gx, gy, gz)``, N+1 factors in (0, 1] per axis in global indexing
+                (an entry may be None: ones; see :func:`sponge_taper`). With G = gx[i] (gy[j] gz[k]) the
+                step becomes ``u = G ((2 u1 - G u2) + m lap u1)``; the source term is not damped in
+                its own step. gx[0] must equal gx[N] (one periodic plane).
     """
 
     def __init__(self, problem: MediumProblem, backend: str = "hip", *, u0=None, sources=(), wavelet=None,
-                 receivers=(), check_every: int = 0, device: int | None = None, variant: str | None = None):
+                 receivers=(), check_every: int = 0, device: int | None = None, variant: str | None = None,
+                 taper=None):
         if backend not in ("hip", "cpu"):
             raise ValueError(f"unknown backend {backend!r}")
         N, K = problem.N, problem.timesteps
@@ -153,6 +191,26 @@ class MediumSolver:
             if tuple(u0.shape) != (N + 1, N + 1, N + 1):
                 raise ValueError(f"u0 must have shape {(N + 1,) * 3}, not {tuple(u0.shape)}")
         self.u0 = u0
+        self.taper = None if taper is None else self._check_taper(taper, N)
+
+    @staticmethod
+    def _check_taper(taper, N):
+        if len(taper) != 3:
+            raise ValueError("taper = (gx, gy, gz)")
+        out = []
+        for name, t in zip("xyz", taper):
+            t = torch.ones(N + 1, dtype=torch.float64) if t is None else torch.as_tensor(t, dtype=torch.float64).cpu()
+            if t.dim() != 1 or t.numel() != N + 1:
+                raise ValueError(f"taper g{name} must have {N + 1} values, not shape {tuple(t.shape)}")
+            bad = ~(torch.isfinite(t) & (t > 0) & (t <= 1))
+            if bool(bad.any()):
+                q = int(bad.nonzero()[0])
+                raise ValueError(f"taper g{name} must be finite and in (0, 1], found g{name}[{q}] = {t[q].item()}")
+            out.append(t)
+        gx = out[0]
+        if gx[0] != gx[N]:
+            raise ValueError(f"taper gx must be periodic in x: gx[0] = {gx[0].item()} but gx[{N}] = {gx[N].item()}")
+        return tuple(out)
 
     def run(self) -> MediumResult:
         return self._run_cpu() if self.backend == "cpu" else self._run_hip()
@@ -172,7 +230,8 @@ class MediumSolver:
         t0 = time.perf_counter()
         tr, uf, mx = reference.solve_medium(p.N, p.timesteps, p.speed2, u0=self.u0, sources=self.sources,
                                             wavelet=self.wavelet, receivers=self.receivers,
-                                            L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype)
+                                            L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
+                                            taper=self.taper)
         return self._result(tr, uf, mx, (time.perf_counter() - t0) * 1e3)
 
     def _run_hip(self) -> MediumResult:
@@ -189,6 +248,9 @@ class MediumSolver:
             lv = [kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(3)]
             m = kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev)
             m.copy_(reference.medium_coefficient(p.speed2, c["tau"], N, dt))
+            taper = None
+            if self.taper is not None:
+                taper = tuple(t.to(dev) for t in reference.taper_tables(self.taper, N, dt))
             if self.u0 is not None:
                 lv[0][1:N + 2] = self.u0.to(dt).to(dev)
                 lv[0][0] = lv[0][N]
@@ -216,7 +278,7 @@ class MediumSolver:
                     u[:, :, 0] = 0
                     u[:, :, N] = 0
                 kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=stat[3 * n:3 * n + 3],
-                                    stat_i=(1, N + 1), wrap=wrap, variant=self.variant)
+                                    stat_i=(1, N + 1), wrap=wrap, variant=self.variant, taper=taper)
                 kernels.inject(u, m, src, g[n - 1], wrap)
                 kernels.record(u, rec, traces[n])
                 if self.check_every > 0 and n % self.check_every == 0:

@@ -333,8 +333,21 @@ def receiver_nodes(nodes, u) -> NodeList:
 _MEDIUM_VARIANTS = {None: -1, "plain": 0, "nt": 1, "r2": 2, "r2nt": 3}
 
 
+def _check_taper(taper, u) -> list[int]:
+    if taper is None:
+        return [0, 0, 0]
+    if len(taper) != 3:
+        raise ValueError("taper = (gx, gy, gz)")
+    for t, n, name in zip(taper, u.shape, ("gx", "gy", "gz")):
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != u.device or t.dtype != u.dtype
+                or t.dim() != 1 or t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"taper table {name} must be a contiguous 1-D {u.dtype} tensor of {n} values "
+                             f"on {u.device}")
+    return [t.data_ptr() for t in taper]
+
+
 def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None, chunk: int = 0,
-                variant: str | None = None) -> None:
+                variant: str | None = None, taper=None) -> None:
     """One layer of ``u_tt = c^2 (lap u + f)`` over ``boxes``: ``u = (2 u1 - u2) + m lap(u1)``, on
     the Taylor start (``first``) ``u = u1 + (0.5 m) lap(u1)``, with ``m = c^2 tau^2`` per node.
 
@@ -344,6 +357,11 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     :func:`step`. ``variant`` (ablation; the results are the same bit for bit): "nt" non-temporal
     loads of m with 4 rows per lane (the default, None), "plain" ordinary loads of m, "r2" / "r2nt"
     the same with 2 rows per lane.
+
+    ``taper`` = (gx, gy, gz): the absorbing sponge, 1-D device tensors of exactly nx, ny, nz factors
+    in (0, 1] (storage indexing). With ``G = gx[i] (gy[j] gz[k])`` the step is the damped leapfrog
+    ``u = G ((2 u1 - G u2) + m lap(u1))``, on the Taylor start ``u = G (u1 + (0.5 m) lap(u1))``;
+    tables of ones give the undamped bits. None: the undamped kernels.
     """
     gv = _check_grid_strided(u1, u2, m, u)
     if isinstance(boxes[0], int):
@@ -358,10 +376,11 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     w = _check_wrap(wrap, gv)
     if variant not in _MEDIUM_VARIANTS:
         raise ValueError(f"unknown variant {variant!r}")
+    gp = _check_taper(taper, u)
     fn = getattr(_C(), "k_step_medium_" + _sfx(u))
     fn(bool(first), u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, bl, int(stat_i[0]),
        int(stat_i[1]), w, [float(v) for v in h2], stat.data_ptr(), int(chunk), _stream(),
-       _MEDIUM_VARIANTS[variant])
+       _MEDIUM_VARIANTS[variant], *gp)
 
 
 def inject(u, m, nodes, g, wrap=None) -> None:

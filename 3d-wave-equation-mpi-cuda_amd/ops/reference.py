@@ -179,16 +179,29 @@ def chained_layers(A, B, nlayers: int, *, first: bool, mask, hx2, hy2, hz2, coef
 
 # ---- heterogeneous medium: u_tt = c^2 (lap u + f) -----------------------------------------
 
-def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2) -> torch.Tensor:
+def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None) -> torch.Tensor:
     """Layer update on ``box`` with the per-node coefficient ``m = c^2 tau^2``: the Taylor start
-    ``c + (0.5 m) lap`` or ``(2c - u2) + m lap``; returns the updated box values."""
+    ``c + (0.5 m) lap`` or ``(2c - u2) + m lap``; returns the updated box values.
+
+    taper = (gx, gy, gz), 1-D factors in (0, 1] per axis in storage indexing (the lengths of the
+    grid's axes): the damped leapfrog of an absorbing sponge with ``G = gx (gy gz)`` per node,
+    ``G (c + (0.5 m) lap)`` or ``G ((2c - G u2) + m lap)``, every operation rounded on its own."""
     i0, i1, j0, j1, k0, k1 = box
     lap = laplace7(u1, hx2, hy2, hz2)[i0 - 1:i1, j0 - 1:j1, k0 - 1:k1]
     c = u1[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
     mb = m[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
+    if taper is None:
+        if first:
+            return c + (0.5 * mb) * lap
+        return (2 * c - u2[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]) + mb * lap
+    gx, gy, gz = taper
+    for t, n in zip(taper, u1.shape):
+        if t.dim() != 1 or t.numel() != n or t.dtype != u1.dtype:
+            raise ValueError(f"taper tables must be 1-D {u1.dtype} tensors of lengths {tuple(u1.shape)}")
+    G = gx[i0:i1 + 1, None, None] * (gy[None, j0:j1 + 1, None] * gz[None, None, k0:k1 + 1])
     if first:
-        return c + (0.5 * mb) * lap
-    return (2 * c - u2[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]) + mb * lap
+        return G * (c + (0.5 * mb) * lap)
+    return G * ((2 * c - G * u2[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]) + mb * lap)
 
 
 def max_abs_field(u: torch.Tensor, init: float = -100.0) -> float:
@@ -238,8 +251,28 @@ def source_entries(sources, N: int) -> list[tuple[tuple[int, int, int], int]]:
     return out
 
 
+def taper_tables(taper, N: int, dtype) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Sponge factors (gx, gy, gz), each ``N+1`` values in global indexing (an entry may be None:
+    ones), cast to ``dtype`` in ``solve()``'s storage: gx ``[N+3]`` with the x ghosts filled
+    periodically like ``medium_coefficient``, gy and gz ``[N+1]``."""
+    if len(taper) != 3:
+        raise ValueError("taper = (gx, gy, gz)")
+    out = []
+    for name, t in zip("xyz", taper):
+        t = torch.ones(N + 1, dtype=torch.float64) if t is None else torch.as_tensor(t, dtype=torch.float64).cpu()
+        if t.dim() != 1 or t.numel() != N + 1:
+            raise ValueError(f"taper g{name} must have {N + 1} values, not shape {tuple(t.shape)}")
+        out.append(t.to(dtype))
+    gx = torch.empty(N + 3, dtype=dtype)
+    gx[1:N + 2] = out[0]
+    gx[0] = gx[N]
+    gx[N + 2] = gx[2]
+    return gx, out[1].contiguous(), out[2].contiguous()
+
+
 def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, receivers=(),
-                 L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, device="cpu"):
+                 L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, device="cpu",
+                 taper=None):
     """Whole single-domain solve of ``(1/c^2) u_tt = lap u + f`` from rest in PyTorch, in
     ``solve()``'s storage (x ghosts, local = global + 1).
 
@@ -248,8 +281,14 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
     f_s at t_n = n tau, n = 0..K-1. Step n adds ``m[x_s] * g[n-1, s]`` after the stencil and before
     the periodic wrap. Returns (traces ``[K+1, R]`` with row 0 the initial field, u_K ``(N+1)^3``,
     max |u| per layer ``[K+1]``: over the stencil nodes, of the step's result before its source term).
+
+    taper = (gx, gy, gz): sponge factors per axis, ``N+1`` values each in global indexing
+    (``taper_tables``); every step is then the damped one of ``step_medium`` (the source term is
+    not tapered in its own step). None: the undamped scheme.
     """
     c = tables(N, K, L, T, pi)[4]
+    if taper is not None:
+        taper = tuple(t.to(device) for t in taper_tables(taper, N, dtype))
     m = medium_coefficient(speed2, c["tau"], N, dtype).to(device)
     ent = source_entries(sources, N)
     g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype).to(device)
@@ -278,7 +317,7 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
     for n in range(1, K + 1):
         u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
         u.zero_()
-        vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"])
+        vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=taper)
         mx.append(max_abs_field(vals))
         u[1:N + 2, 1:N, 1:N] = vals
         for nd, s in ent:

@@ -3,13 +3,17 @@
 
     python tools/bench_medium.py [--N 512] [--steps 100] [--dtypes fp64,fp32]
                                  [--variants default,plain,r2,r2nt] [--repeat 3] [--no-yardstick]
+                                 [--taper WIDTH]
 
 For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
 and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
 the variants alternating inside each repeat. The yardstick is the constant-speed solver with
 `--kernel march --math exact` at the same N and steps in the same process. Effective bandwidth
 counts the bytes the algorithm needs: u1, u2, m read and u written once per node (32 B in fp64,
-16 B in fp32) for the medium step, 24 B / 12 B for the yardstick. Prints one JSON line.
+16 B in fp32) for the medium step, 24 B / 12 B for the yardstick. `--taper WIDTH` adds, per dtype
+and variant, the same run with the absorbing sponge `sponge_taper(prob, WIDTH)` (the TAPER
+instantiation of k_march_m, the same bytes), alternating with the untapered one inside each
+repeat, and reports its ms/step and the ratio tapered / untapered. Prints one JSON line.
 """
 import argparse
 import json
@@ -43,6 +47,8 @@ def main(argv=None) -> int:
     ap.add_argument("--variants", default="default")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--no-yardstick", action="store_true")
+    ap.add_argument("--taper", type=int, default=0, metavar="WIDTH",
+                    help="also time the step with sponge_taper(prob, WIDTH)")
     a = ap.parse_args(argv)
 
     import math
@@ -68,25 +74,34 @@ def main(argv=None) -> int:
         w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
         mid = N // 2
 
-        def solver(v):
-            return wave3d.MediumSolver(prob, "hip", sources=[(mid, mid, mid)], wavelet=w,
-                                       receivers=[(mid // 2, mid, mid)], variant=None if v == "default" else v)
+        sponge = wave3d.sponge_taper(prob, a.taper) if a.taper > 0 else None
 
-        ms = {v: [] for v in variants}
-        for v in variants:
-            solver(v).run()  # warm-up
+        def solver(v, tapered):
+            return wave3d.MediumSolver(prob, "hip", sources=[(mid, mid, mid)], wavelet=w,
+                                       receivers=[(mid // 2, mid, mid)], variant=None if v == "default" else v,
+                                       taper=sponge if tapered else None)
+
+        cfgs = [(v, t) for v in variants for t in ((False, True) if sponge is not None else (False,))]
+        ms = {c: [] for c in cfgs}
+        for c in cfgs:
+            solver(*c).run()  # warm-up
         for _ in range(a.repeat):
-            for v in variants:
-                r = solver(v).run()
+            for c in cfgs:
+                r = solver(*c).run()
                 assert not r.aborted and math.isfinite(max(r.max_abs_u)), "the benchmark run diverged"
-                ms[v].append(r.total_ms)
-                print(f"bench_medium: {dtype} {v}: {r.total_ms:.2f} ms", file=sys.stderr, flush=True)
-        for v in variants:
-            best = min(ms[v])
-            out["runs"].append({"kernel": "k_march_m", "variant": v, "dtype": dtype, "courant": round(prob.courant, 4),
-                                "loop_ms": [round(t, 3) for t in ms[v]], "ms_per_step": round(best / K, 4),
-                                "mpts_per_s": round(nodes * K / best / 1e3, 1), "bytes_per_node": 4 * es,
-                                "eff_tb_per_s": round(4 * es * nodes * K / (best * 1e-3) / 1e12, 3)})
+                ms[c].append(r.total_ms)
+                print(f"bench_medium: {dtype} {c[0]}{' taper' if c[1] else ''}: {r.total_ms:.2f} ms",
+                      file=sys.stderr, flush=True)
+        for c in cfgs:
+            best = min(ms[c])
+            row = {"kernel": "k_march_m", "variant": c[0], "dtype": dtype, "courant": round(prob.courant, 4),
+                   "loop_ms": [round(t, 3) for t in ms[c]], "ms_per_step": round(best / K, 4),
+                   "mpts_per_s": round(nodes * K / best / 1e3, 1), "bytes_per_node": 4 * es,
+                   "eff_tb_per_s": round(4 * es * nodes * K / (best * 1e-3) / 1e12, 3)}
+            if c[1]:
+                row["taper"] = a.taper
+                row["vs_untapered"] = round(best / min(ms[(c[0], False)]), 4)
+            out["runs"].append(row)
         if not a.no_yardstick:
             yp = wave3d.WaveProblem(N, timesteps=K, dtype=dtype)
             r = wave3d.WaveSolver(yp, "hip", kernel="march", device=0).run(repeat=a.repeat, warmup=1)
