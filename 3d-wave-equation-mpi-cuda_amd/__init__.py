@@ -24,7 +24,8 @@ def __getattr__(name):
         from .models import wave
 
         return getattr(wave, name)
-    if name in ("MediumProblem", "MediumSolver", "MediumResult", "ricker", "sponge_taper"):
+    if name in ("MediumProblem", "MediumSolver", "MediumResult", "MediumGradient", "ricker", "sponge_taper",
+                "gradient_levels"):
         from .models import medium
 
         return getattr(medium, name)

@@ -328,18 +328,19 @@ void k_zero_faces(uintptr_t u, const std::vector<i64>& g, int mask, uintptr_t st
 // Heterogeneous-medium step (k_march_m): m = c^2 tau^2 per node, h2 = (hx2, hy2, hz2); the grid
 // view carries explicit strides (dense tensors or the padded views of ops.kernels.alloc_level).
 // gx, gy, gz: the sponge tables (nx, ny, nz device values), all 0 for the undamped step.
+// lap_out / (q, acc): the grids of the save / image modes, all 0 for the plain step.
 template <class T>
 void k_step_medium(bool first, uintptr_t u1, uintptr_t u2, uintptr_t m, uintptr_t u, const std::vector<i64>& g,
                    const std::vector<std::vector<int>>& boxes, int ei0, int ei1, const std::vector<int>& wrap,
                    const std::vector<double>& h2, uintptr_t err, int chunk, uintptr_t stream, int variant,
-                   uintptr_t gx, uintptr_t gy, uintptr_t gz) {
+                   uintptr_t gx, uintptr_t gy, uintptr_t gz, uintptr_t lap_out, uintptr_t q, uintptr_t acc) {
     std::vector<Box> bx;
     for (auto& b : boxes) bx.push_back(tobox(b));
     W3D_REQUIRE(h2.size() == 3, "h2 = (hx2, hy2, hz2)");
     const double h[3] = {h2[0], h2[1], h2[2]};
     launch_step_medium<T>(first, P<T>(u1), P<T>(u2), P<T>(m), P<T>(u), gview(g), bx.data(), int(bx.size()), ei0,
                           ei1, towrap(wrap), h, P<u64>(err), chunk, (hipStream_t)stream, variant, P<T>(gx), P<T>(gy),
-                          P<T>(gz));
+                          P<T>(gz), P<T>(lap_out), P<T>(q), P<T>(acc));
 }
 
 // nodes: device int32 [n][3] of (i, j, k); g / out: n device values

@@ -47,13 +47,24 @@ struct MediumParams {
     T yx2, yy2, yz2;  // RN(1/h^2) in T for the correctly rounded constant division
     u64* err;
     const T *gx, *gy, *gz;  // TAPER: sponge factors per axis, storage indexing (X+2, Y+2, Z+2 values)
+    T* lap_out;             // kSave: receives lap(u1) at the box nodes (strides of u)
+    const T* q;             // kImage: the grid multiplied with the centre value of u1 ...
+    T* acc;                 // ... and the grid the product is added to, at the box nodes
 };
+
+// k_march_m modes: the plain step; kSave also stores the Laplacian that entered the update; kImage
+// also accumulates acc = acc + u1 * q (the imaging condition of the adjoint-state gradient).
+enum MarchMode { kPlain = 0, kSave = 1, kImage = 2 };
 
 // R = rows (j) per lane; the workgroup tile is (4R) x 64. NTM = non-temporal loads of m.
 // Register slots as in k_march: u1(x) -> (x - ib + 1) & 3; u2(x), m(x), halo(x) and the LDS
 // buffer -> (x - ib) & 1; the i loop is unrolled by 4 with the phase as a constant.
 // TAPER = false compiles to the undamped kernel (every use of the tables is `if constexpr`).
-template <class T, bool FIRST, int R, bool NTM, bool TAPER>
+// MODE (kSave / kImage: FIRST = false only) adds, likewise behind `if constexpr`, one write-once
+// stream (lap_out), or a read-once stream (q) and a read-modify-write one (acc), both prefetched
+// one plane ahead in two-slot rings like m; all at the lane's own nodes, masked like the stores
+// of u and without the periodic wrap.
+template <class T, bool FIRST, int R, bool NTM, bool TAPER, int MODE = kPlain>
 __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
     constexpr int kTJ = kWaves * R;
     constexpr unsigned ES = sizeof(T);
@@ -122,8 +133,20 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
     constexpr int kMAux = NTM ? 2 : 0;  // non-temporal m (read once per step)
     constexpr int kStAux = 2;           // non-temporal stores (write-once stream)
 
+    static_assert(MODE == kPlain || !FIRST, "save / image modes: leapfrog steps only");
+    constexpr bool kImg = MODE == kImage;
     T u1[4][R], u2[2][R], mm[2][R];
+    T qq[kImg ? 2 : 1][kImg ? R : 1], aa[kImg ? 2 : 1][kImg ? R : 1];
     T hv[2];
+    if constexpr (kImg) {
+        const auto rQ = prs(p.q, ib), rA = prs(p.acc, ib);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            qq[0][r] = bld<T, 2>(rQ, os[r]);
+            aa[0][r] = bld<T, 2>(rA, os[r]);
+            qq[1][r] = aa[1][r] = T(0);
+        }
+    }
     {
         const auto r0 = prs(p.u1, ib - 1), r1 = prs(p.u1, ib), r2 = prs(p.u1, ib + 1);
         const auto q0 = prs(p.u2, ib), m0 = prs(p.m, ib);
@@ -181,6 +204,15 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
                 mm[H1][r] = bld<T, kMAux>(rM, os[r]);
             }
             hv[H1] = bld<T>(rH, hoff);
+            if constexpr (kImg) {
+                const auto rQ = plane_rsrc(p.q + (i64(i + d1) * si - p.poff), nb);
+                const auto rA = plane_rsrc(p.acc + (i64(i + d1) * si - p.poff), nb);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    qq[H1][r] = bld<T, 2>(rQ, os[r]);
+                    aa[H1][r] = bld<T, 2>(rA, os[r]);
+                }
+            }
         }
 
         // stage plane i
@@ -193,6 +225,7 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
         const T gxi = gxn;
         if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
         T vv[R];
+        T xv[MODE == kPlain ? 1 : R];  // kSave: lap; kImage: the new acc
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int lr = 1 + w * R + r;
@@ -202,6 +235,12 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
             const T km = lds[H0][lr][lane];
             const T kp = lds[H0][lr][lane + 2];
             const T lap = laplace7_cr(c, u1[S0][r], u1[S2][r], jm, jp, km, kp, hx2, hy2, hz2, yx2, yy2, yz2);
+            if constexpr (MODE == kSave) xv[r] = lap;
+            if constexpr (kImg) {
+#pragma clang fp contract(off)
+                const T pr = c * qq[H0][r];
+                xv[r] = aa[H0][r] + pr;
+            }
             if constexpr (FIRST) {
 #pragma clang fp contract(off)
                 const T half_m = T(0.5) * mm[H0][r];  // exact
@@ -227,6 +266,11 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
 #pragma unroll
                     for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
                 }
+            if constexpr (MODE != kPlain) {
+                const auto rx = prs(MODE == kSave ? p.lap_out : p.acc, i);
+#pragma unroll
+                for (int r = 0; r < R; ++r) bst<kStAux>(xv[r], rx, os[r]);
+            }
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -329,7 +373,7 @@ template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant, const T* gx,
-                        const T* gy, const T* gz) {
+                        const T* gy, const T* gz, T* lap_out, const T* q, T* acc) {
     const bool taper = gx || gy || gz;
     W3D_REQUIRE(!taper || (gx && gy && gz), "the sponge needs all three tables");
     W3D_REQUIRE(!taper || gv.G == 1, "sponge tables: one ghost layer");
@@ -338,6 +382,12 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     W3D_REQUIRE(gv.si > 0 && gv.si * i64(sizeof(T)) < (1ll << 31), "plane larger than a buffer descriptor's range");
     W3D_REQUIRE(gv.sj >= gv.Z + 2 * gv.G && gv.si >= i64(gv.Y + 2 * gv.G) * gv.sj, "strides smaller than the grid");
     if (variant < 0) variant = medium_variant();
+    const bool save = lap_out != nullptr, image = q || acc;
+    W3D_REQUIRE(!image || (q && acc), "image mode needs both q and acc");
+    W3D_REQUIRE(!(save && image), "save mode (lap_out) and image mode (q, acc) cannot be combined");
+    W3D_REQUIRE(!(save || image) || !first, "save / image modes: not on the Taylor start (first)");
+    W3D_REQUIRE(!(save || image) || variant == 1,
+                "save / image modes are instantiated for the default variant only (nt, 4 rows per lane)");
     MediumParams<T> p{};
     p.xcd = xcd_swizzle_enabled();
     p.u1 = u1;
@@ -365,6 +415,9 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     p.gx = gx;
     p.gy = gy;
     p.gz = gz;
+    p.lap_out = lap_out;
+    p.q = q;
+    p.acc = acc;
     const int tj_rows = kWaves * ((variant & 2) ? 2 : 4);
     int btiles[kMaxBoxes], bplanes[kMaxBoxes], nbt = 0;
     for (int q = 0; q < nbox; ++q) {
@@ -400,6 +453,8 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     void (*kern)(const MediumParams<T>) =
         taper ? (first ? march_m_kernel<T, true, true>(variant) : march_m_kernel<T, false, true>(variant))
               : (first ? march_m_kernel<T, true, false>(variant) : march_m_kernel<T, false, false>(variant));
+    if (save) kern = taper ? k_march_m<T, false, 4, true, true, kSave> : k_march_m<T, false, 4, true, false, kSave>;
+    if (image) kern = taper ? k_march_m<T, false, 4, true, true, kImage> : k_march_m<T, false, 4, true, false, kImage>;
     hipLaunchKernelGGL(kern, dim3(total), dim3(kThreads), 0, s, p);
     HIP_OK(hipGetLastError());
 }
@@ -422,7 +477,8 @@ void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int
 #define W3D_MEDIUM_INST(T)                                                                              \
     template void launch_step_medium<T>(bool, const T*, const T*, const T*, T*, const GridView&,       \
                                         const Box*, int, int, int, const Wrap&, const double[3], u64*, \
-                                        int, hipStream_t, int, const T*, const T*, const T*);          \
+                                        int, hipStream_t, int, const T*, const T*, const T*, T*,       \
+                                        const T*, T*);                                                 \
     template void launch_inject<T>(T*, const T*, const GridView&, const int*, const T*, int,           \
                                    const Wrap&, hipStream_t);                                          \
     template void launch_record<T>(const T*, const GridView&, const int*, T*, int, hipStream_t);

@@ -21,11 +21,19 @@ namespace wave3d {
 // each product rounded, and the damped leapfrog u = G ((2 u1 - G u2) + m lap(u1)), on the Taylor
 // start u = G (u1 + (0.5 m) lap(u1)). Tables of ones give the undamped bits; err as above, of the
 // damped values.
+//
+// Modes for the adjoint-state gradient (leapfrog steps with variant 1 only; every other
+// combination is rejected): save (lap_out non-null) also stores lap(u1), the value that entered
+// the update, at the box nodes of lap_out; image (q and acc non-null) also does
+// acc = acc + u1 * q at the box nodes, the product rounded before the add. lap_out, q and acc
+// have the strides of u; nothing outside the boxes is written and the wrap applies to u alone.
+// u and err are those of the plain step bit for bit. Per node in fp64: 40 B (save), 56 B (image).
 template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant = -1,
-                        const T* gx = nullptr, const T* gy = nullptr, const T* gz = nullptr);
+                        const T* gx = nullptr, const T* gy = nullptr, const T* gz = nullptr,
+                        T* lap_out = nullptr, const T* q = nullptr, T* acc = nullptr);
 
 // Point sources: u(node[e]) += m(node[e]) * g[e] for e < n (the product rounded, then the add);
 // an entry on a wrap source plane is also copied to its ghost plane. nodes = n x (i, j, k),

@@ -298,3 +298,200 @@ class MediumSolver:
                 extra["nonfinite_layer"] = next(n for n in range(1, K + 1) if dec[n][2])
             uf = lv[done % 3][1:N + 2].cpu()
             return self._result(traces.cpu(), uf, mx, ms, extra=extra, **abort)
+
+    # ---- misfit gradients (adjoint state; ops/reference.py has the mathematics) ------------
+
+    def gradient(self, observed, *, segment: int | None = None) -> "MediumGradient":
+        """Misfit ``J = 1/2 sum_{n=1..K} sum_r (trace[n, r] - observed[n, r])^2`` and its gradients
+        with respect to ``speed2`` and the wavelet (full-waveform-inversion gradient / reverse-time
+        migration image). ``observed``: ``[timesteps + 1, len(receivers)]``, row 0 is ignored.
+
+        ``grad_speed2`` is taken with respect to the unique nodes: entry [0] is the derivative with
+        respect to the shared value of planes 0 and N, entry [N] a copy of it, the Dirichlet faces
+        are 0; for a periodic perturbation d the directional derivative is ``(grad[:N] * d[:N]).sum()``.
+
+        "hip": the forward history does not stay in memory; steps 2..K are cut into segments of
+        ``segment`` steps, the two newest levels are checkpointed before each segment and the
+        reverse pass recomputes one segment at a time (``segment >= K - 1``: nothing is
+        recomputed). The result does not depend on ``segment`` bit for bit. None: the segment
+        with the fewest levels (:func:`gradient_levels`), checked against the free device memory.
+        """
+        p = self.problem
+        K = p.timesteps
+        if self.u0 is not None:
+            raise ValueError("gradient() starts from rest: u0 is not supported")
+        if not self.receivers:
+            raise ValueError("gradient() needs at least one receiver")
+        obs = torch.as_tensor(observed)
+        if tuple(obs.shape) != (K + 1, len(self.receivers)):
+            raise ValueError(f"observed must have shape {(K + 1, len(self.receivers))} (timesteps + 1 x receivers), "
+                             f"not {tuple(obs.shape)}")
+        if segment is not None and int(segment) < 1:
+            raise ValueError(f"segment must be >= 1 step, not {segment}")
+        obs = obs.detach().cpu()
+        return self._gradient_cpu(obs) if self.backend == "cpu" else self._gradient_hip(obs, segment)
+
+    def _gradient_cpu(self, obs) -> "MediumGradient":
+        import time
+
+        from ..ops import reference
+
+        p = self.problem
+        t0 = time.perf_counter()
+        J, gs, gw, tr = reference.gradient_medium(p.N, p.timesteps, p.speed2, obs, sources=self.sources,
+                                                  wavelet=self.wavelet, receivers=self.receivers,
+                                                  taper=self.taper, L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi,
+                                                  dtype=p.torch_dtype)
+        return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr,
+                              total_ms=(time.perf_counter() - t0) * 1e3,
+                              extra=dict(segment=None, levels=None, recomputed_steps=0))
+
+    def _gradient_hip(self, obs, segment) -> "MediumGradient":
+        import time
+
+        from ..ops import kernels, reference
+
+        p = self.problem
+        N, K, dt = p.N, p.timesteps, p.torch_dtype
+        if not torch.cuda.is_available():
+            raise RuntimeError("the hip backend needs a HIP device")
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else self.device)
+        c = reference.tables(N, K, (p.Lx, p.Ly, p.Lz), p.T, p.pi)[4]
+        h2 = (c["hx2"], c["hy2"], c["hz2"])
+        with torch.cuda.device(dev):
+            level_bytes = kernels.level_bytes(N + 3, N + 1, N + 1, dt)
+            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            if segment is None:
+                segment = best_gradient_segment(K)
+                what = "the smallest schedule"
+            else:
+                segment = int(segment)
+                what = f"the schedule of segment = {segment}"
+            nlev = gradient_levels(K, segment)
+            if nlev * level_bytes > free:
+                raise RuntimeError(f"gradient(): {what} holds {nlev} levels = {nlev * level_bytes} bytes, but only "
+                                   f"{free} bytes of device memory are free")
+            # forward steps 2..K in segments [a, b]; the last one keeps its q, the others a checkpoint
+            segs = [(a, min(a + segment - 1, K)) for a in range(2, K + 1, segment)]
+            qlen = min(segment, K - 1)
+            t0 = time.perf_counter()
+
+            def level():
+                return kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev)
+
+            lv = [level() for _ in range(3)]
+            ad = [level() for _ in range(3)] if len(segs) > 1 else lv  # the adjoint's ring
+            m, acc = level(), level()
+            qb = [level() for _ in range(qlen)]
+            ck = [(level(), level()) for _ in segs[:-1]]
+            mc = reference.medium_coefficient(p.speed2, c["tau"], N, dt)
+            m.copy_(mc)
+            tt = None if self.taper is None else reference.taper_tables(self.taper, N, dt)
+            taper = None if tt is None else tuple(t.to(dev) for t in tt)
+            ent = reference.source_entries(self.sources, N)
+            gsrc = reference.source_table(self.wavelet, K, len(self.sources), c["hx"], c["hy"], c["hz"], dt)
+            g = gsrc[:, [s for _, s in ent]].contiguous().to(dev)
+            src = kernels.source_nodes([nd for nd, _ in ent], lv[0])
+            rec = kernels.receiver_nodes([(i + 1, j, k) for i, j, k in self.receivers], lv[0])
+            traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
+            stat = kernels.new_err(K + 1, device=dev)
+            scratch = kernels.new_err(1, device=dev)  # statistics of the recomputed steps (those of `stat` again)
+            box = (1, N + 1, 1, N - 1, 1, N - 1)
+            wrap = (N, 0, 2, N + 2)
+
+            def forward_step(n, slot, save):
+                u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
+                kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=slot, stat_i=(1, N + 1), wrap=wrap,
+                                    variant=None if save is not None else self.variant, taper=taper, lap_out=save)
+                kernels.inject(u, m, src, g[n - 1], wrap)
+
+            def check(st, name):
+                flags = st[2::3].cpu()  # the one read-back of this pass
+                if bool((flags != 0).any()):
+                    raise RuntimeError(f"gradient(): non-finite values in the {name} pass at layer "
+                                       f"{int((flags != 0).nonzero()[0])}")
+
+            # forward pass: run()'s steps; checkpoints before the segments, q of the last segment
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record()
+            kernels.record(lv[0], rec, traces[0])
+            forward_step(1, stat[3:6], None)
+            kernels.record(lv[1], rec, traces[1])
+            for si, (a, b) in enumerate(segs):
+                last = si == len(segs) - 1
+                if not last:
+                    ck[si][0]._base.copy_(lv[(a - 1) % 3]._base)
+                    ck[si][1]._base.copy_(lv[(a - 2) % 3]._base)
+                for n in range(a, b + 1):
+                    forward_step(n, stat[3 * n:3 * n + 3], qb[n - a] if last else None)
+                    kernels.record(lv[n % 3], rec, traces[n])
+            ev[1].record()
+            check(stat, "forward")
+            tr = traces.cpu()
+            J, res = reference.misfit_medium(tr, obs)
+            anodes, atab = reference.adjoint_source_table(res, self.receivers, N, tt)
+            adj = kernels.source_nodes(anodes, lv[0])
+            ag = atab.to(dev)
+            snodes = kernels.receiver_nodes(reference.source_unique_nodes(self.sources, N), lv[0])
+            a_dev = torch.zeros(K, len(snodes), dtype=dt, device=dev)
+            astat = kernels.new_err(K + 1, device=dev)
+
+            # reverse pass: mu^K into zero levels, then mu^n for n = K-1 .. 1, level mu^n in ad[n % 3]
+            ev[2].record()
+            ad[(K + 1) % 3].zero_()
+            ad[K % 3].zero_()
+            kernels.inject(ad[K % 3], m, adj, ag[K], wrap)
+            kernels.record(ad[K % 3], snodes, a_dev[K - 1])
+            recomputed = 0
+            for si in range(len(segs) - 1, -1, -1):
+                a, b = segs[si]
+                if si != len(segs) - 1:
+                    lv[(a - 1) % 3]._base.copy_(ck[si][0]._base)
+                    lv[(a - 2) % 3]._base.copy_(ck[si][1]._base)
+                    for n in range(a, b + 1):
+                        forward_step(n, scratch, qb[n - a])
+                    recomputed += b - a + 1
+                for n in range(b - 1, a - 2, -1):  # q^n is what forward step n + 1 saved
+                    u1, u2, u = ad[(n + 1) % 3], ad[(n + 2) % 3], ad[n % 3]
+                    kernels.step_medium(u1, u2, m, u, box, first=False, h2=h2, stat=astat[3 * n:3 * n + 3],
+                                        stat_i=(1, N + 1), wrap=wrap, taper=taper, image=(qb[n + 1 - a], acc))
+                    kernels.inject(u, m, adj, ag[n], wrap)
+                    kernels.record(u, snodes, a_dev[n - 1])
+            ev[3].record()
+            check(astat, "adjoint")
+            gs, gw = reference.finish_gradient_medium(acc.cpu(), a_dev.cpu(), gsrc, mc, tt, self.sources, N, c["tau"],
+                                                      c["hx"], c["hy"], c["hz"])
+            torch.cuda.synchronize(dev)
+            ms = (time.perf_counter() - t0) * 1e3
+            return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr, total_ms=ms,
+                                  extra=dict(segment=segment, levels=nlev, recomputed_steps=recomputed,
+                                             forward_ms=ev[0].elapsed_time(ev[1]), reverse_ms=ev[2].elapsed_time(ev[3])))
+
+
+@dataclass
+class MediumGradient:
+    misfit: float               # J = 1/2 sum_{n >= 1} sum_r (trace - observed)^2
+    grad_speed2: torch.Tensor   # (N+1)^3, dJ/dspeed2 on the unique nodes (plane N = plane 0, faces 0)
+    grad_wavelet: torch.Tensor  # [K, S]
+    traces: torch.Tensor        # [K+1, R], those of run()
+    total_ms: float             # wall time of the whole call
+    # segment, levels, recomputed_steps; "hip" also forward_ms / reverse_ms, the device time of the two passes
+    extra: dict = field(default_factory=dict)
+
+
+def gradient_levels(K: int, segment: int) -> int:
+    """Number of grid levels the "hip" schedule of :meth:`MediumSolver.gradient` holds for K
+    timesteps cut into segments of ``segment`` steps (steps 2..K): the forward ring (3), m, acc, the
+    q buffer (one level per step of a segment), a checkpoint pair per segment but the last, and,
+    when there is anything to recompute, a second ring for the adjoint field."""
+    K, segment = int(K), int(segment)
+    if K < 1 or segment < 1:
+        raise ValueError(f"need K >= 1 and segment >= 1, not K={K} segment={segment}")
+    nseg = -(-(K - 1) // segment)
+    return 5 + min(segment, K - 1) + (2 * (nseg - 1) + 3 if nseg > 1 else 0)
+
+
+def best_gradient_segment(K: int) -> int:
+    """The segment length with the fewest levels; every schedule recomputes less than one extra
+    forward pass, and of equal level counts the longer segment (less recomputation) wins."""
+    return min(range(1, max(K - 1, 1) + 1), key=lambda s: (gradient_levels(K, s), -s))

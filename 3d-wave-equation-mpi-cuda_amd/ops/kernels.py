@@ -253,6 +253,13 @@ def alloc_level(nx: int, ny: int, nz: int, dtype, device=None) -> torch.Tensor:
     return buf.as_strided((nx, ny, nz), (si, sj, 1), off)
 
 
+def level_bytes(nx: int, ny: int, nz: int, dtype) -> int:
+    """Size of the allocation behind one :func:`alloc_level` view."""
+    es = torch.empty((), dtype=dtype).element_size()
+    line = 128 // es
+    return (line - 1 + nx * ny * (-(-nz // line) * line)) * es
+
+
 def _check_grid_strided(*ts: torch.Tensor) -> list[int]:
     """Grids that are dense or padded views (last stride 1), all with the same strides."""
     u = ts[0]
@@ -347,7 +354,7 @@ def _check_taper(taper, u) -> list[int]:
 
 
 def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None, chunk: int = 0,
-                variant: str | None = None, taper=None) -> None:
+                variant: str | None = None, taper=None, lap_out=None, image=None) -> None:
     """One layer of ``u_tt = c^2 (lap u + f)`` over ``boxes``: ``u = (2 u1 - u2) + m lap(u1)``, on
     the Taylor start (``first``) ``u = u1 + (0.5 m) lap(u1)``, with ``m = c^2 tau^2`` per node.
 
@@ -362,8 +369,32 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     in (0, 1] (storage indexing). With ``G = gx[i] (gy[j] gz[k])`` the step is the damped leapfrog
     ``u = G ((2 u1 - G u2) + m lap(u1))``, on the Taylor start ``u = G (u1 + (0.5 m) lap(u1))``;
     tables of ones give the undamped bits. None: the undamped kernels.
+
+    Two modes serve the adjoint-state gradient; ``u`` and ``stat`` stay those of the plain step bit
+    for bit. ``lap_out`` (save mode): a grid that receives ``lap(u1)``, the value that entered the
+    update, at the box nodes. ``image = (q, acc)`` (image mode): ``acc = acc + u1 * q`` at the box
+    nodes, the product rounded before the add. These grids match ``u`` in shape, dtype, device and
+    strides; nothing outside the boxes is written and the wrap applies to ``u`` alone. Both modes
+    exist for leapfrog steps (``first=False``) of the default variant only and cannot be combined.
     """
-    gv = _check_grid_strided(u1, u2, m, u)
+    extra = []
+    if lap_out is not None or image is not None:
+        if lap_out is not None and image is not None:
+            raise ValueError("save mode (lap_out) and image mode (image) cannot be combined")
+        if first:
+            raise ValueError("save / image modes: not on the Taylor start (first=True)")
+        if variant not in (None, "nt"):
+            raise ValueError(f"save / image modes exist for the default variant only, not {variant!r}")
+        variant = "nt"
+        if image is not None:
+            if len(image) != 2:
+                raise ValueError("image = (q, acc)")
+            extra = list(image)
+        else:
+            extra = [lap_out]
+        if not all(isinstance(t, torch.Tensor) for t in extra):
+            raise ValueError("lap_out, q and acc must be tensors")
+    gv = _check_grid_strided(u1, u2, m, u, *extra)
     if isinstance(boxes[0], int):
         boxes = [boxes]
     if not 1 <= len(boxes) <= 7:
@@ -380,7 +411,8 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     fn = getattr(_C(), "k_step_medium_" + _sfx(u))
     fn(bool(first), u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, bl, int(stat_i[0]),
        int(stat_i[1]), w, [float(v) for v in h2], stat.data_ptr(), int(chunk), _stream(),
-       _MEDIUM_VARIANTS[variant], *gp)
+       _MEDIUM_VARIANTS[variant], *gp, lap_out.data_ptr() if lap_out is not None else 0,
+       *((image[0].data_ptr(), image[1].data_ptr()) if image is not None else (0, 0)))
 
 
 def inject(u, m, nodes, g, wrap=None) -> None:

@@ -325,3 +325,181 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
         wrap(u)
         sample(n, u)
     return traces, lv[K % 3][1:N + 2].clone(), mx
+
+
+# ---- misfit gradients of the medium solver (adjoint state) ---------------------------------
+#
+# From rest, on the unique nodes (plane N is plane 0, Dirichlet faces 0), solve_medium is
+#   u^1 = m g[0] e_s,   u^{n+1} = G ((2 u^n - G u^{n-1}) + m L u^n) + m g[n] e_s,
+# with L symmetric. With J = 1/2 sum_{n=1..K} sum_r (u^n[x_r] - d[n, r])^2, lambda the adjoint state
+# and mu = m G lambda, the adjoint recurrence is the forward step run backwards in time,
+#   mu^K = m (G rho^K),   mu^n = G ((2 mu^{n+1} - G mu^{n+2}) + m L mu^{n+1}) + m (G rho^n),
+# rho^n the residuals scattered to the receiver nodes, and with q^n = L u^n
+#   dJ/dm = (sum_{n=K-1..1} mu^{n+1} q^n) / m + e_s (sum_n mu^{n+1}[x_s] g[n, s]) / (m[x_s] G[x_s]),
+#   dJ/dg[n, s] = mu^{n+1}[x_s] / G[x_s].
+# The helpers below are the host-side arithmetic shared by gradient_medium and the HIP front-end
+# (models/medium.py): both call them on CPU tensors, so they round alike.
+
+def _medium_box(N: int):
+    return (1, N + 1, 1, N - 1, 1, N - 1)
+
+
+def _wrap_x(u, N: int) -> None:
+    u[0] = u[N]
+    u[N + 2] = u[2]
+
+
+def taper_at(tt, node):
+    """G = gx[i] (gy[j] gz[k]) at a storage node, rounded like ``step_medium``; ``tt`` = the
+    ``taper_tables`` (None: 1)."""
+    if tt is None:
+        return 1.0
+    i, j, k = node
+    return tt[0][i] * (tt[1][j] * tt[2][k])
+
+
+def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None, receivers=(), taper=None,
+                            L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
+                            keep_lap: bool = False):
+    """``solve_medium`` from rest, restated out of place: every level is a new tensor, so
+    ``torch.autograd`` can differentiate the traces with respect to ``speed2`` (an ``(N+1)^3``
+    tensor) and ``wavelet``. The operations and their order are those of ``solve_medium``: the traces
+    ``[K+1, R]`` are equal bit for bit. ``keep_lap``: also return [q^1 .. q^{K-1}], q^n = lap u^n on
+    the stencil nodes (the value step n+1 uses)."""
+    c = tables(N, K, L, T, pi)[4]
+    tt = None if taper is None else taper_tables(taper, N, dtype)
+    m = medium_coefficient(speed2, c["tau"], N, dtype)
+    ent = source_entries(sources, N)
+    g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
+    rec = [(i + 1, j, k) for i, j, k in receivers]
+    box = _medium_box(N)
+    u2 = torch.zeros(N + 3, N + 1, N + 1, dtype=dtype)
+    u1 = torch.zeros(N + 3, N + 1, N + 1, dtype=dtype)
+    rows = [torch.stack([u1[nd] for nd in rec]) if rec else torch.zeros(0, dtype=dtype)]
+    laps = []
+    for n in range(1, K + 1):
+        if keep_lap and n >= 2:
+            laps.append(laplace7(u1, c["hx2"], c["hy2"], c["hz2"])[0:N + 1, 0:N - 1, 0:N - 1])
+        vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt)
+        u = torch.zeros(N + 3, N + 1, N + 1, dtype=dtype)
+        u[1:N + 2, 1:N, 1:N] = vals
+        for nd, s in ent:
+            u[nd] = u[nd] + m[nd] * g[n - 1, s]
+        _wrap_x(u, N)
+        rows.append(torch.stack([u[nd] for nd in rec]) if rec else torch.zeros(0, dtype=dtype))
+        u2, u1 = u1, u
+    traces = torch.stack(rows)
+    return (traces, laps) if keep_lap else traces
+
+
+def misfit_medium(traces, observed):
+    """J = 1/2 sum_{n=1..K} sum_r (traces[n, r] - observed[n, r])^2 in the dtype of ``traces`` (row
+    0 does not enter); returns (J as a float, the residuals ``[K+1, R]`` with row 0 zeroed)."""
+    if tuple(observed.shape) != tuple(traces.shape):
+        raise ValueError(f"observed must have shape {tuple(traces.shape)} (timesteps + 1 x receivers), "
+                         f"not {tuple(observed.shape)}")
+    res = traces - torch.as_tensor(observed).to(traces.dtype).cpu()
+    res[0] = 0
+    return (0.5 * (res * res).sum()).item(), res
+
+
+def adjoint_source_table(res, receivers, N: int, tt):
+    """Adjoint sources of the residuals ``res`` ``[K+1, R]``: ([storage nodes], table ``[K+1, E]``).
+
+    Receivers that share a unique node (planes 0 and N are one plane) are summed in list order;
+    a receiver on a Dirichlet face injects nothing; a node on the periodic plane yields entries on
+    both storage planes, like ``source_entries``. Column e of the table is ``G[node] * rho`` rounded
+    in the dtype of ``res`` (``tt`` = the ``taper_tables``, None: G = 1)."""
+    rho = {}
+    for r, (i, j, k) in enumerate(receivers):
+        if j in (0, N) or k in (0, N):
+            continue
+        key = (i % N, j, k)
+        rho[key] = rho[key] + res[:, r] if key in rho else res[:, r].clone()
+    nodes, cols = [], []
+    for (i, j, k), v in rho.items():
+        for gi in ((0, N) if i == 0 else (i,)):
+            nd = (gi + 1, j, k)
+            nodes.append(nd)
+            cols.append(taper_at(tt, nd) * v)
+    tab = torch.stack(cols, 1).contiguous() if cols else torch.zeros(res.shape[0], 0, dtype=res.dtype)
+    return nodes, tab
+
+
+def source_unique_nodes(sources, N: int):
+    """One storage node per source for sampling the adjoint field: plane N is read on plane 0."""
+    return [((i % N) + 1, j, k) for i, j, k in sources]
+
+
+def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: float, hy: float, hz: float):
+    """The host-side end of the gradient. acc ``[N+3][N+1][N+1]`` = sum mu^{n+1} q^n in storage
+    (faces 0), a ``[K, S]`` with ``a[n, s] = mu^{n+1}[x_s]``, g = the ``source_table``, m = the
+    ``medium_coefficient``, all CPU tensors of the working dtype. Returns (dJ/dspeed2 ``(N+1)^3``
+    with respect to the unique nodes: plane N a copy of plane 0, faces 0; dJ/dwavelet ``[K, S]``)."""
+    gm = acc[1:N + 2] / m[1:N + 2]
+    nodes = source_unique_nodes(sources, N)
+    if nodes:
+        dots = (a * g).sum(0)
+        for s, nd in enumerate(nodes):
+            at = (nd[0] - 1, nd[1], nd[2])
+            gm[at] = gm[at] + dots[s] / (m[nd] * taper_at(tt, nd))
+    grad = (gm * tau) * tau  # m = (speed2 tau) tau
+    grad[N] = grad[0]
+    grad[:, 0, :] = 0
+    grad[:, N, :] = 0
+    grad[:, :, 0] = 0
+    grad[:, :, N] = 0
+    gw = torch.zeros_like(a)
+    for s, nd in enumerate(nodes):
+        gw[:, s] = a[:, s] / taper_at(tt, nd) / (hx * hy * hz)
+    if gw.shape[0] > 0:
+        gw[0] = gw[0] * 0.5
+    return grad, gw
+
+
+def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,
+                    L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64):
+    """Misfit J of the traces against ``observed`` ``[K+1, R]`` (row 0 ignored) and its gradients by
+    the hand-written adjoint above: (J, dJ/dspeed2 ``(N+1)^3``, dJ/dwavelet ``[K, S]``, traces).
+
+    The adjoint field runs on ``step_medium(first=False)`` itself, each step followed by the
+    injection of ``G rho``; ``acc = acc + mu q`` is accumulated for n = K-1 .. 1 in that order.
+    dJ/dspeed2 is taken with respect to the unique nodes: entry [0] is the derivative with respect
+    to the shared value of planes 0 and N (autograd's ``g[0] + g[N]`` for an ``(N+1)^3`` leaf) and
+    entry [N] a copy of it; for a periodic perturbation d the directional derivative is
+    ``(grad[:N] * d[:N]).sum()``."""
+    with torch.no_grad():
+        traces, laps = forward_medium_autograd(N, K, speed2, sources=sources, wavelet=wavelet,
+                                               receivers=receivers, taper=taper, L=L, T=T, pi=pi, dtype=dtype,
+                                               keep_lap=True)
+        J, res = misfit_medium(traces, observed)
+        c = tables(N, K, L, T, pi)[4]
+        tt = None if taper is None else taper_tables(taper, N, dtype)
+        m = medium_coefficient(speed2, c["tau"], N, dtype)
+        g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
+        anodes, atab = adjoint_source_table(res, receivers, N, tt)
+        snodes = source_unique_nodes(sources, N)
+        box = _medium_box(N)
+        shape = (N + 3, N + 1, N + 1)
+        a = torch.zeros(K, len(snodes), dtype=dtype)
+
+        def finish_level(mu, n):  # inject G rho^n, wrap, sample mu^n at the sources
+            for e, nd in enumerate(anodes):
+                mu[nd] = mu[nd] + m[nd] * atab[n, e]
+            _wrap_x(mu, N)
+            for s, nd in enumerate(snodes):
+                a[n - 1, s] = mu[nd]
+
+        mu2 = torch.zeros(shape, dtype=dtype)
+        mu1 = torch.zeros(shape, dtype=dtype)
+        finish_level(mu1, K)
+        acc = torch.zeros(shape, dtype=dtype)
+        for n in range(K - 1, 0, -1):
+            vals = step_medium(mu1, mu2, m, box, first=False, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt)
+            acc[1:N + 2, 1:N, 1:N] = acc[1:N + 2, 1:N, 1:N] + mu1[1:N + 2, 1:N, 1:N] * laps[n - 1]
+            mu = torch.zeros(shape, dtype=dtype)
+            mu[1:N + 2, 1:N, 1:N] = vals
+            finish_level(mu, n)
+            mu2, mu1 = mu1, mu
+        grad, gw = finish_gradient_medium(acc, a, g, m, tt, sources, N, c["tau"], c["hx"], c["hy"], c["hz"])
+        return J, grad, gw, traces

@@ -4,6 +4,7 @@
     python tools/bench_medium.py [--N 512] [--steps 100] [--dtypes fp64,fp32]
                                  [--variants default,plain,r2,r2nt] [--repeat 3] [--no-yardstick]
                                  [--taper WIDTH]
+    python tools/bench_medium.py --gradient [--N 512] [--steps 100] [--dtypes fp64,fp32] [--segment 10]
 
 For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
 and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
@@ -14,6 +15,13 @@ counts the bytes the algorithm needs: u1, u2, m read and u written once per node
 and variant, the same run with the absorbing sponge `sponge_taper(prob, WIDTH)` (the TAPER
 instantiation of k_march_m, the same bytes), alternating with the untapered one inside each
 repeat, and reports its ms/step and the ratio tapered / untapered. Prints one JSON line.
+
+`--gradient` measures the adjoint-state gradient instead (MediumSolver.gradient), per dtype in one
+process: ms/step of the plain step, the save step (+ lap_out: 40 B per node in fp64 against 32) and
+the image step (+ q, acc read, acc written: 56 B), `--repeat` rounds of 20 launches each, the three
+alternating inside each round, with and without a sponge of 16 nodes; then, alternating as well,
+one forward run() and gradient() with every q stored (segment = steps) and with `--segment`: the
+device time of the passes beside run()'s time loop, and the wall time of the whole call.
 """
 import argparse
 import json
@@ -39,6 +47,99 @@ def smooth_speed2(N: int, lo: float, hi: float, seed: int = 7):
     return s.contiguous()
 
 
+def gradient_bench(a) -> int:
+    import math
+
+    import torch
+
+    import wave3d
+    from wave3d.ops import kernels, reference
+
+    N, K = a.N, a.steps
+    h = 3.1415926535 / N
+    hi = (0.9 / math.sqrt(3) * h * K) ** 2
+    speed2 = smooth_speed2(N, 0.5 * hi, hi)
+    nodes = float(N + 1) ** 3
+    out = {"N": N, "steps": K, "device": torch.cuda.get_device_name(0), "kernels": [], "gradient": []}
+    dev = torch.device("cuda", 0)
+    for dtype in a.dtypes.split(","):
+        es = 8 if dtype == "fp64" else 4
+        prob = wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype)
+        dt = prob.torch_dtype
+        c = reference.tables(N, K)[4]
+        h2 = (c["hx2"], c["hy2"], c["hz2"])
+        sponge = wave3d.sponge_taper(prob, 16)
+
+        # the three kernels on one set of levels (values of a short run, so nothing is denormal)
+        lv = [kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(6)]
+        u1, u2, m, u, x, q = lv
+        m.copy_(reference.medium_coefficient(speed2, c["tau"], N, dt))
+        g = torch.Generator().manual_seed(1)
+        seed = torch.rand(N + 1, N + 1, generator=g, dtype=torch.float64).to(dt).to(dev)
+        for t in (u1, u2, q):
+            t[:, 1:N, 1:N] = seed[1:N, 1:N]
+        box, wrap = (1, N + 1, 1, N - 1, 1, N - 1), (N, 0, 2, N + 2)
+        stat = kernels.new_err(1, device=dev)
+        reps = 20
+        for tp_name, tp in (("", None), ("sponge", tuple(t.to(dev) for t in reference.taper_tables(sponge, N, dt)))):
+            modes = {"plain": {}, "save": {"lap_out": x}, "image": {"image": (q, x)}}
+            ms = {k: [] for k in modes}
+            for rnd in range(a.repeat + 1):  # round 0 warms up
+                for name, kw in modes.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    x.zero_()
+                    e0.record()
+                    for _ in range(reps):
+                        kernels.step_medium(u1, u2, m, u, box, first=False, h2=h2, stat=stat, stat_i=(1, N + 1),
+                                            wrap=wrap, taper=tp, **kw)
+                    e1.record()
+                    e1.synchronize()
+                    if rnd:
+                        ms[name].append(e0.elapsed_time(e1) / reps)
+            for name, bpn in (("plain", 4), ("save", 5), ("image", 7)):
+                best = min(ms[name])
+                out["kernels"].append({"dtype": dtype, "mode": name, "sponge": bool(tp_name),
+                                       "ms_per_step": round(best, 4), "all_ms": [round(v, 4) for v in ms[name]],
+                                       "bytes_per_node": bpn * es, "expected_ratio": bpn / 4,
+                                       "ratio_to_plain": round(best / min(ms["plain"]), 4),
+                                       "eff_tb_per_s": round(bpn * es * nodes / (best * 1e-3) / 1e12, 3)})
+                print(f"bench_medium: {dtype} {name} {tp_name}: {best:.4f} ms/step", file=sys.stderr, flush=True)
+        del lv, u1, u2, m, u, x, q
+        torch.cuda.empty_cache()
+
+        # gradient() beside one forward run()
+        w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
+        mid = N // 2
+        sol = wave3d.MediumSolver(prob, "hip", sources=[(mid, mid, mid)], wavelet=w,
+                                  receivers=[(mid - K // 5, mid, mid), (mid, mid - K // 4, mid + 3)], taper=sponge)
+        obs = 0.9 * sol.run().traces  # warm-up
+        cfgs = [("run", None), ("all_q", K), (f"segment_{a.segment}", a.segment)]
+        rows = {n: [] for n, _ in cfgs}
+        for _ in range(a.repeat):
+            for name, seg in cfgs:
+                if seg is None:
+                    r = sol.run()
+                    rows[name].append({"loop_ms": round(r.total_ms, 2)})
+                else:
+                    r = sol.gradient(obs, segment=seg)
+                    assert math.isfinite(r.misfit) and r.misfit > 0
+                    rows[name].append({"wall_ms": round(r.total_ms, 1), "forward_ms": round(r.extra["forward_ms"], 2),
+                                       "reverse_ms": round(r.extra["reverse_ms"], 2), "levels": r.extra["levels"],
+                                       "recomputed_steps": r.extra["recomputed_steps"]})
+                print(f"bench_medium: {dtype} {name}: {rows[name][-1]}", file=sys.stderr, flush=True)
+                del r
+                torch.cuda.empty_cache()
+        run_ms = min(v["loop_ms"] for v in rows["run"])
+        for name, seg in cfgs[1:]:
+            best = min(rows[name], key=lambda v: v["forward_ms"] + v["reverse_ms"])
+            passes = best["forward_ms"] + best["reverse_ms"]
+            out["gradient"].append({"dtype": dtype, "schedule": name, **best, "passes_ms": round(passes, 2),
+                                    "run_loop_ms": run_ms, "passes_vs_run": round(passes / run_ms, 3),
+                                    "wall_ms_all": [v["wall_ms"] for v in rows[name]]})
+    print(json.dumps(out))
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--N", type=int, default=512)
@@ -49,6 +150,8 @@ def main(argv=None) -> int:
     ap.add_argument("--no-yardstick", action="store_true")
     ap.add_argument("--taper", type=int, default=0, metavar="WIDTH",
                     help="also time the step with sponge_taper(prob, WIDTH)")
+    ap.add_argument("--gradient", action="store_true", help="time the gradient's kernels and schedules instead")
+    ap.add_argument("--segment", type=int, default=10, help="--gradient: steps per checkpoint segment")
     a = ap.parse_args(argv)
 
     import math
@@ -61,6 +164,8 @@ def main(argv=None) -> int:
         print("bench_medium: no HIP device (timings are only taken on the GPU)", file=sys.stderr)
         return 2
     N, K = a.N, a.steps
+    if a.gradient:
+        return gradient_bench(a)
     variants = a.variants.split(",")
     # speed2 <= hi keeps the Courant number at 0.9 of the limit 1/sqrt(3) for T = 1
     h = 3.1415926535 / N
