@@ -333,14 +333,17 @@ template <class T>
 void k_step_medium(bool first, uintptr_t u1, uintptr_t u2, uintptr_t m, uintptr_t u, const std::vector<i64>& g,
                    const std::vector<std::vector<int>>& boxes, int ei0, int ei1, const std::vector<int>& wrap,
                    const std::vector<double>& h2, uintptr_t err, int chunk, uintptr_t stream, int variant,
-                   uintptr_t gx, uintptr_t gy, uintptr_t gz, uintptr_t lap_out, uintptr_t q, uintptr_t acc) {
+                   uintptr_t gx, uintptr_t gy, uintptr_t gz, uintptr_t lap_out, uintptr_t q, uintptr_t acc, int order,
+                   const std::vector<int>& mirror) {
     std::vector<Box> bx;
     for (auto& b : boxes) bx.push_back(tobox(b));
     W3D_REQUIRE(h2.size() == 3, "h2 = (hx2, hy2, hz2)");
     const double h[3] = {h2[0], h2[1], h2[2]};
+    // mirror: empty = none, or (j_lo, j_hi, k_lo, k_hi) with no_mirror for a side without a face
+    W3D_REQUIRE(mirror.empty() || mirror.size() == 4, "mirror = (j_lo, j_hi, k_lo, k_hi)");
     launch_step_medium<T>(first, P<T>(u1), P<T>(u2), P<T>(m), P<T>(u), gview(g), bx.data(), int(bx.size()), ei0,
                           ei1, towrap(wrap), h, P<u64>(err), chunk, (hipStream_t)stream, variant, P<T>(gx), P<T>(gy),
-                          P<T>(gz), P<T>(lap_out), P<T>(q), P<T>(acc));
+                          P<T>(gz), P<T>(lap_out), P<T>(q), P<T>(acc), order, mirror.empty() ? nullptr : mirror.data());
 }
 
 // nodes: device int32 [n][3] of (i, j, k); g / out: n device values
@@ -559,13 +562,22 @@ PYBIND11_MODULE(_wave3d_C, m) {
     m.def("tb_supported", [](int depth, int rows, int waves, bool fm) {
         return depth == 3 && tb3_supported(rows, waves, fm);
     }, py::arg("depth"), py::arg("rows"), py::arg("waves"), py::arg("fm") = false);
-    m.def("k_step_medium_f64", &k_step_medium<double>);
-    m.def("k_step_medium_f32", &k_step_medium<float>);
+    // order and mirror are optional (order 2, no faces): every earlier positional call still binds
+#define W3D_STEP_MEDIUM_ARGS                                                                                      \
+    py::arg("first"), py::arg("u1"), py::arg("u2"), py::arg("m"), py::arg("u"), py::arg("grid"), py::arg("boxes"), \
+        py::arg("ei0"), py::arg("ei1"), py::arg("wrap"), py::arg("h2"), py::arg("err"), py::arg("chunk"),          \
+        py::arg("stream"), py::arg("variant"), py::arg("gx"), py::arg("gy"), py::arg("gz"), py::arg("lap_out"),    \
+        py::arg("q"), py::arg("acc"), py::arg("order") = 2, py::arg("mirror") = std::vector<int>{}
+    m.def("k_step_medium_f64", &k_step_medium<double>, W3D_STEP_MEDIUM_ARGS);
+    m.def("k_step_medium_f32", &k_step_medium<float>, W3D_STEP_MEDIUM_ARGS);
+#undef W3D_STEP_MEDIUM_ARGS
     m.def("k_inject_f64", &k_inject<double>);
     m.def("k_inject_f32", &k_inject<float>);
     m.def("k_record_f64", &k_record<double>);
     m.def("k_record_f32", &k_record<float>);
     m.def("medium_variant", &medium_variant);
+    m.def("medium_weight", &medium_weight);
+    m.attr("no_mirror") = kNoMirror;
     m.def("k_init_f64", &k_init<double>);
     m.def("k_init_f32", &k_init<float>);
     m.def("k_faces_f64", &k_faces<double>);

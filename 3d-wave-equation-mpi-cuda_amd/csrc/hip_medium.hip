@@ -11,6 +11,9 @@
 //    TAPER: the damped leapfrog of an absorbing sponge, u = G ((2 u1 - G u2) + m lap) with the
 //    separable G = gx[i] (gy[j] gz[k]): gy gz is one register per lane row, formed before the
 //    march, gx[i] a wave-uniform scalar load fetched one plane ahead. No further stream.
+//  * k_march_mh: the same march with a star stencil of half-width M = 2 or 4 per axis (space
+//    orders 4 and 8): a (2M + 2)-slot u^{n-1} ring, an M-deep LDS halo and odd reflection at the
+//    Dirichlet faces (described at the kernel).
 //  * k_inject / k_record: one thread per source entry / receiver.
 //
 // FP contraction is off (-ffp-contract=off + the pragmas in stencil_math.hpp): every operation
@@ -294,6 +297,338 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
     commit_errors(ma, T(kErrInit), chk, p.err);
 }
 
+// ---- space orders 4 and 8: k_march_mh ------------------------------------------------------
+// Central second-derivative weights of the star stencil of half-width M: double quotients of
+// integers, cast to T by the kernel (ops/reference.py star_weights forms the same values).
+constexpr double star_weight(int M, int d) {
+    return M == 1   ? (d == 0 ? -2.0 : 1.0)
+           : M == 2 ? (d == 0 ? -5.0 / 2.0 : d == 1 ? 4.0 / 3.0 : -1.0 / 12.0)
+                    : (d == 0   ? -205.0 / 72.0
+                       : d == 1 ? 8.0 / 5.0
+                       : d == 2 ? -1.0 / 5.0
+                       : d == 3 ? 8.0 / 315.0
+                                : -1.0 / 560.0);
+}
+
+template <class T>
+struct MediumParamsH : MediumParams<T> {
+    int mj0, mj1, mk0, mk1;  // reflecting faces (storage indices); -+2^29 = none on that side
+};
+
+// k_march_m's design with a star stencil of half-width M (2 or 4) per axis: the same tile, march,
+// streams, stores, statistic and masking. What differs:
+//  * the u1 ring holds the planes i-M .. i+M and the prefetch slot, NS = 2M + 2 register slots per
+//    row; plane x lives in slot (x - ib + M) % NS, and the i loop is unrolled by NS so that every
+//    slot index is a constant (no in-flight load is ever copied);
+//  * the LDS tile carries an M-deep halo in j and k, (4R + 2M) x (64 + 2M) per buffer, no corners;
+//    its 2M 64 + 4R 2M halo cells are dealt to the 256 threads, NH cells each, prefetched one plane
+//    ahead like k_march_m's single cell;
+//  * every load of u1, own node or halo, goes through `src`: a node beyond a reflecting face f is
+//    read at 2f - j and negated when it is staged (odd reflection, an exact negation); a node with
+//    no source in the plane gets kOOB (reads 0). The host has checked that each node a box node
+//    reaches has a source, so 0 never enters a stored value. The x neighbours of the lane's own
+//    nodes come from the ring unreflected: only box nodes use them, and those lie inside the faces.
+// Per node and axis: t = c_0 v, t = t + c_d (p_-d + p_+d) for d = 1 .. M; the j neighbours of a
+// lane's own rows come from its registers, the rest and all k neighbours from LDS.
+template <class T, int M, bool FIRST, int R, bool TAPER, int MODE = kPlain>
+__global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p) {
+    constexpr int kTJ = kWaves * R;
+    constexpr int NS = 2 * M + 2;
+    constexpr int LR = kTJ + 2 * M, LC = kTK + 2 * M;
+    constexpr int kHaloJ = 2 * M * kTK, kHaloK = kTJ * 2 * M;
+    constexpr int NH = (kHaloJ + kHaloK + kThreads - 1) / kThreads;
+    constexpr unsigned ES = sizeof(T);
+    __shared__ T lds[2][LR][LC];
+
+    const int bid = xcd_swizzle(blockIdx.x, gridDim.x, p.xcd);
+    const int b = find_box(p, bid);
+    const BoxLaunch B = p.box[b];
+    int local = bid - B.block_begin;
+    const int tk = local % B.tiles_k;
+    local /= B.tiles_k;
+    const int tj = local % B.tiles_j;
+    const int ci = local / B.tiles_j;
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int kb = B.kbase + tk * kTK;
+    const int k = kb + lane;
+    const int jt = B.j0 + tj * kTJ;
+    const int ib = B.i0 + ci * B.chunk;
+    const int ie = min(B.i1, ib + B.chunk - 1);
+
+    const bool kin = k >= B.k0 && k <= B.k1;
+    const i64 si = p.si;
+    const unsigned pbytes = unsigned(si) * ES;
+    auto boff = [&](int j, int kk, bool ok) { return ok ? unsigned(j * p.sj + kk + p.poff) * ES : kOOB; };
+    auto prs = [&](const T* base, int i) { return plane_rsrc(base + (i64(i) * si - p.poff), pbytes); };
+    // byte offset of the source of u1(j, kk) in a plane block and whether it is negated
+    auto src = [&](int j, int kk, bool& neg) {
+        neg = false;
+        if (j < p.mj0) j = 2 * p.mj0 - j, neg = !neg;
+        else if (j > p.mj1) j = 2 * p.mj1 - j, neg = !neg;
+        if (kk < p.mk0) kk = 2 * p.mk0 - kk, neg = !neg;
+        else if (kk > p.mk1) kk = 2 * p.mk1 - kk, neg = !neg;
+        return boff(j, kk, j >= 0 && j <= p.jmax && kk >= 0 && kk <= p.kmax);
+    };
+
+    unsigned oa[R], ou2[R], os[R];
+    bool valid[R], ng[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int j = jt + w * R + r;
+        valid[r] = kin && j <= B.j1;
+        oa[r] = src(j, k, ng[r]);
+        ou2[r] = boff(j, k, !FIRST && valid[r]);
+        os[r] = boff(j, k, valid[r]);  // stores, and the loads of m
+    }
+
+    // halo cells of this thread: cell c = h 256 + tid; the first 2M 64 are the rows jt-M .. jt-1 and
+    // jt+TJ .. jt+TJ+M-1, the next TJ 2M the columns kb-M .. kb-1 and kb+64 .. kb+64+M-1
+    unsigned hoff[NH];
+    int hidx[NH];  // LDS cell (element index in a buffer), -1 = none
+    bool hng[NH];
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        const int c = h * kThreads + int(threadIdx.x);
+        int j = 0, kk = 0;
+        hidx[h] = -1;
+        hng[h] = false;
+        hoff[h] = kOOB;
+        if (c < kHaloJ) {
+            const int hr = c / kTK, col = c % kTK;
+            j = hr < M ? jt - M + hr : jt + kTJ + hr - M;
+            kk = kb + col;
+            hidx[h] = (hr < M ? hr : kTJ + hr) * LC + M + col;
+        } else if (c < kHaloJ + kHaloK) {
+            const int c2 = c - kHaloJ;
+            const int rr = c2 / (2 * M), hc = c2 % (2 * M);
+            j = jt + rr;
+            kk = hc < M ? kb - M + hc : kb + kTK + hc - M;
+            hidx[h] = (M + rr) * LC + (hc < M ? hc : kTK + hc);
+        }
+        if (hidx[h] >= 0) hoff[h] = src(j, kk, hng[h]);
+    }
+    constexpr int kMAux = 2;   // non-temporal m (read once per step)
+    constexpr int kStAux = 2;  // non-temporal stores (write-once stream)
+
+    static_assert(MODE == kPlain || !FIRST, "save / image modes: leapfrog steps only");
+    static_assert(M == 2 || M == 4, "orders 4 and 8");
+    constexpr bool kImg = MODE == kImage;
+    T u1[NS][R], u2[2][R], mm[2][R];
+    T qq[kImg ? 2 : 1][kImg ? R : 1], aa[kImg ? 2 : 1][kImg ? R : 1];
+    T hv[2][NH];
+    if constexpr (kImg) {
+        const auto rQ = prs(p.q, ib), rA = prs(p.acc, ib);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            qq[0][r] = bld<T, 2>(rQ, os[r]);
+            aa[0][r] = bld<T, 2>(rA, os[r]);
+            qq[1][r] = aa[1][r] = T(0);
+        }
+    }
+    {
+        // planes ib-M .. ib+M into slots 0 .. 2M (the host keeps the boxes M planes inside)
+#pragma unroll
+        for (int s = 0; s <= 2 * M; ++s) {
+            const auto rp = prs(p.u1, ib - M + s);
+#pragma unroll
+            for (int r = 0; r < R; ++r) u1[s][r] = bld<T>(rp, oa[r]);
+            if (s == M) {
+#pragma unroll
+                for (int h = 0; h < NH; ++h) {
+                    hv[0][h] = bld<T>(rp, hoff[h]);
+                    hv[1][h] = T(0);
+                }
+            }
+        }
+        const auto q0 = prs(p.u2, ib), m0 = prs(p.m, ib);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            u1[NS - 1][r] = T(0);
+            u2[0][r] = FIRST ? T(0) : bld<T>(q0, ou2[r]);
+            u2[1][r] = T(0);
+            mm[0][r] = bld<T, kMAux>(m0, os[r]);
+            mm[1][r] = T(0);
+        }
+    }
+    const T hx2 = p.hx2, hy2 = p.hy2, hz2 = p.hz2;
+    const T yx2 = p.yx2, yy2 = p.yy2, yz2 = p.yz2;
+
+    T gyz[TAPER ? R : 1];
+    T gxn = T(1);
+    if constexpr (TAPER) {
+#pragma clang fp contract(off)
+        const T gzk = p.gz[min(k, p.kmax)];
+#pragma unroll
+        for (int r = 0; r < R; ++r) gyz[r] = ldconst(p.gy, min(jt + w * R + r, p.jmax)) * gzk;
+        gxn = ldconst(p.gx, ib);
+    }
+
+    T ma = T(kErrInit);
+    T chk = T(0);
+    T* const lds0 = &lds[0][0][0];
+
+    auto plane = [&](auto phase, const int i) {
+#pragma clang fp contract(off)
+        constexpr int P = decltype(phase)::value;
+        constexpr int SC = (P + M) % NS;          // plane i
+        constexpr int SN = (P + 2 * M + 1) % NS;  // plane i+M+1, prefetched here
+        constexpr int H0 = P & 1, H1 = (P + 1) & 1;
+        {
+            const bool more = i < ie;
+            const unsigned nb = more ? pbytes : 0u;
+            const int dn = more ? M + 1 : 0, d1 = more ? 1 : 0;
+            const auto rN = plane_rsrc(p.u1 + (i64(i + dn) * si - p.poff), nb);
+            const auto rH = plane_rsrc(p.u1 + (i64(i + d1) * si - p.poff), nb);
+            const auto rU = plane_rsrc(p.u2 + (i64(i + d1) * si - p.poff), nb);
+            const auto rM = plane_rsrc(p.m + (i64(i + d1) * si - p.poff), nb);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                u1[SN][r] = bld<T>(rN, oa[r]);
+                if (!FIRST) u2[H1][r] = bld<T>(rU, ou2[r]);
+                mm[H1][r] = bld<T, kMAux>(rM, os[r]);
+            }
+#pragma unroll
+            for (int h = 0; h < NH; ++h) hv[H1][h] = bld<T>(rH, hoff[h]);
+            if constexpr (kImg) {
+                const auto rQ = plane_rsrc(p.q + (i64(i + d1) * si - p.poff), nb);
+                const auto rA = plane_rsrc(p.acc + (i64(i + d1) * si - p.poff), nb);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    qq[H1][r] = bld<T, 2>(rQ, os[r]);
+                    aa[H1][r] = bld<T, 2>(rA, os[r]);
+                }
+            }
+        }
+
+        // stage plane i, reflected nodes negated
+        T cs[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            cs[r] = ng[r] ? -u1[SC][r] : u1[SC][r];
+            lds[H0][M + w * R + r][M + lane] = cs[r];
+        }
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+            if (hidx[h] >= 0) lds0[H0 * (LR * LC) + hidx[h]] = hng[h] ? -hv[H0][h] : hv[H0][h];
+        __syncthreads();
+
+        const bool erow = i >= p.ei0 && i <= p.ei1;
+        const T gxi = gxn;
+        if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
+        T vv[R];
+        T xv[MODE == kPlain ? 1 : R];  // kSave: lap; kImage: the new acc
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int lr = M + w * R + r;
+            const T c = u1[SC][r];
+            T tx = T(star_weight(M, 0)) * c, ty = tx, tz = tx;
+#pragma unroll
+            for (int d = 1; d <= M; ++d) {
+                const T wd = T(star_weight(M, d));
+                tx = tx + wd * (u1[(SC + NS - d) % NS][r] + u1[(SC + d) % NS][r]);
+                const T jm = r - d >= 0 ? cs[r - d >= 0 ? r - d : 0] : lds[H0][lr - d][M + lane];
+                const T jp = r + d < R ? cs[r + d < R ? r + d : 0] : lds[H0][lr + d][M + lane];
+                ty = ty + wd * (jm + jp);
+                tz = tz + wd * (lds[H0][lr][M + lane - d] + lds[H0][lr][M + lane + d]);
+            }
+            T lap = T(0);
+            lap = lap + div_const(tx, hx2, yx2);
+            lap = lap + div_const(ty, hy2, yy2);
+            lap = lap + div_const(tz, hz2, yz2);
+            if constexpr (MODE == kSave) xv[r] = lap;
+            if constexpr (kImg) {
+                const T pr = c * qq[H0][r];
+                xv[r] = aa[H0][r] + pr;
+            }
+            if constexpr (FIRST) {
+                const T half_m = T(0.5) * mm[H0][r];  // exact
+                vv[r] = taylor_first(c, lap, half_m);
+                if constexpr (TAPER) vv[r] = (gxi * gyz[r]) * vv[r];
+            } else if constexpr (TAPER) {
+                const T g = gxi * gyz[r];
+                vv[r] = g * leapfrog(c, g * u2[H0][r], lap, mm[H0][r]);
+            } else {
+                vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]);
+            }
+        }
+        {
+            const auto rs = prs(p.u, i);
+#pragma unroll
+            for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rs, os[r]);
+#pragma unroll
+            for (int g = 0; g < 2; ++g)
+                if (i >= p.w_lo[g] && i <= p.w_hi[g]) {
+                    const auto rw = prs(p.u, i + p.w_sh[g]);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
+                }
+            if constexpr (MODE != kPlain) {
+                const auto rx = prs(MODE == kSave ? p.lap_out : p.acc, i);
+#pragma unroll
+                for (int r = 0; r < R; ++r) bst<kStAux>(xv[r], rx, os[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (!valid[r]) continue;
+            chk += vv[r];
+            if (erow) ma = max_abs(ma, vv[r]);
+        }
+    };
+
+    for (int i = ib;;) {
+        plane(Ph<0>{}, i);
+        if (++i > ie) break;
+        plane(Ph<1>{}, i);
+        if (++i > ie) break;
+        plane(Ph<2>{}, i);
+        if (++i > ie) break;
+        plane(Ph<3>{}, i);
+        if (++i > ie) break;
+        plane(Ph<4>{}, i);
+        if (++i > ie) break;
+        plane(Ph<5>{}, i);
+        if (++i > ie) break;
+        if constexpr (NS > 6) {
+            plane(Ph<6>{}, i);
+            if (++i > ie) break;
+            plane(Ph<7>{}, i);
+            if (++i > ie) break;
+            plane(Ph<8>{}, i);
+            if (++i > ie) break;
+            plane(Ph<9>{}, i);
+            if (++i > ie) break;
+        }
+    }
+    commit_errors(ma, T(kErrInit), chk, p.err);
+}
+
+// rows per lane of the k_march_mh instantiations (`make resources`: no scratch in any of them)
+template <class T, int M, int MODE>
+constexpr int mh_rows() {
+    return 4;
+}
+
+template <class T, int M>
+void (*march_mh_kernel(bool first, bool taper, int mode))(const MediumParamsH<T>) {
+    if (mode == kSave)
+        return taper ? k_march_mh<T, M, false, mh_rows<T, M, kSave>(), true, kSave>
+                     : k_march_mh<T, M, false, mh_rows<T, M, kSave>(), false, kSave>;
+    if (mode == kImage)
+        return taper ? k_march_mh<T, M, false, mh_rows<T, M, kImage>(), true, kImage>
+                     : k_march_mh<T, M, false, mh_rows<T, M, kImage>(), false, kImage>;
+    constexpr int RP = mh_rows<T, M, kPlain>();
+    if (first) return taper ? k_march_mh<T, M, true, RP, true> : k_march_mh<T, M, true, RP, false>;
+    return taper ? k_march_mh<T, M, false, RP, true> : k_march_mh<T, M, false, RP, false>;
+}
+
+template <class T, int M>
+int march_mh_rows(int mode) {
+    return mode == kSave ? mh_rows<T, M, kSave>() : mode == kImage ? mh_rows<T, M, kImage>() : mh_rows<T, M, kPlain>();
+}
+
 struct NodeGrid {
     i64 si;
     int sj;
@@ -369,11 +704,18 @@ int medium_variant() {
     return v;
 }
 
+double medium_weight(int order, int d) {
+    W3D_REQUIRE((order == 2 || order == 4 || order == 8) && d >= 0 && d <= order / 2, "no such stencil weight");
+    return star_weight(order / 2, d);
+}
+
 template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant, const T* gx,
-                        const T* gy, const T* gz, T* lap_out, const T* q, T* acc) {
+                        const T* gy, const T* gz, T* lap_out, const T* q, T* acc, int order, const int* mirror) {
+    W3D_REQUIRE(order == 2 || order == 4 || order == 8, "space order must be 2, 4 or 8, not " + std::to_string(order));
+    const int M = order / 2;
     const bool taper = gx || gy || gz;
     W3D_REQUIRE(!taper || (gx && gy && gz), "the sponge needs all three tables");
     W3D_REQUIRE(!taper || gv.G == 1, "sponge tables: one ghost layer");
@@ -386,8 +728,28 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     W3D_REQUIRE(!image || (q && acc), "image mode needs both q and acc");
     W3D_REQUIRE(!(save && image), "save mode (lap_out) and image mode (q, acc) cannot be combined");
     W3D_REQUIRE(!(save || image) || !first, "save / image modes: not on the Taylor start (first)");
-    W3D_REQUIRE(!(save || image) || variant == 1,
+    W3D_REQUIRE(!(save || image) || variant == 1 || M > 1,
                 "save / image modes are instantiated for the default variant only (nt, 4 rows per lane)");
+    const int mode = save ? kSave : image ? kImage : kPlain;
+    // reflecting faces of k_march_mh: (j_lo, j_hi, k_lo, k_hi), +-2^29 where there is none
+    int mir[4] = {kNoMirror, -kNoMirror, kNoMirror, -kNoMirror};
+    bool has[4] = {false, false, false, false};
+    if (M > 1) {
+        W3D_REQUIRE(gv.G == 1 && gv.poff == 0, "orders 4 and 8: one ghost layer in the grid view");
+        for (int f = 0; f < 4; ++f) {
+            if (!mirror || mirror[f] == kNoMirror) continue;
+            const int top = f < 2 ? gv.jmax() : gv.kmax();
+            W3D_REQUIRE(mirror[f] >= 0 && mirror[f] <= top, "mirror face outside the storage");
+            // the farthest reflected index, M - 1 nodes inside the face, must exist
+            W3D_REQUIRE((f & 1) ? mirror[f] - (M - 1) >= 0 : mirror[f] + (M - 1) <= top,
+                        "a node reflected at a mirror face would leave the storage");
+            mir[f] = mirror[f];
+            has[f] = true;
+        }
+        for (int a = 0; a < 2; ++a)
+            W3D_REQUIRE(!(has[2 * a] && has[2 * a + 1]) || mir[2 * a + 1] - mir[2 * a] >= M,
+                        "mirror faces nearer than the stencil's half-width");
+    }
     MediumParams<T> p{};
     p.xcd = xcd_swizzle_enabled();
     p.u1 = u1;
@@ -418,7 +780,10 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     p.lap_out = lap_out;
     p.q = q;
     p.acc = acc;
-    const int tj_rows = kWaves * ((variant & 2) ? 2 : 4);
+    const int tj_rows = kWaves * (M == 2   ? march_mh_rows<T, 2>(mode)
+                                  : M == 4 ? march_mh_rows<T, 4>(mode)
+                                  : (variant & 2) ? 2
+                                                  : 4);
     int btiles[kMaxBoxes], bplanes[kMaxBoxes], nbt = 0;
     for (int q = 0; q < nbox; ++q) {
         const Box& bx = boxes[q];
@@ -434,6 +799,18 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
         if (bx.empty()) continue;
         W3D_REQUIRE(bx.i0 >= 1 && bx.i1 <= gv.X && bx.j0 >= 1 && bx.j1 <= gv.Y && bx.k0 >= 1 && bx.k1 <= gv.Z,
                     "step box outside the owned region");
+        if (M > 1) {
+            W3D_REQUIRE(bx.i0 >= M && bx.i1 <= gv.X + 1 - M, "step box nearer than order / 2 to the storage edge in x");
+            const int lo[2] = {bx.j0, bx.k0}, hi[2] = {bx.j1, bx.k1}, top[2] = {gv.jmax(), gv.kmax()};
+            for (int a = 0; a < 2; ++a) {
+                W3D_REQUIRE(has[2 * a] ? lo[a] > mir[2 * a] : lo[a] >= M,
+                            has[2 * a] ? "step box not strictly inside its mirror faces"
+                                       : "step box nearer than order / 2 to an unmirrored storage edge");
+                W3D_REQUIRE(has[2 * a + 1] ? hi[a] < mir[2 * a + 1] : hi[a] <= top[a] - M,
+                            has[2 * a + 1] ? "step box not strictly inside its mirror faces"
+                                           : "step box nearer than order / 2 to an unmirrored storage edge");
+            }
+        }
         BoxLaunch& L = p.box[nb];
         L.i0 = bx.i0, L.i1 = bx.i1, L.j0 = bx.j0, L.j1 = bx.j1, L.k0 = bx.k0, L.k1 = bx.k1;
         const int t0 = (bx.k0 - 1) / kTK, t1 = (bx.k1 - 1) / kTK;
@@ -450,6 +827,15 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     }
     p.nbox = nb;
     if (nb == 0) return;
+    if (M > 1) {
+        MediumParamsH<T> ph{};
+        static_cast<MediumParams<T>&>(ph) = p;
+        ph.mj0 = mir[0], ph.mj1 = mir[1], ph.mk0 = mir[2], ph.mk1 = mir[3];
+        auto kh = M == 2 ? march_mh_kernel<T, 2>(first, taper, mode) : march_mh_kernel<T, 4>(first, taper, mode);
+        hipLaunchKernelGGL(kh, dim3(total), dim3(kThreads), 0, s, ph);
+        HIP_OK(hipGetLastError());
+        return;
+    }
     void (*kern)(const MediumParams<T>) =
         taper ? (first ? march_m_kernel<T, true, true>(variant) : march_m_kernel<T, false, true>(variant))
               : (first ? march_m_kernel<T, true, false>(variant) : march_m_kernel<T, false, false>(variant));
@@ -478,7 +864,7 @@ void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int
     template void launch_step_medium<T>(bool, const T*, const T*, const T*, T*, const GridView&,       \
                                         const Box*, int, int, int, const Wrap&, const double[3], u64*, \
                                         int, hipStream_t, int, const T*, const T*, const T*, T*,       \
-                                        const T*, T*);                                                 \
+                                        const T*, T*, int, const int*);                                \
     template void launch_inject<T>(T*, const T*, const GridView&, const int*, const T*, int,           \
                                    const Wrap&, hipStream_t);                                          \
     template void launch_record<T>(const T*, const GridView&, const int*, T*, int, hipStream_t);

@@ -28,12 +28,32 @@ namespace wave3d {
 // acc = acc + u1 * q at the box nodes, the product rounded before the add. lap_out, q and acc
 // have the strides of u; nothing outside the boxes is written and the wrap applies to u alone.
 // u and err are those of the plain step bit for bit. Per node in fp64: 40 B (save), 56 B (image).
+//
+// Space order (order = 2, 4 or 8; half-width M = order / 2). Order 2 is the 7-point kernel above
+// and ignores `mirror`. Orders 4 and 8 run k_march_mh, a star stencil of 2M + 1 points per axis with
+// the central second-derivative weights c_0 .. c_M (medium_weight): per axis t = c_0 v, then
+// t = t + c_d (p_-d + p_+d) for d = 1 .. M, and lap = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2,
+// every operation rounded on its own, the divisions correctly rounded; the updates, the sponge and
+// the save / image modes are those above (any variant is accepted and ignored). The x neighbours
+// come from storage: the boxes keep M planes from both ends of the storage. mirror = (j_lo, j_hi,
+// k_lo, k_hi), storage indices of reflecting (Dirichlet) faces, kNoMirror = none on that side
+// (nullptr: none at all): a neighbour beyond a face f is read as -u1[2 f - j], the face itself as
+// stored; the boxes lie strictly inside the faces, a pair of faces is at least M apart, and on a
+// side without a face the boxes keep M nodes from the storage edge. Every violation is rejected
+// before the launch, so no address outside a level's plane is formed.
+constexpr int kNoMirror = -(1 << 29);
 template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant = -1,
                         const T* gx = nullptr, const T* gy = nullptr, const T* gz = nullptr,
-                        T* lap_out = nullptr, const T* q = nullptr, T* acc = nullptr);
+                        T* lap_out = nullptr, const T* q = nullptr, T* acc = nullptr, int order = 2,
+                        const int* mirror = nullptr);
+
+// Central second-derivative weight c_d of the star stencil of `order` (2, 4, 8), d = 0 .. order / 2:
+// the double quotient of its two integers (order 4: -5/2, 4/3, -1/12; order 8: -205/72, 8/5, -1/5,
+// 8/315, -1/560); the kernels cast it to the working type.
+double medium_weight(int order, int d);
 
 // Point sources: u(node[e]) += m(node[e]) * g[e] for e < n (the product rounded, then the add);
 // an entry on a wrap source plane is also copied to its ghost plane. nodes = n x (i, j, k),

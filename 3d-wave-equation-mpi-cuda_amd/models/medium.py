@@ -15,20 +15,41 @@ from typing import Any
 
 import torch
 
-from .wave import CFL_LIMIT, PI_REF
+from .wave import PI_REF
 
 _DTYPES = {"fp64": torch.float64, "fp32": torch.float32}
+_ORDERS = (2, 4, 8)
+
+
+def cfl_limit(order: int = 2) -> float:
+    """Largest stable Courant number ``c_max tau / h_min`` of the leapfrog with the star Laplacian
+    of space ``order`` (2, 4 or 8): ``2 / sqrt(3 S)`` with ``S = |c_0| + 2 sum |c_d|`` over the
+    stencil weights: 1/sqrt(3) = 0.5774 (order 2), 0.5 (4), 0.4529 (8)."""
+    from ..ops import reference
+
+    return reference.cfl_limit(order)
 
 
 class MediumProblem:
-    """N intervals per axis, ``speed2`` = c^2 as a float or an ``(N+1)^3`` array/tensor."""
+    """N intervals per axis, ``speed2`` = c^2 as a float or an ``(N+1)^3`` array/tensor.
+
+    ``space_order``: 2 (the 7-point Laplacian, the default), 4 or 8 (star stencils of half-width
+    M = order / 2 with odd reflection at the Dirichlet faces; needs N >= 2 M). The stability limit
+    of the Courant number depends on it (:func:`cfl_limit`)."""
 
     def __init__(self, N: int, speed2, Lx: Any = "pi", Ly: Any = "pi", Lz: Any = "pi", T: float = 1.0,
-                 timesteps: int = 20, dtype: str = "fp64", pi: str = "ref", strict_cfl: bool = True):
+                 timesteps: int = 20, dtype: str = "fp64", pi: str = "ref", strict_cfl: bool = True,
+                 space_order: int = 2):
         if dtype not in _DTYPES:
             raise ValueError(f"dtype must be fp64 or fp32, not {dtype!r}")
         if N < 2 or timesteps < 1:
             raise ValueError(f"need N >= 2 and timesteps >= 1, not N={N} timesteps={timesteps}")
+        if space_order not in _ORDERS:
+            raise ValueError(f"space_order must be 2, 4 or 8, not {space_order!r}")
+        if N < space_order:
+            raise ValueError(f"space_order {space_order} needs N >= {space_order}, not N={N}")
+        self.space_order = int(space_order)
+        self.cfl_limit = cfl_limit(self.space_order)
         self.N, self.Lx, self.Ly, self.Lz = int(N), Lx, Ly, Lz
         self.T, self.timesteps, self.dtype, self.pi = float(T), int(timesteps), dtype, pi
         s = torch.as_tensor(speed2, dtype=torch.float64).cpu()
@@ -45,8 +66,9 @@ class MediumProblem:
                              f"speed2[{self.N},{j},{k}] = {s[self.N, j, k].item()}")
         self.speed2 = s
         self.max_speed2 = float(s.max())
-        if self.courant > CFL_LIMIT:
-            msg = (f"Courant number {self.courant:.4g} exceeds the stability limit {CFL_LIMIT:.4g}: "
+        if self.courant > self.cfl_limit:
+            msg = (f"Courant number {self.courant:.4g} exceeds the stability limit {self.cfl_limit:.4g} of space "
+                   f"order {self.space_order}: "
                    f"needs timesteps >= {self.min_stable_timesteps()}")
             if strict_cfl:
                 raise ValueError(msg)
@@ -68,10 +90,14 @@ class MediumProblem:
         return math.sqrt(self.max_speed2) * self.tau / (min(self.lengths()) / self.N)
 
     def stable(self) -> bool:
-        return self.courant <= CFL_LIMIT
+        return self.courant <= self.cfl_limit
 
     def min_stable_timesteps(self) -> int:
-        return math.ceil(math.sqrt(self.max_speed2) * self.T * self.N / (min(self.lengths()) * CFL_LIMIT))
+        k = math.ceil(math.sqrt(self.max_speed2) * self.T * self.N / (min(self.lengths()) * self.cfl_limit))
+        # the quotient may round down onto the limit while the Courant number rounds up past it
+        while math.sqrt(self.max_speed2) * (self.T / k) / (min(self.lengths()) / self.N) > self.cfl_limit:
+            k += 1
+        return k
 
     @property
     def points(self) -> int:
@@ -212,6 +238,19 @@ class MediumSolver:
             raise ValueError(f"taper gx must be periodic in x: gx[0] = {gx[0].item()} but gx[{N}] = {gx[N].item()}")
         return tuple(out)
 
+    def _layout(self):
+        """Storage of the "hip" levels for the problem's space order: (x ghost depth M = order / 2
+        with local i = global + M, the step box, the 2M periodic wrap pairs, the order / mirror
+        keywords of ``kernels.step_medium``)."""
+        N, order = self.problem.N, self.problem.space_order
+        M = order // 2
+        box = (M, N + M, 1, N - 1, 1, N - 1)
+        wrap = []
+        for g in range(1, M + 1):  # ghost -g <- global N - g, ghost N + g <- global g
+            wrap += [N + M - g, M - g, M + g, N + M + g]
+        kw = {} if order == 2 else dict(order=order, mirror=(0, N, 0, N))
+        return M, box, tuple(wrap), kw
+
     def run(self) -> MediumResult:
         return self._run_cpu() if self.backend == "cpu" else self._run_hip()
 
@@ -231,8 +270,8 @@ class MediumSolver:
         tr, uf, mx = reference.solve_medium(p.N, p.timesteps, p.speed2, u0=self.u0, sources=self.sources,
                                             wavelet=self.wavelet, receivers=self.receivers,
                                             L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
-                                            taper=self.taper)
-        return self._result(tr, uf, mx, (time.perf_counter() - t0) * 1e3)
+                                            taper=self.taper, order=p.space_order)
+        return self._result(tr, uf, mx, (time.perf_counter() - t0) * 1e3, extra=dict(space_order=p.space_order))
 
     def _run_hip(self) -> MediumResult:
         from ..ops import kernels, reference
@@ -244,27 +283,25 @@ class MediumSolver:
         dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else self.device)
         c = reference.tables(N, K, (p.Lx, p.Ly, p.Lz), p.T, p.pi)[4]
         h2 = (c["hx2"], c["hy2"], c["hz2"])
+        M, box, wrap, step_kw = self._layout()
         with torch.cuda.device(dev):
-            lv = [kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(3)]
-            m = kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev)
-            m.copy_(reference.medium_coefficient(p.speed2, c["tau"], N, dt))
+            lv = [kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev) for _ in range(3)]
+            m = kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev)
+            m.copy_(reference.medium_coefficient(p.speed2, c["tau"], N, dt, M))
             taper = None
             if self.taper is not None:
-                taper = tuple(t.to(dev) for t in reference.taper_tables(self.taper, N, dt))
+                taper = tuple(t.to(dev) for t in reference.taper_tables(self.taper, N, dt, M))
             if self.u0 is not None:
-                lv[0][1:N + 2] = self.u0.to(dt).to(dev)
-                lv[0][0] = lv[0][N]
-                lv[0][N + 2] = lv[0][2]
-            ent = reference.source_entries(self.sources, N)
+                lv[0][M:N + 1 + M] = self.u0.to(dt).to(dev)
+                reference._wrap_x(lv[0], N, M)
+            ent = reference.source_entries(self.sources, N, M)
             g = reference.source_table(self.wavelet, K, len(self.sources), c["hx"], c["hy"], c["hz"], dt)
             g = g[:, [s for _, s in ent]].contiguous().to(dev)  # one column per storage node
             src = kernels.source_nodes([nd for nd, _ in ent], lv[0])
-            rec = kernels.receiver_nodes([(i + 1, j, k) for i, j, k in self.receivers], lv[0])
+            rec = kernels.receiver_nodes([(i + M, j, k) for i, j, k in self.receivers], lv[0])
             traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
-            box = (1, N + 1, 1, N - 1, 1, N - 1)
-            wrap = (N, 0, 2, N + 2)
-            mx0 = reference.max_abs_field(lv[0][1:N + 2, 1:N, 1:N])
+            mx0 = reference.max_abs_field(lv[0][M:N + 1 + M, 1:N, 1:N])
             kernels.record(lv[0], rec, traces[0])
             abort = {}
             done = K
@@ -278,7 +315,7 @@ class MediumSolver:
                     u[:, :, 0] = 0
                     u[:, :, N] = 0
                 kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=stat[3 * n:3 * n + 3],
-                                    stat_i=(1, N + 1), wrap=wrap, variant=self.variant, taper=taper)
+                                    stat_i=(M, N + M), wrap=wrap, variant=self.variant, taper=taper, **step_kw)
                 kernels.inject(u, m, src, g[n - 1], wrap)
                 kernels.record(u, rec, traces[n])
                 if self.check_every > 0 and n % self.check_every == 0:
@@ -293,10 +330,10 @@ class MediumSolver:
             ms = ev0.elapsed_time(ev1)
             dec = kernels.decode_err(stat)  # the one read-back of the statistics
             mx = [mx0] + [dec[n][0] for n in range(1, done + 1)]
-            extra = {}
+            extra = dict(space_order=p.space_order)
             if not abort and any(d[2] for d in dec[1:]):  # ran to the end, but not on finite values
                 extra["nonfinite_layer"] = next(n for n in range(1, K + 1) if dec[n][2])
-            uf = lv[done % 3][1:N + 2].cpu()
+            uf = lv[done % 3][M:N + 1 + M].cpu()
             return self._result(traces.cpu(), uf, mx, ms, extra=extra, **abort)
 
     # ---- misfit gradients (adjoint state; ops/reference.py has the mathematics) ------------
@@ -341,10 +378,10 @@ class MediumSolver:
         J, gs, gw, tr = reference.gradient_medium(p.N, p.timesteps, p.speed2, obs, sources=self.sources,
                                                   wavelet=self.wavelet, receivers=self.receivers,
                                                   taper=self.taper, L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi,
-                                                  dtype=p.torch_dtype)
+                                                  dtype=p.torch_dtype, order=p.space_order)
         return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr,
                               total_ms=(time.perf_counter() - t0) * 1e3,
-                              extra=dict(segment=None, levels=None, recomputed_steps=0))
+                              extra=dict(segment=None, levels=None, recomputed_steps=0, space_order=p.space_order))
 
     def _gradient_hip(self, obs, segment) -> "MediumGradient":
         import time
@@ -358,8 +395,9 @@ class MediumSolver:
         dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else self.device)
         c = reference.tables(N, K, (p.Lx, p.Ly, p.Lz), p.T, p.pi)[4]
         h2 = (c["hx2"], c["hy2"], c["hz2"])
+        M, box, wrap, step_kw = self._layout()
         with torch.cuda.device(dev):
-            level_bytes = kernels.level_bytes(N + 3, N + 1, N + 1, dt)
+            level_bytes = kernels.level_bytes(N + 1 + 2 * M, N + 1, N + 1, dt)
             free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
             if segment is None:
                 segment = best_gradient_segment(K)
@@ -377,32 +415,31 @@ class MediumSolver:
             t0 = time.perf_counter()
 
             def level():
-                return kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev)
+                return kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev)
 
             lv = [level() for _ in range(3)]
             ad = [level() for _ in range(3)] if len(segs) > 1 else lv  # the adjoint's ring
             m, acc = level(), level()
             qb = [level() for _ in range(qlen)]
             ck = [(level(), level()) for _ in segs[:-1]]
-            mc = reference.medium_coefficient(p.speed2, c["tau"], N, dt)
+            mc = reference.medium_coefficient(p.speed2, c["tau"], N, dt, M)
             m.copy_(mc)
-            tt = None if self.taper is None else reference.taper_tables(self.taper, N, dt)
+            tt = None if self.taper is None else reference.taper_tables(self.taper, N, dt, M)
             taper = None if tt is None else tuple(t.to(dev) for t in tt)
-            ent = reference.source_entries(self.sources, N)
+            ent = reference.source_entries(self.sources, N, M)
             gsrc = reference.source_table(self.wavelet, K, len(self.sources), c["hx"], c["hy"], c["hz"], dt)
             g = gsrc[:, [s for _, s in ent]].contiguous().to(dev)
             src = kernels.source_nodes([nd for nd, _ in ent], lv[0])
-            rec = kernels.receiver_nodes([(i + 1, j, k) for i, j, k in self.receivers], lv[0])
+            rec = kernels.receiver_nodes([(i + M, j, k) for i, j, k in self.receivers], lv[0])
             traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
             scratch = kernels.new_err(1, device=dev)  # statistics of the recomputed steps (those of `stat` again)
-            box = (1, N + 1, 1, N - 1, 1, N - 1)
-            wrap = (N, 0, 2, N + 2)
 
             def forward_step(n, slot, save):
                 u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
-                kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=slot, stat_i=(1, N + 1), wrap=wrap,
-                                    variant=None if save is not None else self.variant, taper=taper, lap_out=save)
+                kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=slot, stat_i=(M, N + M), wrap=wrap,
+                                    variant=None if save is not None else self.variant, taper=taper, lap_out=save,
+                                    **step_kw)
                 kernels.inject(u, m, src, g[n - 1], wrap)
 
             def check(st, name):
@@ -429,10 +466,10 @@ class MediumSolver:
             check(stat, "forward")
             tr = traces.cpu()
             J, res = reference.misfit_medium(tr, obs)
-            anodes, atab = reference.adjoint_source_table(res, self.receivers, N, tt)
+            anodes, atab = reference.adjoint_source_table(res, self.receivers, N, tt, M)
             adj = kernels.source_nodes(anodes, lv[0])
             ag = atab.to(dev)
-            snodes = kernels.receiver_nodes(reference.source_unique_nodes(self.sources, N), lv[0])
+            snodes = kernels.receiver_nodes(reference.source_unique_nodes(self.sources, N, M), lv[0])
             a_dev = torch.zeros(K, len(snodes), dtype=dt, device=dev)
             astat = kernels.new_err(K + 1, device=dev)
 
@@ -454,17 +491,19 @@ class MediumSolver:
                 for n in range(b - 1, a - 2, -1):  # q^n is what forward step n + 1 saved
                     u1, u2, u = ad[(n + 1) % 3], ad[(n + 2) % 3], ad[n % 3]
                     kernels.step_medium(u1, u2, m, u, box, first=False, h2=h2, stat=astat[3 * n:3 * n + 3],
-                                        stat_i=(1, N + 1), wrap=wrap, taper=taper, image=(qb[n + 1 - a], acc))
+                                        stat_i=(M, N + M), wrap=wrap, taper=taper, image=(qb[n + 1 - a], acc),
+                                        **step_kw)
                     kernels.inject(u, m, adj, ag[n], wrap)
                     kernels.record(u, snodes, a_dev[n - 1])
             ev[3].record()
             check(astat, "adjoint")
             gs, gw = reference.finish_gradient_medium(acc.cpu(), a_dev.cpu(), gsrc, mc, tt, self.sources, N, c["tau"],
-                                                      c["hx"], c["hy"], c["hz"])
+                                                      c["hx"], c["hy"], c["hz"], M)
             torch.cuda.synchronize(dev)
             ms = (time.perf_counter() - t0) * 1e3
             return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr, total_ms=ms,
                                   extra=dict(segment=segment, levels=nlev, recomputed_steps=recomputed,
+                                             space_order=p.space_order,
                                              forward_ms=ev[0].elapsed_time(ev[1]), reverse_ms=ev[2].elapsed_time(ev[3])))
 
 

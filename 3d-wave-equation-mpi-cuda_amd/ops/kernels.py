@@ -354,7 +354,8 @@ def _check_taper(taper, u) -> list[int]:
 
 
 def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None, chunk: int = 0,
-                variant: str | None = None, taper=None, lap_out=None, image=None) -> None:
+                variant: str | None = None, taper=None, lap_out=None, image=None, order: int = 2,
+                mirror=None) -> None:
     """One layer of ``u_tt = c^2 (lap u + f)`` over ``boxes``: ``u = (2 u1 - u2) + m lap(u1)``, on
     the Taylor start (``first``) ``u = u1 + (0.5 m) lap(u1)``, with ``m = c^2 tau^2`` per node.
 
@@ -376,7 +377,22 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     nodes, the product rounded before the add. These grids match ``u`` in shape, dtype, device and
     strides; nothing outside the boxes is written and the wrap applies to ``u`` alone. Both modes
     exist for leapfrog steps (``first=False``) of the default variant only and cannot be combined.
+
+    ``order`` = 2 (the 7-point Laplacian: the kernels above, ``mirror`` is not used), 4 or 8: the star
+    stencil of half-width M = order / 2 (``k_march_mh``; ``ops.reference.laplace_star`` has the
+    scheme), every mode and the sponge as above; ``variant`` must then be None. The box and mirror
+    contract, checked here before any launch (``ValueError``): the boxes keep M planes from both
+    ends of the storage in x, whose neighbours always come from storage. ``mirror = (j_lo, j_hi,
+    k_lo, k_hi)`` names the storage indices of reflecting (Dirichlet) faces in y and z, an entry or
+    the whole tuple may be None: a neighbour beyond a face f is read as ``-u1[2 f - j]``, the face
+    itself as stored. The boxes lie strictly inside their faces, a pair of faces is at least M
+    apart, every reflected node exists in storage, and on a side without a face the boxes keep M
+    nodes from the storage edge.
     """
+    if order not in (2, 4, 8):
+        raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
+    if order != 2 and variant is not None:
+        raise ValueError("the ablation variants exist for order 2 only")
     extra = []
     if lap_out is not None or image is not None:
         if lap_out is not None and image is not None:
@@ -385,7 +401,8 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
             raise ValueError("save / image modes: not on the Taylor start (first=True)")
         if variant not in (None, "nt"):
             raise ValueError(f"save / image modes exist for the default variant only, not {variant!r}")
-        variant = "nt"
+        if order == 2:
+            variant = "nt"
         if image is not None:
             if len(image) != 2:
                 raise ValueError("image = (q, acc)")
@@ -400,6 +417,13 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     if not 1 <= len(boxes) <= 7:
         raise ValueError("1..7 boxes per launch")
     bl = [_check_box(b, gv) for b in boxes]
+    mir = []
+    if order != 2:
+        from .reference import _check_star_box
+
+        no = _C().no_mirror
+        for b in bl:
+            mir = [no if f is None else int(f) for f in _check_star_box(gv[:3], b, order // 2, mirror)]
     if len(h2) != 3 or not all(float(v) > 0 for v in h2):
         raise ValueError("h2 = (hx2, hy2, hz2), all > 0")
     if stat.dtype != torch.int64 or stat.numel() < 3 or not stat.is_cuda or not stat.is_contiguous():
@@ -412,7 +436,7 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     fn(bool(first), u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, bl, int(stat_i[0]),
        int(stat_i[1]), w, [float(v) for v in h2], stat.data_ptr(), int(chunk), _stream(),
        _MEDIUM_VARIANTS[variant], *gp, lap_out.data_ptr() if lap_out is not None else 0,
-       *((image[0].data_ptr(), image[1].data_ptr()) if image is not None else (0, 0)))
+       *((image[0].data_ptr(), image[1].data_ptr()) if image is not None else (0, 0)), int(order), mir)
 
 
 def inject(u, m, nodes, g, wrap=None) -> None:

@@ -179,15 +179,121 @@ def chained_layers(A, B, nlayers: int, *, first: bool, mask, hx2, hy2, hz2, coef
 
 # ---- heterogeneous medium: u_tt = c^2 (lap u + f) -----------------------------------------
 
-def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None) -> torch.Tensor:
+STAR_WEIGHTS = {
+    2: ((-2, 1), (1, 1)),
+    4: ((-5, 2), (4, 3), (-1, 12)),
+    8: ((-205, 72), (8, 5), (-1, 5), (8, 315), (-1, 560)),
+}
+
+
+def star_weights(order: int) -> list[float]:
+    """Central second-derivative weights c_0 .. c_M of the star stencil of ``order`` (2, 4, 8;
+    M = order / 2): each the Python float quotient of its two integers."""
+    if order not in STAR_WEIGHTS:
+        raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
+    return [a / b for a, b in STAR_WEIGHTS[order]]
+
+
+def cfl_limit(order: int = 2) -> float:
+    """Largest stable Courant number ``c tau / h_min`` of the leapfrog with the star Laplacian of
+    ``order``: ``2 / sqrt(3 S)``, ``S = |c_0| + 2 sum |c_d|`` (order 2: 1/sqrt(3), 4: 0.5, 8: 0.4528...)."""
+    w = star_weights(order)
+    if order == 2:
+        return 1.0 / math.sqrt(3.0)  # the constant-speed solver's CFL_LIMIT, bit for bit
+    return 2.0 / math.sqrt(3.0 * (abs(w[0]) + 2.0 * sum(abs(v) for v in w[1:])))
+
+
+def _check_star_box(shape, box, M: int, mirror) -> tuple:
+    """The box and mirror contract of the high-order step (the same checks as the HIP launcher);
+    returns the mirror as a 4-tuple."""
+    mirror = (None,) * 4 if mirror is None else tuple(mirror)
+    if len(mirror) != 4:
+        raise ValueError("mirror = (j_lo, j_hi, k_lo, k_hi), an entry may be None")
+    nx, ny, nz = shape
+    i0, i1, j0, j1, k0, k1 = box
+    if not (M <= i0 and i1 <= nx - 1 - M):
+        raise ValueError(f"box {tuple(box)} nearer than {M} to the storage edge in x ({nx} planes)")
+    for name, lo, hi, n, f_lo, f_hi in (("y", j0, j1, ny, mirror[0], mirror[1]), ("z", k0, k1, nz, mirror[2], mirror[3])):
+        for f, inside in ((f_lo, lambda f: f + (M - 1) <= n - 1), (f_hi, lambda f: f - (M - 1) >= 0)):
+            if f is not None and not (0 <= f <= n - 1 and inside(f)):
+                raise ValueError(f"mirror face {f} in {name}: outside the storage of {n} nodes, or a reflected "
+                                 f"node would leave it")
+        if f_lo is not None and f_hi is not None and f_hi - f_lo < M:
+            raise ValueError(f"mirror faces {f_lo}, {f_hi} in {name} are nearer than {M}")
+        if not (lo > f_lo if f_lo is not None else lo >= M) or not (hi < f_hi if f_hi is not None else hi <= n - 1 - M):
+            raise ValueError(f"box {tuple(box)} in {name}: not strictly inside its mirror faces {f_lo}, {f_hi}, or "
+                             f"nearer than {M} to an unmirrored storage edge ({n} nodes)")
+    return mirror
+
+
+def laplace_star(u, box, hx2, hy2, hz2, *, order: int, mirror=None) -> torch.Tensor:
+    """Star Laplacian of ``order`` (half-width M = order / 2) on the nodes of ``box`` (storage
+    indices, inclusive) of the grid ``u``. Per axis, with centre v and neighbours p_-d, p_+d:
+    ``t = c_0 v``, then ``t = t + c_d (p_-d + p_+d)`` for d = 1 .. M, every operation rounded on its
+    own, and ``lap = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2``.
+
+    The x neighbours come from storage (the box keeps M planes from both ends). ``mirror = (j_lo,
+    j_hi, k_lo, k_hi)``: storage indices of reflecting (Dirichlet) faces in y and z, an entry may be
+    None. A neighbour beyond a face f is read as ``-u[2 f - j]`` (odd reflection), the face itself as
+    stored; the box lies strictly inside its faces and a pair of faces is at least M apart. On a
+    side without a face the neighbours come from storage and the box keeps M nodes from its edge."""
+    w = [torch.tensor(v, dtype=u.dtype, device=u.device) for v in star_weights(order)]
+    M = order // 2
+    i0, i1, j0, j1, k0, k1 = (int(v) for v in box)
+    mirror = _check_star_box(u.shape, (i0, i1, j0, j1, k0, k1), M, mirror)
+    si, sj, sk = slice(i0, i1 + 1), slice(j0, j1 + 1), slice(k0, k1 + 1)
+    c = u[si, sj, sk]
+
+    def shifted(axis, lo, hi, off, f_lo, f_hi):
+        idx = torch.arange(lo + off, hi + off + 1, device=u.device)
+        neg = torch.zeros_like(idx, dtype=torch.bool)
+        if f_lo is not None:
+            neg = neg | (idx < f_lo)
+            idx = torch.where(idx < f_lo, 2 * f_lo - idx, idx)
+        if f_hi is not None:
+            neg = neg | (idx > f_hi)
+            idx = torch.where(idx > f_hi, 2 * f_hi - idx, idx)
+        sl = [si, sj, sk]
+        sl[axis] = slice(None)
+        v = u[tuple(sl)].index_select(axis, idx)
+        shape = [1, 1, 1]
+        shape[axis] = -1
+        return torch.where(neg.reshape(shape), -v, v)
+
+    ans = torch.zeros_like(c)
+    for axis, (lo, hi, f_lo, f_hi, h2) in enumerate(((i0, i1, None, None, hx2), (j0, j1, mirror[0], mirror[1], hy2),
+                                                     (k0, k1, mirror[2], mirror[3], hz2))):
+        t = w[0] * c
+        for d in range(1, M + 1):
+            t = t + w[d] * (shifted(axis, lo, hi, -d, f_lo, f_hi) + shifted(axis, lo, hi, d, f_lo, f_hi))
+        ans = ans + t / h2
+    return ans
+
+
+def _lap_box(u1, box, hx2, hy2, hz2, order: int, mirror):
+    """lap(u1) on the nodes of ``box``: order 2 is ``laplace7`` (today's operations), 4 and 8
+    ``laplace_star``."""
+    if order == 2:
+        i0, i1, j0, j1, k0, k1 = box
+        return laplace7(u1, hx2, hy2, hz2)[i0 - 1:i1, j0 - 1:j1, k0 - 1:k1]
+    return laplace_star(u1, box, hx2, hy2, hz2, order=order, mirror=mirror)
+
+
+def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None, order: int = 2,
+                mirror=None) -> torch.Tensor:
     """Layer update on ``box`` with the per-node coefficient ``m = c^2 tau^2``: the Taylor start
     ``c + (0.5 m) lap`` or ``(2c - u2) + m lap``; returns the updated box values.
+
+    order = 2: the 7-point Laplacian (``mirror`` is not used); 4 or 8: ``laplace_star`` with its box
+    and ``mirror`` contract.
 
     taper = (gx, gy, gz), 1-D factors in (0, 1] per axis in storage indexing (the lengths of the
     grid's axes): the damped leapfrog of an absorbing sponge with ``G = gx (gy gz)`` per node,
     ``G (c + (0.5 m) lap)`` or ``G ((2c - G u2) + m lap)``, every operation rounded on its own."""
+    if order not in STAR_WEIGHTS:
+        raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
     i0, i1, j0, j1, k0, k1 = box
-    lap = laplace7(u1, hx2, hy2, hz2)[i0 - 1:i1, j0 - 1:j1, k0 - 1:k1]
+    lap = _lap_box(u1, box, hx2, hy2, hz2, order, mirror)
     c = u1[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
     mb = m[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
     if taper is None:
@@ -211,18 +317,24 @@ def max_abs_field(u: torch.Tensor, init: float = -100.0) -> float:
     return max(torch.where(torch.isnan(a), neg, a).max().item() if a.numel() else -math.inf, init)
 
 
-def medium_coefficient(speed2, tau: float, N: int, dtype) -> torch.Tensor:
-    """m = ((speed2 * tau) * tau), left to right in float64, then cast: ``[N+3][N+1][N+1]`` in
-    ``solve()``'s storage (x ghosts filled periodically)."""
+def _wrap_x(u, N: int, ghost: int = 1) -> None:
+    """Fill the ``ghost`` periodic x planes per side of a level (local i = global + ghost)."""
+    for g in range(1, ghost + 1):
+        u[ghost - g] = u[N + ghost - g]
+        u[N + ghost + g] = u[ghost + g]
+
+
+def medium_coefficient(speed2, tau: float, N: int, dtype, ghost: int = 1) -> torch.Tensor:
+    """m = ((speed2 * tau) * tau), left to right in float64, then cast: ``[N+1+2 ghost][N+1][N+1]``
+    in ``solve()``'s storage with ``ghost`` x ghost planes per side, filled periodically."""
     s = torch.as_tensor(speed2, dtype=torch.float64)
     if s.dim() == 0:
         s = s.expand(N + 1, N + 1, N + 1)
     if tuple(s.shape) != (N + 1, N + 1, N + 1):
         raise ValueError(f"speed2 must be a scalar or have shape {(N + 1,) * 3}, not {tuple(s.shape)}")
-    m = torch.zeros(N + 3, N + 1, N + 1, dtype=dtype)
-    m[1:N + 2] = ((s * tau) * tau).to(dtype)
-    m[0] = m[N]
-    m[N + 2] = m[2]
+    m = torch.zeros(N + 1 + 2 * ghost, N + 1, N + 1, dtype=dtype)
+    m[ghost:N + 1 + ghost] = ((s * tau) * tau).to(dtype)
+    _wrap_x(m, N, ghost)
     return m
 
 
@@ -241,19 +353,19 @@ def source_table(wavelet, K: int, S: int, hx: float, hy: float, hz: float, dtype
     return g.to(dtype)
 
 
-def source_entries(sources, N: int) -> list[tuple[tuple[int, int, int], int]]:
+def source_entries(sources, N: int, ghost: int = 1) -> list[tuple[tuple[int, int, int], int]]:
     """Storage nodes of the sources, ((local i, j, k), column of the source table): local =
-    global + 1 in x; a source on the periodic plane 0 or N acts on both planes."""
+    global + ghost in x; a source on the periodic plane 0 or N acts on both planes."""
     out = []
     for s, (i, j, k) in enumerate(sources):
         for gi in ((0, N) if i in (0, N) else (i,)):
-            out.append(((gi + 1, j, k), s))
+            out.append(((gi + ghost, j, k), s))
     return out
 
 
-def taper_tables(taper, N: int, dtype) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def taper_tables(taper, N: int, dtype, ghost: int = 1) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Sponge factors (gx, gy, gz), each ``N+1`` values in global indexing (an entry may be None:
-    ones), cast to ``dtype`` in ``solve()``'s storage: gx ``[N+3]`` with the x ghosts filled
+    ones), cast to ``dtype`` in ``solve()``'s storage: gx ``[N+1+2 ghost]`` with the x ghosts filled
     periodically like ``medium_coefficient``, gy and gz ``[N+1]``."""
     if len(taper) != 3:
         raise ValueError("taper = (gx, gy, gz)")
@@ -263,18 +375,21 @@ def taper_tables(taper, N: int, dtype) -> tuple[torch.Tensor, torch.Tensor, torc
         if t.dim() != 1 or t.numel() != N + 1:
             raise ValueError(f"taper g{name} must have {N + 1} values, not shape {tuple(t.shape)}")
         out.append(t.to(dtype))
-    gx = torch.empty(N + 3, dtype=dtype)
-    gx[1:N + 2] = out[0]
-    gx[0] = gx[N]
-    gx[N + 2] = gx[2]
+    gx = torch.empty(N + 1 + 2 * ghost, dtype=dtype)
+    gx[ghost:N + 1 + ghost] = out[0]
+    _wrap_x(gx, N, ghost)
     return gx, out[1].contiguous(), out[2].contiguous()
 
 
 def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, receivers=(),
                  L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, device="cpu",
-                 taper=None):
+                 taper=None, order: int = 2):
     """Whole single-domain solve of ``(1/c^2) u_tt = lap u + f`` from rest in PyTorch, in
     ``solve()``'s storage (x ghosts, local = global + 1).
+
+    order: the space order, 2 (the 7-point Laplacian), 4 or 8 (``laplace_star``: the levels then
+    carry order / 2 x ghost planes per side, local = global + order / 2, and the Dirichlet faces
+    reflect oddly); the results keep their shapes.
 
     speed2: c^2, a scalar or ``(N+1)^3``; u0: the initial field (``(N+1)^3``, default 0), used as
     given, face values included; sources / receivers: global (i, j, k) nodes; wavelet ``[K, S]``:
@@ -287,24 +402,24 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
     not tapered in its own step). None: the undamped scheme.
     """
     c = tables(N, K, L, T, pi)[4]
+    M, box, mirror = _medium_layout(N, order)
     if taper is not None:
-        taper = tuple(t.to(device) for t in taper_tables(taper, N, dtype))
-    m = medium_coefficient(speed2, c["tau"], N, dtype).to(device)
-    ent = source_entries(sources, N)
+        taper = tuple(t.to(device) for t in taper_tables(taper, N, dtype, M))
+    m = medium_coefficient(speed2, c["tau"], N, dtype, M).to(device)
+    ent = source_entries(sources, N, M)
     g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype).to(device)
-    lv = [torch.zeros(N + 3, N + 1, N + 1, dtype=dtype, device=device) for _ in range(3)]
+    lv = [torch.zeros(N + 1 + 2 * M, N + 1, N + 1, dtype=dtype, device=device) for _ in range(3)]
 
     def wrap(u):
-        u[0] = u[N]
-        u[N + 2] = u[2]
+        _wrap_x(u, N, M)
 
     if u0 is not None:
         u0 = torch.as_tensor(u0)
         if tuple(u0.shape) != (N + 1, N + 1, N + 1):
             raise ValueError(f"u0 must have shape {(N + 1,) * 3}, not {tuple(u0.shape)}")
-        lv[0][1:N + 2] = u0.to(dtype).to(device)
+        lv[0][M:N + 1 + M] = u0.to(dtype).to(device)
         wrap(lv[0])
-    rec = [(i + 1, j, k) for i, j, k in receivers]
+    rec = [(i + M, j, k) for i, j, k in receivers]
     traces = torch.zeros(K + 1, len(rec), dtype=dtype, device=device)
 
     def sample(n, u):
@@ -312,19 +427,19 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
             traces[n, r] = u[nd]
 
     sample(0, lv[0])
-    box = (1, N + 1, 1, N - 1, 1, N - 1)
-    mx = [max_abs_field(lv[0][1:N + 2, 1:N, 1:N])]
+    mx = [max_abs_field(lv[0][M:N + 1 + M, 1:N, 1:N])]
     for n in range(1, K + 1):
         u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
         u.zero_()
-        vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=taper)
+        vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=taper,
+                           order=order, mirror=mirror)
         mx.append(max_abs_field(vals))
-        u[1:N + 2, 1:N, 1:N] = vals
+        u[M:N + 1 + M, 1:N, 1:N] = vals
         for nd, s in ent:
             u[nd] = u[nd] + m[nd] * g[n - 1, s]
         wrap(u)
         sample(n, u)
-    return traces, lv[K % 3][1:N + 2].clone(), mx
+    return traces, lv[K % 3][M:N + 1 + M].clone(), mx
 
 
 # ---- misfit gradients of the medium solver (adjoint state) ---------------------------------
@@ -340,13 +455,19 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
 # The helpers below are the host-side arithmetic shared by gradient_medium and the HIP front-end
 # (models/medium.py): both call them on CPU tensors, so they round alike.
 
-def _medium_box(N: int):
-    return (1, N + 1, 1, N - 1, 1, N - 1)
+def _medium_box(N: int, ghost: int = 1):
+    return (ghost, N + ghost, 1, N - 1, 1, N - 1)
 
 
-def _wrap_x(u, N: int) -> None:
-    u[0] = u[N]
-    u[N + 2] = u[2]
+def _medium_layout(N: int, order: int):
+    """(x ghost depth M = order / 2, the step box, the mirror faces or None) of the medium solver's
+    storage for a space order."""
+    if order not in STAR_WEIGHTS:
+        raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
+    M = order // 2
+    if N < 2 * M:
+        raise ValueError(f"space order {order} needs N >= {2 * M}, not N = {N}")
+    return M, _medium_box(N, M), (None if order == 2 else (0, N, 0, N))
 
 
 def taper_at(tt, node):
@@ -360,32 +481,34 @@ def taper_at(tt, node):
 
 def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None, receivers=(), taper=None,
                             L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
-                            keep_lap: bool = False):
+                            keep_lap: bool = False, order: int = 2):
     """``solve_medium`` from rest, restated out of place: every level is a new tensor, so
     ``torch.autograd`` can differentiate the traces with respect to ``speed2`` (an ``(N+1)^3``
     tensor) and ``wavelet``. The operations and their order are those of ``solve_medium``: the traces
     ``[K+1, R]`` are equal bit for bit. ``keep_lap``: also return [q^1 .. q^{K-1}], q^n = lap u^n on
     the stencil nodes (the value step n+1 uses)."""
     c = tables(N, K, L, T, pi)[4]
-    tt = None if taper is None else taper_tables(taper, N, dtype)
-    m = medium_coefficient(speed2, c["tau"], N, dtype)
-    ent = source_entries(sources, N)
+    M, box, mirror = _medium_layout(N, order)
+    shape = (N + 1 + 2 * M, N + 1, N + 1)
+    tt = None if taper is None else taper_tables(taper, N, dtype, M)
+    m = medium_coefficient(speed2, c["tau"], N, dtype, M)
+    ent = source_entries(sources, N, M)
     g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
-    rec = [(i + 1, j, k) for i, j, k in receivers]
-    box = _medium_box(N)
-    u2 = torch.zeros(N + 3, N + 1, N + 1, dtype=dtype)
-    u1 = torch.zeros(N + 3, N + 1, N + 1, dtype=dtype)
+    rec = [(i + M, j, k) for i, j, k in receivers]
+    u2 = torch.zeros(shape, dtype=dtype)
+    u1 = torch.zeros(shape, dtype=dtype)
     rows = [torch.stack([u1[nd] for nd in rec]) if rec else torch.zeros(0, dtype=dtype)]
     laps = []
     for n in range(1, K + 1):
         if keep_lap and n >= 2:
-            laps.append(laplace7(u1, c["hx2"], c["hy2"], c["hz2"])[0:N + 1, 0:N - 1, 0:N - 1])
-        vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt)
-        u = torch.zeros(N + 3, N + 1, N + 1, dtype=dtype)
-        u[1:N + 2, 1:N, 1:N] = vals
+            laps.append(_lap_box(u1, box, c["hx2"], c["hy2"], c["hz2"], order, mirror))
+        vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt,
+                           order=order, mirror=mirror)
+        u = torch.zeros(shape, dtype=dtype)
+        u[M:N + 1 + M, 1:N, 1:N] = vals
         for nd, s in ent:
             u[nd] = u[nd] + m[nd] * g[n - 1, s]
-        _wrap_x(u, N)
+        _wrap_x(u, N, M)
         rows.append(torch.stack([u[nd] for nd in rec]) if rec else torch.zeros(0, dtype=dtype))
         u2, u1 = u1, u
     traces = torch.stack(rows)
@@ -403,13 +526,14 @@ def misfit_medium(traces, observed):
     return (0.5 * (res * res).sum()).item(), res
 
 
-def adjoint_source_table(res, receivers, N: int, tt):
+def adjoint_source_table(res, receivers, N: int, tt, ghost: int = 1):
     """Adjoint sources of the residuals ``res`` ``[K+1, R]``: ([storage nodes], table ``[K+1, E]``).
 
     Receivers that share a unique node (planes 0 and N are one plane) are summed in list order;
     a receiver on a Dirichlet face injects nothing; a node on the periodic plane yields entries on
     both storage planes, like ``source_entries``. Column e of the table is ``G[node] * rho`` rounded
-    in the dtype of ``res`` (``tt`` = the ``taper_tables``, None: G = 1)."""
+    in the dtype of ``res`` (``tt`` = the ``taper_tables``, None: G = 1). ``ghost``: the x ghost depth
+    of the storage (local i = global + ghost)."""
     rho = {}
     for r, (i, j, k) in enumerate(receivers):
         if j in (0, N) or k in (0, N):
@@ -419,29 +543,30 @@ def adjoint_source_table(res, receivers, N: int, tt):
     nodes, cols = [], []
     for (i, j, k), v in rho.items():
         for gi in ((0, N) if i == 0 else (i,)):
-            nd = (gi + 1, j, k)
+            nd = (gi + ghost, j, k)
             nodes.append(nd)
             cols.append(taper_at(tt, nd) * v)
     tab = torch.stack(cols, 1).contiguous() if cols else torch.zeros(res.shape[0], 0, dtype=res.dtype)
     return nodes, tab
 
 
-def source_unique_nodes(sources, N: int):
+def source_unique_nodes(sources, N: int, ghost: int = 1):
     """One storage node per source for sampling the adjoint field: plane N is read on plane 0."""
-    return [((i % N) + 1, j, k) for i, j, k in sources]
+    return [((i % N) + ghost, j, k) for i, j, k in sources]
 
 
-def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: float, hy: float, hz: float):
-    """The host-side end of the gradient. acc ``[N+3][N+1][N+1]`` = sum mu^{n+1} q^n in storage
+def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: float, hy: float, hz: float,
+                           ghost: int = 1):
+    """The host-side end of the gradient. acc ``[N+1+2 ghost][N+1][N+1]`` = sum mu^{n+1} q^n in storage
     (faces 0), a ``[K, S]`` with ``a[n, s] = mu^{n+1}[x_s]``, g = the ``source_table``, m = the
     ``medium_coefficient``, all CPU tensors of the working dtype. Returns (dJ/dspeed2 ``(N+1)^3``
     with respect to the unique nodes: plane N a copy of plane 0, faces 0; dJ/dwavelet ``[K, S]``)."""
-    gm = acc[1:N + 2] / m[1:N + 2]
-    nodes = source_unique_nodes(sources, N)
+    gm = acc[ghost:N + 1 + ghost] / m[ghost:N + 1 + ghost]
+    nodes = source_unique_nodes(sources, N, ghost)
     if nodes:
         dots = (a * g).sum(0)
         for s, nd in enumerate(nodes):
-            at = (nd[0] - 1, nd[1], nd[2])
+            at = (nd[0] - ghost, nd[1], nd[2])
             gm[at] = gm[at] + dots[s] / (m[nd] * taper_at(tt, nd))
     grad = (gm * tau) * tau  # m = (speed2 tau) tau
     grad[N] = grad[0]
@@ -458,7 +583,7 @@ def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: fl
 
 
 def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,
-                    L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64):
+                    L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, order: int = 2):
     """Misfit J of the traces against ``observed`` ``[K+1, R]`` (row 0 ignored) and its gradients by
     the hand-written adjoint above: (J, dJ/dspeed2 ``(N+1)^3``, dJ/dwavelet ``[K, S]``, traces).
 
@@ -467,26 +592,30 @@ def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=Non
     dJ/dspeed2 is taken with respect to the unique nodes: entry [0] is the derivative with respect
     to the shared value of planes 0 and N (autograd's ``g[0] + g[N]`` for an ``(N+1)^3`` leaf) and
     entry [N] a copy of it; for a periodic perturbation d the directional derivative is
-    ``(grad[:N] * d[:N]).sum()``."""
+    ``(grad[:N] * d[:N]).sum()``.
+
+    order: the space order of ``solve_medium``; the star Laplacian with periodic wrap and odd
+    reflection is symmetric on the unique nodes, so the adjoint recurrence keeps its form."""
     with torch.no_grad():
         traces, laps = forward_medium_autograd(N, K, speed2, sources=sources, wavelet=wavelet,
                                                receivers=receivers, taper=taper, L=L, T=T, pi=pi, dtype=dtype,
-                                               keep_lap=True)
+                                               keep_lap=True, order=order)
         J, res = misfit_medium(traces, observed)
         c = tables(N, K, L, T, pi)[4]
-        tt = None if taper is None else taper_tables(taper, N, dtype)
-        m = medium_coefficient(speed2, c["tau"], N, dtype)
+        M, box, mirror = _medium_layout(N, order)
+        tt = None if taper is None else taper_tables(taper, N, dtype, M)
+        m = medium_coefficient(speed2, c["tau"], N, dtype, M)
         g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
-        anodes, atab = adjoint_source_table(res, receivers, N, tt)
-        snodes = source_unique_nodes(sources, N)
-        box = _medium_box(N)
-        shape = (N + 3, N + 1, N + 1)
+        anodes, atab = adjoint_source_table(res, receivers, N, tt, M)
+        snodes = source_unique_nodes(sources, N, M)
+        shape = (N + 1 + 2 * M, N + 1, N + 1)
+        own = (slice(M, N + 1 + M), slice(1, N), slice(1, N))
         a = torch.zeros(K, len(snodes), dtype=dtype)
 
         def finish_level(mu, n):  # inject G rho^n, wrap, sample mu^n at the sources
             for e, nd in enumerate(anodes):
                 mu[nd] = mu[nd] + m[nd] * atab[n, e]
-            _wrap_x(mu, N)
+            _wrap_x(mu, N, M)
             for s, nd in enumerate(snodes):
                 a[n - 1, s] = mu[nd]
 
@@ -495,11 +624,12 @@ def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=Non
         finish_level(mu1, K)
         acc = torch.zeros(shape, dtype=dtype)
         for n in range(K - 1, 0, -1):
-            vals = step_medium(mu1, mu2, m, box, first=False, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt)
-            acc[1:N + 2, 1:N, 1:N] = acc[1:N + 2, 1:N, 1:N] + mu1[1:N + 2, 1:N, 1:N] * laps[n - 1]
+            vals = step_medium(mu1, mu2, m, box, first=False, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt,
+                               order=order, mirror=mirror)
+            acc[own] = acc[own] + mu1[own] * laps[n - 1]
             mu = torch.zeros(shape, dtype=dtype)
-            mu[1:N + 2, 1:N, 1:N] = vals
+            mu[own] = vals
             finish_level(mu, n)
             mu2, mu1 = mu1, mu
-        grad, gw = finish_gradient_medium(acc, a, g, m, tt, sources, N, c["tau"], c["hx"], c["hy"], c["hz"])
+        grad, gw = finish_gradient_medium(acc, a, g, m, tt, sources, N, c["tau"], c["hx"], c["hy"], c["hz"], M)
         return J, grad, gw, traces

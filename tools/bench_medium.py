@@ -3,8 +3,9 @@
 
     python tools/bench_medium.py [--N 512] [--steps 100] [--dtypes fp64,fp32]
                                  [--variants default,plain,r2,r2nt] [--repeat 3] [--no-yardstick]
-                                 [--taper WIDTH]
+                                 [--taper WIDTH] [--order 2,4,8]
     python tools/bench_medium.py --gradient [--N 512] [--steps 100] [--dtypes fp64,fp32] [--segment 10]
+                                 [--order 2,8] [--kernels-only]
 
 For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
 and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
@@ -22,6 +23,13 @@ the image step (+ q, acc read, acc written: 56 B), `--repeat` rounds of 20 launc
 alternating inside each round, with and without a sponge of 16 nodes; then, alternating as well,
 one forward run() and gradient() with every q stored (segment = steps) and with `--segment`: the
 device time of the passes beside run()'s time loop, and the wall time of the whole call.
+
+`--order 2,4,8` runs every configuration at each of the space orders (4 and 8: k_march_mh), the
+orders alternating inside each repeat in the one job, and reports per row the order and the ratio
+of its time to order 2's (`vs_order2`, when 2 is among the orders). The byte count per node does
+not depend on the order; the speed keeps the Courant number at 0.9 of the smallest limit among
+the orders. The ablation variants exist for order 2 only. With `--gradient` the kernel rounds and
+the schedules run at each order; `--kernels-only` skips the schedules.
 """
 import argparse
 import json
@@ -57,85 +65,112 @@ def gradient_bench(a) -> int:
 
     N, K = a.N, a.steps
     h = 3.1415926535 / N
-    hi = (0.9 / math.sqrt(3) * h * K) ** 2
+    orders = [int(v) for v in a.order.split(",")]
+    hi = (0.9 * min(wave3d.cfl_limit(o) for o in orders) * h * K) ** 2
     speed2 = smooth_speed2(N, 0.5 * hi, hi)
     nodes = float(N + 1) ** 3
-    out = {"N": N, "steps": K, "device": torch.cuda.get_device_name(0), "kernels": [], "gradient": []}
+    out = {"N": N, "steps": K, "orders": orders, "device": torch.cuda.get_device_name(0), "kernels": [],
+           "gradient": []}
     dev = torch.device("cuda", 0)
     for dtype in a.dtypes.split(","):
         es = 8 if dtype == "fp64" else 4
-        prob = wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype)
-        dt = prob.torch_dtype
+        probs = {o: wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype, space_order=o) for o in orders}
+        dt = probs[orders[0]].torch_dtype
         c = reference.tables(N, K)[4]
         h2 = (c["hx2"], c["hy2"], c["hz2"])
-        sponge = wave3d.sponge_taper(prob, 16)
+        sponge = wave3d.sponge_taper(probs[orders[0]], 16)
 
-        # the three kernels on one set of levels (values of a short run, so nothing is denormal)
-        lv = [kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(6)]
-        u1, u2, m, u, x, q = lv
-        m.copy_(reference.medium_coefficient(speed2, c["tau"], N, dt))
+        # the three kernels on one set of levels per order (values of a short run, so nothing is denormal)
         g = torch.Generator().manual_seed(1)
         seed = torch.rand(N + 1, N + 1, generator=g, dtype=torch.float64).to(dt).to(dev)
-        for t in (u1, u2, q):
-            t[:, 1:N, 1:N] = seed[1:N, 1:N]
-        box, wrap = (1, N + 1, 1, N - 1, 1, N - 1), (N, 0, 2, N + 2)
+        sets = {}
+        for o in orders:
+            M = o // 2
+            lv = [kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev) for _ in range(6)]
+            lv[2].copy_(reference.medium_coefficient(speed2, c["tau"], N, dt, M))
+            for t in (lv[0], lv[1], lv[5]):
+                t[:, 1:N, 1:N] = seed[1:N, 1:N]
+            wrap = []
+            for gh in range(1, M + 1):
+                wrap += [N + M - gh, M - gh, M + gh, N + M + gh]
+            sets[o] = dict(lv=lv, box=(M, N + M, 1, N - 1, 1, N - 1), wrap=wrap, stat_i=(M, N + M),
+                           kw={} if o == 2 else dict(order=o, mirror=(0, N, 0, N)),
+                           taper=tuple(t.to(dev) for t in reference.taper_tables(sponge, N, dt, M)))
         stat = kernels.new_err(1, device=dev)
         reps = 20
-        for tp_name, tp in (("", None), ("sponge", tuple(t.to(dev) for t in reference.taper_tables(sponge, N, dt)))):
-            modes = {"plain": {}, "save": {"lap_out": x}, "image": {"image": (q, x)}}
-            ms = {k: [] for k in modes}
+        for tp_name in ("", "sponge"):
+            modes = ("plain", "save", "image")
+            ms = {(k, o): [] for k in modes for o in orders}
             for rnd in range(a.repeat + 1):  # round 0 warms up
-                for name, kw in modes.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    x.zero_()
-                    e0.record()
-                    for _ in range(reps):
-                        kernels.step_medium(u1, u2, m, u, box, first=False, h2=h2, stat=stat, stat_i=(1, N + 1),
-                                            wrap=wrap, taper=tp, **kw)
-                    e1.record()
-                    e1.synchronize()
-                    if rnd:
-                        ms[name].append(e0.elapsed_time(e1) / reps)
-            for name, bpn in (("plain", 4), ("save", 5), ("image", 7)):
-                best = min(ms[name])
-                out["kernels"].append({"dtype": dtype, "mode": name, "sponge": bool(tp_name),
-                                       "ms_per_step": round(best, 4), "all_ms": [round(v, 4) for v in ms[name]],
-                                       "bytes_per_node": bpn * es, "expected_ratio": bpn / 4,
-                                       "ratio_to_plain": round(best / min(ms["plain"]), 4),
-                                       "eff_tb_per_s": round(bpn * es * nodes / (best * 1e-3) / 1e12, 3)})
-                print(f"bench_medium: {dtype} {name} {tp_name}: {best:.4f} ms/step", file=sys.stderr, flush=True)
-        del lv, u1, u2, m, u, x, q
+                for name in modes:
+                    for o in orders:  # the orders alternate inside each round
+                        S = sets[o]
+                        u1, u2, m, u, x, q = S["lv"]
+                        kw = {"plain": {}, "save": {"lap_out": x}, "image": {"image": (q, x)}}[name]
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        x.zero_()
+                        e0.record()
+                        for _ in range(reps):
+                            kernels.step_medium(u1, u2, m, u, S["box"], first=False, h2=h2, stat=stat,
+                                                stat_i=S["stat_i"], wrap=S["wrap"],
+                                                taper=S["taper"] if tp_name else None, **kw, **S["kw"])
+                        e1.record()
+                        e1.synchronize()
+                        if rnd:
+                            ms[(name, o)].append(e0.elapsed_time(e1) / reps)
+            for o in orders:
+                for name, bpn in (("plain", 4), ("save", 5), ("image", 7)):
+                    best = min(ms[(name, o)])
+                    row = {"dtype": dtype, "order": o, "mode": name, "sponge": bool(tp_name),
+                           "ms_per_step": round(best, 4), "all_ms": [round(v, 4) for v in ms[(name, o)]],
+                           "bytes_per_node": bpn * es, "expected_ratio": bpn / 4,
+                           "ratio_to_plain": round(best / min(ms[("plain", o)]), 4),
+                           "eff_tb_per_s": round(bpn * es * nodes / (best * 1e-3) / 1e12, 3)}
+                    if 2 in orders:
+                        row["vs_order2"] = round(best / min(ms[(name, 2)]), 4)
+                    out["kernels"].append(row)
+                    print(f"bench_medium: {dtype} order {o} {name} {tp_name}: {best:.4f} ms/step", file=sys.stderr,
+                          flush=True)
+        del sets, lv, u1, u2, m, u, x, q, S
         torch.cuda.empty_cache()
+        if a.kernels_only:
+            continue
 
-        # gradient() beside one forward run()
-        w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
+        # gradient() beside one forward run(), per order
+        w = wave3d.ricker(4.0, 0.25, K, probs[orders[0]].tau).reshape(K, 1)
         mid = N // 2
-        sol = wave3d.MediumSolver(prob, "hip", sources=[(mid, mid, mid)], wavelet=w,
-                                  receivers=[(mid - K // 5, mid, mid), (mid, mid - K // 4, mid + 3)], taper=sponge)
-        obs = 0.9 * sol.run().traces  # warm-up
+        sols = {o: wave3d.MediumSolver(probs[o], "hip", sources=[(mid, mid, mid)], wavelet=w,
+                                       receivers=[(mid - K // 5, mid, mid), (mid, mid - K // 4, mid + 3)],
+                                       taper=sponge) for o in orders}
+        obs = {o: 0.9 * sols[o].run().traces for o in orders}  # warm-up
         cfgs = [("run", None), ("all_q", K), (f"segment_{a.segment}", a.segment)]
-        rows = {n: [] for n, _ in cfgs}
+        rows = {(n, o): [] for n, _ in cfgs for o in orders}
         for _ in range(a.repeat):
             for name, seg in cfgs:
-                if seg is None:
-                    r = sol.run()
-                    rows[name].append({"loop_ms": round(r.total_ms, 2)})
-                else:
-                    r = sol.gradient(obs, segment=seg)
-                    assert math.isfinite(r.misfit) and r.misfit > 0
-                    rows[name].append({"wall_ms": round(r.total_ms, 1), "forward_ms": round(r.extra["forward_ms"], 2),
-                                       "reverse_ms": round(r.extra["reverse_ms"], 2), "levels": r.extra["levels"],
-                                       "recomputed_steps": r.extra["recomputed_steps"]})
-                print(f"bench_medium: {dtype} {name}: {rows[name][-1]}", file=sys.stderr, flush=True)
-                del r
-                torch.cuda.empty_cache()
-        run_ms = min(v["loop_ms"] for v in rows["run"])
-        for name, seg in cfgs[1:]:
-            best = min(rows[name], key=lambda v: v["forward_ms"] + v["reverse_ms"])
-            passes = best["forward_ms"] + best["reverse_ms"]
-            out["gradient"].append({"dtype": dtype, "schedule": name, **best, "passes_ms": round(passes, 2),
-                                    "run_loop_ms": run_ms, "passes_vs_run": round(passes / run_ms, 3),
-                                    "wall_ms_all": [v["wall_ms"] for v in rows[name]]})
+                for o in orders:
+                    if seg is None:
+                        r = sols[o].run()
+                        rows[(name, o)].append({"loop_ms": round(r.total_ms, 2)})
+                    else:
+                        r = sols[o].gradient(obs[o], segment=seg)
+                        assert math.isfinite(r.misfit) and r.misfit > 0
+                        rows[(name, o)].append({"wall_ms": round(r.total_ms, 1),
+                                                "forward_ms": round(r.extra["forward_ms"], 2),
+                                                "reverse_ms": round(r.extra["reverse_ms"], 2),
+                                                "levels": r.extra["levels"],
+                                                "recomputed_steps": r.extra["recomputed_steps"]})
+                    print(f"bench_medium: {dtype} order {o} {name}: {rows[(name, o)][-1]}", file=sys.stderr, flush=True)
+                    del r
+                    torch.cuda.empty_cache()
+        for o in orders:
+            run_ms = min(v["loop_ms"] for v in rows[("run", o)])
+            for name, seg in cfgs[1:]:
+                best = min(rows[(name, o)], key=lambda v: v["forward_ms"] + v["reverse_ms"])
+                passes = best["forward_ms"] + best["reverse_ms"]
+                out["gradient"].append({"dtype": dtype, "order": o, "schedule": name, **best,
+                                        "passes_ms": round(passes, 2), "run_loop_ms": run_ms,
+                                        "passes_vs_run": round(passes / run_ms, 3),
+                                        "wall_ms_all": [v["wall_ms"] for v in rows[(name, o)]]})
     print(json.dumps(out))
     return 0
 
@@ -152,6 +187,8 @@ def main(argv=None) -> int:
                     help="also time the step with sponge_taper(prob, WIDTH)")
     ap.add_argument("--gradient", action="store_true", help="time the gradient's kernels and schedules instead")
     ap.add_argument("--segment", type=int, default=10, help="--gradient: steps per checkpoint segment")
+    ap.add_argument("--order", default="2", help="space orders to time, e.g. 2,4,8 (alternating inside each repeat)")
+    ap.add_argument("--kernels-only", action="store_true", help="--gradient: the kernel rounds without the schedules")
     a = ap.parse_args(argv)
 
     import math
@@ -164,29 +201,36 @@ def main(argv=None) -> int:
         print("bench_medium: no HIP device (timings are only taken on the GPU)", file=sys.stderr)
         return 2
     N, K = a.N, a.steps
+    orders = [int(v) for v in a.order.split(",")]
+    if not orders or any(o not in (2, 4, 8) for o in orders):
+        ap.error("--order: a comma-separated list of 2, 4, 8")
     if a.gradient:
         return gradient_bench(a)
     variants = a.variants.split(",")
-    # speed2 <= hi keeps the Courant number at 0.9 of the limit 1/sqrt(3) for T = 1
+    # speed2 <= hi keeps the Courant number at 0.9 of the limit for T = 1 (order 2: 1/sqrt(3); the
+    # smallest limit among the orders)
     h = 3.1415926535 / N
-    hi = (0.9 / math.sqrt(3) * h * K) ** 2
+    hi = (0.9 * min(wave3d.cfl_limit(o) for o in orders) * h * K) ** 2
     speed2 = smooth_speed2(N, 0.5 * hi, hi)
     nodes = float(N + 1) ** 3
-    out = {"N": N, "steps": K, "device": torch.cuda.get_device_name(0), "runs": []}
+    out = {"N": N, "steps": K, "orders": orders, "device": torch.cuda.get_device_name(0), "runs": []}
     for dtype in a.dtypes.split(","):
         es = 8 if dtype == "fp64" else 4
-        prob = wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype)
+        probs = {o: wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype, space_order=o) for o in orders}
+        prob = probs[orders[0]]
         w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
         mid = N // 2
 
         sponge = wave3d.sponge_taper(prob, a.taper) if a.taper > 0 else None
 
-        def solver(v, tapered):
-            return wave3d.MediumSolver(prob, "hip", sources=[(mid, mid, mid)], wavelet=w,
+        def solver(v, tapered, order):
+            return wave3d.MediumSolver(probs[order], "hip", sources=[(mid, mid, mid)], wavelet=w,
                                        receivers=[(mid // 2, mid, mid)], variant=None if v == "default" else v,
                                        taper=sponge if tapered else None)
 
-        cfgs = [(v, t) for v in variants for t in ((False, True) if sponge is not None else (False,))]
+        # the ablation variants are k_march_m's: order 2 only
+        cfgs = [(v, t, o) for v in variants for t in ((False, True) if sponge is not None else (False,))
+                for o in orders if o == 2 or v == "default"]
         ms = {c: [] for c in cfgs}
         for c in cfgs:
             solver(*c).run()  # warm-up
@@ -195,17 +239,20 @@ def main(argv=None) -> int:
                 r = solver(*c).run()
                 assert not r.aborted and math.isfinite(max(r.max_abs_u)), "the benchmark run diverged"
                 ms[c].append(r.total_ms)
-                print(f"bench_medium: {dtype} {c[0]}{' taper' if c[1] else ''}: {r.total_ms:.2f} ms",
+                print(f"bench_medium: {dtype} order {c[2]} {c[0]}{' taper' if c[1] else ''}: {r.total_ms:.2f} ms",
                       file=sys.stderr, flush=True)
         for c in cfgs:
             best = min(ms[c])
-            row = {"kernel": "k_march_m", "variant": c[0], "dtype": dtype, "courant": round(prob.courant, 4),
+            row = {"kernel": "k_march_m" if c[2] == 2 else "k_march_mh", "order": c[2], "variant": c[0],
+                   "dtype": dtype, "courant": round(prob.courant, 4),
                    "loop_ms": [round(t, 3) for t in ms[c]], "ms_per_step": round(best / K, 4),
                    "mpts_per_s": round(nodes * K / best / 1e3, 1), "bytes_per_node": 4 * es,
                    "eff_tb_per_s": round(4 * es * nodes * K / (best * 1e-3) / 1e12, 3)}
             if c[1]:
                 row["taper"] = a.taper
-                row["vs_untapered"] = round(best / min(ms[(c[0], False)]), 4)
+                row["vs_untapered"] = round(best / min(ms[(c[0], False, c[2])]), 4)
+            if (c[0], c[1], 2) in ms:
+                row["vs_order2"] = round(best / min(ms[(c[0], c[1], 2)]), 4)
             out["runs"].append(row)
         if not a.no_yardstick:
             yp = wave3d.WaveProblem(N, timesteps=K, dtype=dtype)
@@ -215,7 +262,7 @@ def main(argv=None) -> int:
                                 "solve_ms": [round(t, 3) for t in r.solve_ms],
                                 "ms_per_step": round(nodes / mp / 1e3, 4), "mpts_per_s": round(mp, 1),
                                 "bytes_per_node": 3 * es, "eff_tb_per_s": round(3 * es * mp * 1e6 / 1e12, 3)})
-    for d in (x for x in out["runs"] if x["kernel"] == "k_march_m"):
+    for d in (x for x in out["runs"] if x["kernel"] in ("k_march_m", "k_march_mh")):
         y = [x for x in out["runs"] if x["kernel"] == "k_march" and x["dtype"] == d["dtype"]]
         if y:
             d["bw_vs_k_march"] = round(d["eff_tb_per_s"] / y[0]["eff_tb_per_s"], 3)
