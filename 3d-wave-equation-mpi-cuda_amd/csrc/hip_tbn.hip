@@ -17,7 +17,8 @@
 // Staging (gfx950 LDS-DMA, buffer_load_dword ... lds): A and B never pass through VGPRs. Every
 // A plane (tile + D-ring: (TJ+2D) x (64+2D) values) lands in a 4-slot LDS ring, every B plane
 // (tile + (D-1)-ring) in a 2-slot ring, each row as 256-B pieces (64 lanes x 4 B, lane-linear
-// into the odd-pitch frame row); all of a plane's A/B reads — centre, x+-1 planes, y/z
+// into the odd-pitch frame row; fp64: 16-B chunks packed densely across the row ends, two pieces
+// per wave and plane, DenseDma); all of a plane's A/B reads — centre, x+-1 planes, y/z
 // neighbours — are LDS reads. The loads are invisible to the compiler (inline asm), so its own
 // s_waitcnt never drains them; each iteration waits with a counted vmcnt for the pieces issued
 // one iteration earlier (the stores issued after them stay in flight) and crosses one barrier.
@@ -72,6 +73,11 @@
 // layer 0's A(i) LDS reads issued before the plane's barrier (lds_barrier)
 #ifndef W3D_TBN_PRE
 #define W3D_TBN_PRE 1
+#endif
+// fp64 A/B staging as dense 16-B chunks dealt evenly to the waves (DenseDma / dma_dense2); 0: one
+// piece per frame row (dma_fill3). fp32 always fills per row.
+#ifndef W3D_TBN_DENSE
+#define W3D_TBN_DENSE 1
 #endif
 
 namespace wave3d {
@@ -140,9 +146,10 @@ struct TbnGeom {
     static constexpr int W(int s) { return (kTK + 2 * (D - s)) | 1; }
     static constexpr int cells(int s) { return H(s) * W(s); }
     static constexpr int at(int s, int y, int x) { return (y - s) * W(s) + (x - s); }
-    // A slots: the A frame rounded up to RPW rows per wave (rows past the frame are loaded and
-    // never read). B (= u^{m-2}, read by layer 0 on the tile + (D-1)-ring only): the same rows,
-    // columns 1 .. 64+2D-2 of the A frame at the U_0 frame's pitch W(1): B(y, x) at y W(1) + x - 1
+    // A slots: the A frame rounded up to RPW rows per wave (the per-row fill loads the rows past
+    // the frame, never read). B (= u^{m-2}, read by layer 0 on the tile + (D-1)-ring only, frame
+    // rows 1 .. H(0)-2): the same rows, columns 1 .. 64+2D-2 of the A frame at the U_0 frame's
+    // pitch W(1): B(y, x) at y W(1) + x - 1
     static constexpr int RPW = (H(0) + NW - 1) / NW;
     static constexpr int scells = RPW * NW * W(0);
     static constexpr int bcells = RPW * NW * W(1);
@@ -169,6 +176,52 @@ struct TbnGeom {
         return r;
     }
 };
+
+// Dense LDS-DMA cover of ROWS consecutive rows of an fp64 slot whose pitch is W doubles (odd) and
+// whose payload is W - 1: every row ends in one 8-B pad and the rows start at 0 / 8 mod 16 in
+// turn. The region is cut into 16-B chunks counted from its first byte; the LDS destination of a
+// piece is lane-linear while its source offset is a per-lane register, so a piece runs across row
+// ends. Chunk c (LDS bytes 16c .. 16c+15, o = 16c mod pitch in row r = 16c / pitch):
+//   o < pitch - 8: from row r, column o/8 (o = pitch - 16: its upper half lands in row r's pad);
+//   o = pitch - 8: starts in row r's pad: from row r+1, column -1 (the pad receives the cell
+//                  before the frame column, the lower half of the same 16 global bytes).
+// The chunks are dealt evenly: PW pieces per wave, piece g = w PW + q takes chunks g L .. g L + L-1
+// (the last one `last` of them; the lanes beyond are EXEC-masked: pointed out of range they
+// would write 0 into the next piece's chunks).
+template <int W, int ROWS, int NW>
+struct DenseDma {
+    static constexpr int pitch = W * 8, pay = pitch - 8;
+    static constexpr int chunks = ((ROWS - 1) * pitch + pay + 15) / 16;
+    static constexpr int PW = (chunks + 64 * NW - 1) / (64 * NW);  // pieces per wave
+    static constexpr int NP = NW * PW;
+    static constexpr int L = (chunks + NP - 1) / NP;  // lanes (chunks) per piece
+    static constexpr int last = chunks - (NP - 1) * L;
+    static constexpr int src_row(int c) { return 16 * c / pitch + (16 * c % pitch == pay ? 1 : 0); }
+    static constexpr int src_col(int c) { return 16 * c % pitch == pay ? -1 : 16 * c % pitch / 8; }
+    // every payload cell of the region is written by exactly one chunk half (LDS cell 2c + h: no
+    // two halves share one) from its own global cell, every other half lands in a pad, and no
+    // piece is empty or wider than a wave
+    static constexpr bool covers() {
+        if (W % 2 == 0 || last < 1 || L > 64 || 2 * chunks < (ROWS - 1) * W + W - 1) return false;
+        for (int c = 0; c < chunks; ++c)
+            for (int h = 0; h < 2; ++h) {
+                const int y = (2 * c + h) / W, x = (2 * c + h) % W;
+                if (y >= ROWS) return false;  // past the region's last pad
+                if (x < W - 1 && (src_row(c) != y || src_col(c) + h != x)) return false;
+            }
+        return true;
+    }
+};
+// the fp64 sweeps' A (frame rows 0 .. H-1) and B regions (rows 1 .. H-2: all layer 0 reads)
+template <int D>
+constexpr bool dense_dma_ok() {
+    using Gm = TbnGeom<D, 16, 8, 8>;
+    return DenseDma<Gm::W(0), Gm::H(0), 8>::covers() && DenseDma<Gm::W(1), Gm::H(0) - 2, 8>::covers();
+}
+static_assert(dense_dma_ok<4>() && dense_dma_ok<3>(), "dense LDS-DMA cover of the A / B frames");
+static_assert(DenseDma<73, 24, 8>::chunks == 876 && DenseDma<71, 22, 8>::chunks == 781 && DenseDma<73, 24, 8>::PW == 2 &&
+                  DenseDma<71, 22, 8>::PW == 2,
+              "D = 4: 2 + 2 pieces per wave");
 
 // LDS byte address of a __shared__ object (the DMA destination base in M0)
 template <class T>
@@ -244,6 +297,31 @@ __device__ __forceinline__ void dma_fill3(__amdgpu_buffer_rsrc_t r, unsigned src
               [rs] "s"(r), [rowb] "i"(ROWB), [mask] "s"(u64((1ull << ((RB - 256) / 4)) - 1))
             : "memory", "scc", "m0");
     }
+}
+// Dense fp64 fill (DenseDma): the wave's two pieces of LB bytes each at LDS slot + lds0, from the
+// per-lane source offsets o0 / o1 (computed once per work item: the plane enters through the
+// descriptor). n1 = lanes of the second piece (the region's last piece is shorter). One statement,
+// M0 / SCC as dma_fill3; every piece is partial (L < 64), so EXEC is saved and restored around
+// both; no address arithmetic inside. Sources that are 8 mod 16 (every B chunk, every other A
+// row) and chunks that jump from one row to the next: lds_dma_probe.hip, case F.
+template <int L, int LB>
+__device__ __forceinline__ void dma_dense2(__amdgpu_buffer_rsrc_t r, unsigned o0, unsigned o1, unsigned n1,
+                                           unsigned slot, unsigned lds0) {
+    static_assert(L >= 1 && L < 64 && LB == 16 * L, "partial pieces (s_bfm_b64 masks 1..63 lanes)");
+    u64 keep;
+    asm volatile(
+        "s_add_u32 m0, %[slot], %[lds0]\n\t"
+        "s_mov_b64 %[keep], exec\n\t"
+        "s_bfm_b64 exec, %[n0], 0\n\t"
+        "buffer_load_dwordx4 %[o0], %[rs], 0 offen lds\n\t"
+        "s_add_u32 m0, m0, %[lb]\n\t"
+        "s_bfm_b64 exec, %[n1], 0\n\t"
+        "buffer_load_dwordx4 %[o1], %[rs], 0 offen lds\n\t"
+        "s_mov_b64 exec, %[keep]"
+        : [keep] "=&s"(keep)
+        : [slot] "s"(slot), [lds0] "s"(lds0), [o0] "v"(o0), [o1] "v"(o1), [n1] "s"(n1), [rs] "s"(r), [n0] "n"(L),
+          [lb] "i"(LB)
+        : "memory", "scc", "m0");
 }
 // LDS read of t[o] for the layer gathers: volatile, so LLVM neither sinks it into the branch
 // that consumes it (the ring nodes': behind the own nodes' LDS writes, a second LDS round trip
@@ -463,20 +541,58 @@ k_tbn(const TbnParams<T> p) {
     }
 
     // ---- LDS-DMA staging of A and B -------------------------------------------------------
-    // wave w fills slot rows w*RPW .. w*RPW + RPW-1 of A and B alike (rows past the frame are
-    // loaded and never read). Frame rows past the storage read 0 (past the plane's num_records)
+    // per-row fill (fp32, W3D_TBN_DENSE=0): wave w fills slot rows w*RPW .. w*RPW + RPW-1 of A and
+    // B alike (rows past the frame are loaded and never read). Frame rows past the storage read 0 (past the plane's num_records)
     // and frame columns past it the finite row padding / next row: both only ever feed nodes
     // outside the stencil-valued region (masked to 0).
-    static_assert(Gm::RPW == 3, "dma_fill3: three slot rows per wave");
+    //
+    // fp64 (DENSE): the A frame's H(0) rows and B's rows 1 .. H(0)-2 (all layer 0 reads) as 16-B
+    // chunks dealt evenly, PA + PB pieces per wave (DenseDma), their per-lane source offsets
+    // computed here once. A chunk that straddles a row end also fetches the cell before the
+    // frame's first column (k = kb - D - 1; B: kb - D) or the one after its last (kb + 64 + D;
+    // B: kb + 63 + D) into a pad that is never read: 16 consecutive bytes of the plane either
+    // way. Range: the solver's rows are sj = 16 ceil((16 + Z + G) / 16) values long with k = 1 - G
+    // at row offset 16 - G (12 at G = 4; sizing.cpp level_elems(), poff), so the cell before kb - D >=
+    // 1 - G lies in its own row, and the cell after a frame column <= kmax = Z + G (row offset
+    // 15 + Z + G < sj) is row padding or the next row's first value. (The cell before the first
+    // column is fetched for frame rows >= 1 only, so even on a dense grid, k = 1 - G at row offset
+    // 0 (ops.kernels), it is no lower than the previous row's last value.) A chunk is therefore
+    // cut by num_records only when its lower half is the plane's last value: row padding, or the
+    // node (jmax, kmax) when 16 + Z + G is a multiple of 16 (a dense grid: always). Whether the
+    // hardware then drops the upper 8 B or the whole chunk, only (jmax, kmax) can read 0 for it,
+    // and no unmasked node reads that one: the stencil-valued region ends at cj1 < jmax and
+    // ck1 < kmax, and a node reads (j +- 1, k) and (j, k +- 1), never a diagonal neighbour (of
+    // the A frame it is a ring-D corner or outside). Chunks wholly past the storage read 0 as
+    // the rows did.
+    constexpr bool DENSE = W3D_TBN_DENSE && ES == 8;
+    using DA = DenseDma<W0, Gm::H(0), NW>;
+    using DB = DenseDma<Gm::W(1), Gm::H(0) - 2, NW>;
+    static_assert(DENSE || Gm::RPW == 3, "dma_fill3: three slot rows per wave");
+    static_assert(!DENSE || (DA::PW == 2 && DB::PW == 2 && DA::covers() && DB::covers()),
+                  "dma_dense2: two pieces per wave and fill");
     const unsigned sjb = unsigned(sj) * ES;
-    const unsigned src0 = unsigned((jt - D + w * Gm::RPW) * sj + kb - D + p.poff) * ES;
-    const unsigned lds0 = unsigned(w * Gm::RPW * W0 * ES), bds0 = unsigned(w * Gm::RPW * Gm::W(1) * ES);
+    const unsigned src0 = unsigned((jt - D + (DENSE ? 0 : w * Gm::RPW)) * sj + kb - D + p.poff) * ES;
+    const unsigned lds0 = unsigned(DENSE ? w * 2 * DA::L * 16 : w * Gm::RPW * W0 * ES);
+    const unsigned bds0 = unsigned(DENSE ? w * 2 * DB::L * 16 + Gm::W(1) * ES : w * Gm::RPW * Gm::W(1) * ES);
+    // source offset of this lane's chunk of the wave's piece q (masked lanes: the last chunk's)
+    auto dsrc = [&](auto geom, int q, unsigned origin) {
+        using Dn = decltype(geom);
+        const int c = min((w * Dn::PW + q) * Dn::L + lane, Dn::chunks - 1);
+        return origin + unsigned(Dn::src_row(c)) * sjb + unsigned(Dn::src_col(c) * ES);
+    };
+    const unsigned da0 = DENSE ? dsrc(DA{}, 0, src0) : 0u, da1 = DENSE ? dsrc(DA{}, 1, src0) : 0u;
+    const unsigned db0 = DENSE ? dsrc(DB{}, 0, src0 + sjb + ES) : 0u, db1 = DENSE ? dsrc(DB{}, 1, src0 + sjb + ES) : 0u;
+    const unsigned nla = w == NW - 1 ? DA::last : DA::L, nlb = w == NW - 1 ? DB::last : DB::L;
     auto fillA = [&](auto qc, int plane, bool live) {
-        dma_fill3<ES, W0 * ES, Gm::rowb>(prs(p.A, plane, live ? pbytes : 0u), src0, sjb, lds_addr(Ap(qc)), lds0);
+        const auto rs = prs(p.A, plane, live ? pbytes : 0u);
+        if constexpr (DENSE) dma_dense2<DA::L, DA::L * 16>(rs, da0, da1, nla, lds_addr(Ap(qc)), lds0);
+        else dma_fill3<ES, W0 * ES, Gm::rowb>(rs, src0, sjb, lds_addr(Ap(qc)), lds0);
     };
     auto fillB = [&](int q, int plane, bool live) {
-        dma_fill3<ES, Gm::W(1) * ES, Gm::browb>(prs(p.B, plane, live ? pbytes : 0u), src0 + ES, sjb,
-                                                __builtin_amdgcn_readfirstlane(lds_addr(Bp(q))), bds0);
+        const auto rs = prs(p.B, plane, live ? pbytes : 0u);
+        const unsigned slot = __builtin_amdgcn_readfirstlane(lds_addr(Bp(q)));
+        if constexpr (DENSE) dma_dense2<DB::L, DB::L * 16>(rs, db0, db1, nlb, slot, bds0);
+        else dma_fill3<ES, Gm::W(1) * ES, Gm::browb>(rs, src0 + ES, sjb, slot, bds0);
     };
     // Two planes of lookahead for A, one for B: A(x) in A slot (x - i0) & 3 — A(i), A(i+1) read
     // at iteration i, A(i+2) in flight, A(i+3) issued into the slot of A(i-1), whose own-node and
@@ -484,15 +600,17 @@ k_tbn(const TbnParams<T> p) {
     // 0, U_{-1} for layer 1); B(x) in B slot (x - i0) & 1 — B(i) read, B(i+1) issued into the slot
     // of B(i-1). Each iteration issues its B piece first, then its A pieces, then its stores; a
     // steady iteration waits for B(i) and what came before it, i.e. for all but the A pieces and
-    // stores of iteration i-1: NA + NST (the first sweep, with no B: NDMA + 2 NST).
+    // stores of iteration i-1: NA + NST (the first sweep, with no B: NDMA + 2 NST). Pieces per
+    // wave: fp64 dense PA for A and PB for B (2 + 2); per row RPW each (fp32: 2 RPW).
     constexpr int NST = 2 * R;                                  // stores of the last two layers
+    constexpr int PA = DENSE ? DA::PW : (ES == 8 ? 1 : 2) * Gm::RPW, PB = DENSE ? DB::PW : PA;
     // layer 0's A(i) reads issued before the plane's barrier (lds_barrier<NPRE>): 2 + 3R own
     // (outer j neighbours, z neighbours, centres), 5 per ring slot (4 neighbours, centre)
     // (fp64 fma: +4.4 %; exact -1.5 %; fp32 leapfrog neutral, the fp32 increment form spills: -12 %)
     constexpr bool PRE = W3D_TBN_PRE && ES == 8 && FM && !DELTA;  // (the fp64 increment form: registers)
     constexpr int NPRE = std::min(2 + 3 * R + 5 * RP, 15);  // (lgkmcnt holds 0..15)
     // pieces per iteration: A, and B unless this is the first sweep (which reads no B)
-    constexpr int NDMA = (ES == 8 ? 1 : 2) * Gm::RPW * (FIRST ? 1 : 2);
+    constexpr int NDMA = PA + (FIRST ? 0 : PB);
     // prologue: A(i0-1) .. A(i0+2) into slots 3, 0, 1, 2; B(i0) into slot 0; then
     // A(i0-1)'s register copies
     fillA(Ic<3>{}, i0 - 1, true);
@@ -694,7 +812,7 @@ k_tbn(const TbnParams<T> p) {
         // everything), and B(i), which iteration i-1 issued first (wait for it and what came
         // before, leaving its A pieces and stores in flight) -> barrier -> DMA B(i+1), A(i+3)
         // into the slots of B(i-1), A(i-1), whose last readers passed the barrier
-        constexpr int NA = (ES == 8 ? 1 : 2) * Gm::RPW;
+        constexpr int NA = PA;
         if constexpr (FAST && !FIRST) vm_wait<NA + NST>();
         else if constexpr (FAST) vm_wait<NDMA + 2 * NST>();
         else vm_wait<0>();
