@@ -329,21 +329,23 @@ void k_zero_faces(uintptr_t u, const std::vector<i64>& g, int mask, uintptr_t st
 // view carries explicit strides (dense tensors or the padded views of ops.kernels.alloc_level).
 // gx, gy, gz: the sponge tables (nx, ny, nz device values), all 0 for the undamped step.
 // lap_out / (q, acc): the grids of the save / image modes, all 0 for the plain step.
+// b: the buoyancy grid 1 / rho of the variable-density step (k_march_mb), 0 for constant density.
 template <class T>
 void k_step_medium(bool first, uintptr_t u1, uintptr_t u2, uintptr_t m, uintptr_t u, const std::vector<i64>& g,
                    const std::vector<std::vector<int>>& boxes, int ei0, int ei1, const std::vector<int>& wrap,
                    const std::vector<double>& h2, uintptr_t err, int chunk, uintptr_t stream, int variant,
                    uintptr_t gx, uintptr_t gy, uintptr_t gz, uintptr_t lap_out, uintptr_t q, uintptr_t acc, int order,
-                   const std::vector<int>& mirror) {
+                   const std::vector<int>& mirror, uintptr_t b) {
     std::vector<Box> bx;
-    for (auto& b : boxes) bx.push_back(tobox(b));
+    for (auto& e : boxes) bx.push_back(tobox(e));
     W3D_REQUIRE(h2.size() == 3, "h2 = (hx2, hy2, hz2)");
     const double h[3] = {h2[0], h2[1], h2[2]};
     // mirror: empty = none, or (j_lo, j_hi, k_lo, k_hi) with no_mirror for a side without a face
     W3D_REQUIRE(mirror.empty() || mirror.size() == 4, "mirror = (j_lo, j_hi, k_lo, k_hi)");
     launch_step_medium<T>(first, P<T>(u1), P<T>(u2), P<T>(m), P<T>(u), gview(g), bx.data(), int(bx.size()), ei0,
                           ei1, towrap(wrap), h, P<u64>(err), chunk, (hipStream_t)stream, variant, P<T>(gx), P<T>(gy),
-                          P<T>(gz), P<T>(lap_out), P<T>(q), P<T>(acc), order, mirror.empty() ? nullptr : mirror.data());
+                          P<T>(gz), P<T>(lap_out), P<T>(q), P<T>(acc), order, mirror.empty() ? nullptr : mirror.data(),
+                          P<T>(b));
 }
 
 // nodes: device int32 [n][3] of (i, j, k); g / out: n device values
@@ -567,7 +569,8 @@ PYBIND11_MODULE(_wave3d_C, m) {
     py::arg("first"), py::arg("u1"), py::arg("u2"), py::arg("m"), py::arg("u"), py::arg("grid"), py::arg("boxes"), \
         py::arg("ei0"), py::arg("ei1"), py::arg("wrap"), py::arg("h2"), py::arg("err"), py::arg("chunk"),          \
         py::arg("stream"), py::arg("variant"), py::arg("gx"), py::arg("gy"), py::arg("gz"), py::arg("lap_out"),    \
-        py::arg("q"), py::arg("acc"), py::arg("order") = 2, py::arg("mirror") = std::vector<int>{}
+        py::arg("q"), py::arg("acc"), py::arg("order") = 2, py::arg("mirror") = std::vector<int>{},         \
+        py::arg("b") = 0
     m.def("k_step_medium_f64", &k_step_medium<double>, W3D_STEP_MEDIUM_ARGS);
     m.def("k_step_medium_f32", &k_step_medium<float>, W3D_STEP_MEDIUM_ARGS);
 #undef W3D_STEP_MEDIUM_ARGS

@@ -14,6 +14,9 @@
 //  * k_march_mh: the same march with a star stencil of half-width M = 2 or 4 per axis (space
 //    orders 4 and 8): a (2M + 2)-slot u^{n-1} ring, an M-deep LDS halo and odd reflection at the
 //    Dirichlet faces (described at the kernel).
+//  * k_march_mb: k_march_m with a variable density: the operator div(b grad u) with the buoyancy
+//    b = 1 / rho as a fifth stream that rolls through registers and LDS like u^{n-1} (described at
+//    the kernel).
 //  * k_inject / k_record: one thread per source entry / receiver.
 //
 // FP contraction is off (-ffp-contract=off + the pragmas in stencil_math.hpp): every operation
@@ -629,6 +632,290 @@ int march_mh_rows(int mode) {
     return mode == kSave ? mh_rows<T, M, kSave>() : mode == kImage ? mh_rows<T, M, kImage>() : mh_rows<T, M, kPlain>();
 }
 
+// ---- variable density: k_march_mb ----------------------------------------------------------
+template <class T>
+struct MediumParamsB : MediumParams<T> {
+    const T* b;  // buoyancy 1 / rho, a level with the strides of u1 (x ghost planes filled)
+};
+
+// One axis of div(b grad u): the difference of the two face fluxes, a face buoyancy being the
+// arithmetic mean of its two nodes' (the product with 0.5 is exact); ops/reference.py
+// laplace_density has the same operations in the same order.
+template <class T>
+__device__ __forceinline__ T flux_diff(T c, T um, T up, T bc, T bm, T bp) {
+#pragma clang fp contract(off)
+    const T fp = (T(0.5) * (bc + bp)) * (up - c);
+    const T fm = (T(0.5) * (bc + bm)) * (c - um);
+    return fp - fm;
+}
+
+// k_march_m (non-temporal m, R rows per lane) with lap(u1) replaced by
+// D_b u1 = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2, t = flux_diff per axis: the same tile, march,
+// streams, sponge, modes (kSave stores D_b u1), stores, statistic and masking. The fifth stream b
+// needs its six neighbours, so it is handled exactly like u1: b at the lane's own nodes rolls
+// through a 4-slot register ring (planes i-1, i, i+1 and the prefetch slot, the phase a template
+// constant), plane i of b is staged in a second double-buffered LDS tile of the same shape, and
+// each halo lane loads its one b cell per plane beside its u1 cell, with the same offset and the
+// same kOOB masking. The plane's one barrier covers both tiles. The j neighbours of a lane's inner
+// rows come from registers for b as for u1. The loads of b are ordinary temporal loads (the halo
+// lines are reused across tiles through L2); m stays non-temporal. A masked b reads 0: it only
+// enters nodes whose stores are masked too. 40 B per node in fp64 (20 B in fp32).
+template <class T, bool FIRST, int R, bool TAPER, int MODE = kPlain>
+__global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p) {
+    constexpr int kTJ = kWaves * R;
+    constexpr unsigned ES = sizeof(T);
+    __shared__ T lds[2][kTJ + 2][kLW];
+    __shared__ T ldb[2][kTJ + 2][kLW];
+
+    const int bid = xcd_swizzle(blockIdx.x, gridDim.x, p.xcd);
+    const int b = find_box(p, bid);
+    const BoxLaunch B = p.box[b];
+    int local = bid - B.block_begin;
+    const int tk = local % B.tiles_k;
+    local /= B.tiles_k;
+    const int tj = local % B.tiles_j;
+    const int ci = local / B.tiles_j;
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int kb = B.kbase + tk * kTK;
+    const int k = kb + lane;
+    const int jt = B.j0 + tj * kTJ;
+    const int ib = B.i0 + ci * B.chunk;
+    const int ie = min(B.i1, ib + B.chunk - 1);
+
+    const bool kload = k <= p.kmax;
+    const bool kin = k >= B.k0 && k <= B.k1;
+    const i64 si = p.si;
+    const unsigned pbytes = unsigned(si) * ES;
+    auto boff = [&](int j, int kk, bool ok) { return ok ? unsigned(j * p.sj + kk + p.poff) * ES : kOOB; };
+    auto prs = [&](const T* base, int i) { return plane_rsrc(base + (i64(i) * si - p.poff), pbytes); };
+
+    unsigned oa[R], ou2[R], os[R];
+    bool valid[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int j = jt + w * R + r;
+        valid[r] = kin && j <= B.j1;
+        oa[r] = boff(j, k, kload && j <= p.jmax);  // u1 and b
+        ou2[r] = boff(j, k, !FIRST && valid[r]);
+        os[r] = boff(j, k, valid[r]);  // stores, and the loads of m
+    }
+
+    // halo role of this lane (k_march_m's): one LDS cell per plane and tile
+    int hrow = 0, hcol = 0;
+    unsigned hoff = kOOB;
+    bool hon = false;
+    if (w == 0) {  // row jt-1
+        hon = true;
+        hoff = boff(jt - 1, k, kload);
+        hrow = 0;
+        hcol = 1 + lane;
+    } else if (w == kWaves - 1) {  // row jt+TJ
+        const int j = jt + kTJ;
+        hon = true;
+        hoff = boff(j, k, kload && j <= p.jmax);
+        hrow = kTJ + 1;
+        hcol = 1 + lane;
+    } else if (w == 1) {  // columns kb-1 (lanes 0..TJ-1) and kb+64 (lanes 32..32+TJ-1)
+        const int side = lane >> 5, rr = lane & 31;
+        const int j = jt + rr;
+        const int kk = side ? kb + kTK : kb - 1;
+        hon = rr < kTJ;
+        hoff = boff(j, kk, hon && j <= p.jmax && kk <= p.kmax);
+        hrow = 1 + rr;
+        hcol = side ? kTK + 1 : 0;
+    }
+    constexpr int kMAux = 2;   // non-temporal m (read once per step)
+    constexpr int kStAux = 2;  // non-temporal stores (write-once stream)
+
+    static_assert(MODE == kPlain || !FIRST, "save / image modes: leapfrog steps only");
+    constexpr bool kImg = MODE == kImage;
+    T u1[4][R], bb[4][R], u2[2][R], mm[2][R];
+    T qq[kImg ? 2 : 1][kImg ? R : 1], aa[kImg ? 2 : 1][kImg ? R : 1];
+    T hv[2], hb[2];
+    if constexpr (kImg) {
+        const auto rQ = prs(p.q, ib), rA = prs(p.acc, ib);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            qq[0][r] = bld<T, 2>(rQ, os[r]);
+            aa[0][r] = bld<T, 2>(rA, os[r]);
+            qq[1][r] = aa[1][r] = T(0);
+        }
+    }
+    {
+        const auto r0 = prs(p.u1, ib - 1), r1 = prs(p.u1, ib), r2 = prs(p.u1, ib + 1);
+        const auto b0 = prs(p.b, ib - 1), b1 = prs(p.b, ib), b2 = prs(p.b, ib + 1);
+        const auto q0 = prs(p.u2, ib), m0 = prs(p.m, ib);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            u1[0][r] = bld<T>(r0, oa[r]);
+            u1[1][r] = bld<T>(r1, oa[r]);
+            u1[2][r] = bld<T>(r2, oa[r]);
+            u1[3][r] = T(0);
+            bb[0][r] = bld<T>(b0, oa[r]);
+            bb[1][r] = bld<T>(b1, oa[r]);
+            bb[2][r] = bld<T>(b2, oa[r]);
+            bb[3][r] = T(0);
+            u2[0][r] = FIRST ? T(0) : bld<T>(q0, ou2[r]);
+            u2[1][r] = T(0);
+            mm[0][r] = bld<T, kMAux>(m0, os[r]);
+            mm[1][r] = T(0);
+        }
+        hv[0] = bld<T>(r1, hoff);
+        hb[0] = bld<T>(b1, hoff);
+        hv[1] = hb[1] = T(0);
+    }
+    const T hx2 = p.hx2, hy2 = p.hy2, hz2 = p.hz2;
+    const T yx2 = p.yx2, yy2 = p.yy2, yz2 = p.yz2;
+
+    T gyz[TAPER ? R : 1];
+    T gxn = T(1);
+    if constexpr (TAPER) {
+#pragma clang fp contract(off)
+        const T gzk = p.gz[min(k, p.kmax)];
+#pragma unroll
+        for (int r = 0; r < R; ++r) gyz[r] = ldconst(p.gy, min(jt + w * R + r, p.jmax)) * gzk;
+        gxn = ldconst(p.gx, ib);
+    }
+
+    T ma = T(kErrInit);
+    T chk = T(0);
+
+    auto plane = [&](auto phase, const int i) {
+        constexpr int P = decltype(phase)::value;
+        constexpr int S0 = P & 3, S1 = (P + 1) & 3, S2 = (P + 2) & 3, S3 = (P + 3) & 3;
+        constexpr int H0 = P & 1, H1 = (P + 1) & 1;
+        // prefetch u1, b (i+2, own rows), u1, b (i+1, halo), u2(i+1), m(i+1); 0-record descriptors
+        // on the last plane (loads return 0 without touching memory)
+        {
+            const bool more = i < ie;
+            const unsigned nb = more ? pbytes : 0u;
+            const int d2 = more ? 2 : 0, d1 = more ? 1 : 0;
+            const auto rN = plane_rsrc(p.u1 + (i64(i + d2) * si - p.poff), nb);
+            const auto rH = plane_rsrc(p.u1 + (i64(i + d1) * si - p.poff), nb);
+            const auto bN = plane_rsrc(p.b + (i64(i + d2) * si - p.poff), nb);
+            const auto bH = plane_rsrc(p.b + (i64(i + d1) * si - p.poff), nb);
+            const auto rU = plane_rsrc(p.u2 + (i64(i + d1) * si - p.poff), nb);
+            const auto rM = plane_rsrc(p.m + (i64(i + d1) * si - p.poff), nb);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                u1[S3][r] = bld<T>(rN, oa[r]);
+                bb[S3][r] = bld<T>(bN, oa[r]);
+                if (!FIRST) u2[H1][r] = bld<T>(rU, ou2[r]);
+                mm[H1][r] = bld<T, kMAux>(rM, os[r]);
+            }
+            hv[H1] = bld<T>(rH, hoff);
+            hb[H1] = bld<T>(bH, hoff);
+            if constexpr (kImg) {
+                const auto rQ = plane_rsrc(p.q + (i64(i + d1) * si - p.poff), nb);
+                const auto rA = plane_rsrc(p.acc + (i64(i + d1) * si - p.poff), nb);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    qq[H1][r] = bld<T, 2>(rQ, os[r]);
+                    aa[H1][r] = bld<T, 2>(rA, os[r]);
+                }
+            }
+        }
+
+        // stage plane i of u1 and b: one barrier for both tiles
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            lds[H0][1 + w * R + r][1 + lane] = u1[S1][r];
+            ldb[H0][1 + w * R + r][1 + lane] = bb[S1][r];
+        }
+        if (hon) {
+            lds[H0][hrow][hcol] = hv[H0];
+            ldb[H0][hrow][hcol] = hb[H0];
+        }
+        __syncthreads();
+
+        const bool erow = i >= p.ei0 && i <= p.ei1;
+        const T gxi = gxn;
+        if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
+        T vv[R];
+        T xv[MODE == kPlain ? 1 : R];  // kSave: D_b u1; kImage: the new acc
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+#pragma clang fp contract(off)
+            const int lr = 1 + w * R + r;
+            const T c = u1[S1][r], bc = bb[S1][r];
+            const T jm = r == 0 ? lds[H0][lr - 1][1 + lane] : u1[S1][r - 1];
+            const T jp = r == R - 1 ? lds[H0][lr + 1][1 + lane] : u1[S1][r + 1];
+            const T bjm = r == 0 ? ldb[H0][lr - 1][1 + lane] : bb[S1][r - 1];
+            const T bjp = r == R - 1 ? ldb[H0][lr + 1][1 + lane] : bb[S1][r + 1];
+            const T tx = flux_diff(c, u1[S0][r], u1[S2][r], bc, bb[S0][r], bb[S2][r]);
+            const T ty = flux_diff(c, jm, jp, bc, bjm, bjp);
+            const T tz = flux_diff(c, lds[H0][lr][lane], lds[H0][lr][lane + 2], bc, ldb[H0][lr][lane],
+                                   ldb[H0][lr][lane + 2]);
+            T lap = T(0);
+            lap = lap + div_const(tx, hx2, yx2);
+            lap = lap + div_const(ty, hy2, yy2);
+            lap = lap + div_const(tz, hz2, yz2);
+            if constexpr (MODE == kSave) xv[r] = lap;
+            if constexpr (kImg) {
+                const T pr = c * qq[H0][r];
+                xv[r] = aa[H0][r] + pr;
+            }
+            if constexpr (FIRST) {
+                const T half_m = T(0.5) * mm[H0][r];  // exact
+                vv[r] = taylor_first(c, lap, half_m);
+                if constexpr (TAPER) vv[r] = (gxi * gyz[r]) * vv[r];
+            } else if constexpr (TAPER) {
+                const T g = gxi * gyz[r];
+                vv[r] = g * leapfrog(c, g * u2[H0][r], lap, mm[H0][r]);
+            } else {
+                vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]);
+            }
+        }
+        // stores: own plane + fused periodic wrap (buffer stores, masked lanes dropped)
+        {
+            const auto rs = prs(p.u, i);
+#pragma unroll
+            for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rs, os[r]);
+#pragma unroll
+            for (int g = 0; g < 2; ++g)
+                if (i >= p.w_lo[g] && i <= p.w_hi[g]) {
+                    const auto rw = prs(p.u, i + p.w_sh[g]);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
+                }
+            if constexpr (MODE != kPlain) {
+                const auto rx = prs(MODE == kSave ? p.lap_out : p.acc, i);
+#pragma unroll
+                for (int r = 0; r < R; ++r) bst<kStAux>(xv[r], rx, os[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (!valid[r]) continue;
+            chk += vv[r];
+            if (erow) ma = max_abs(ma, vv[r]);
+        }
+    };
+
+    for (int i = ib;;) {
+        plane(Ph<0>{}, i);
+        if (++i > ie) break;
+        plane(Ph<1>{}, i);
+        if (++i > ie) break;
+        plane(Ph<2>{}, i);
+        if (++i > ie) break;
+        plane(Ph<3>{}, i);
+        if (++i > ie) break;
+    }
+    commit_errors(ma, T(kErrInit), chk, p.err);
+}
+
+// the k_march_mb instantiations: 4 rows per lane (`make resources`: no scratch in any of them)
+template <class T>
+void (*march_mb_kernel(bool first, bool taper, int mode))(const MediumParamsB<T>) {
+    if (mode == kSave) return taper ? k_march_mb<T, false, 4, true, kSave> : k_march_mb<T, false, 4, false, kSave>;
+    if (mode == kImage) return taper ? k_march_mb<T, false, 4, true, kImage> : k_march_mb<T, false, 4, false, kImage>;
+    if (first) return taper ? k_march_mb<T, true, 4, true> : k_march_mb<T, true, 4, false>;
+    return taper ? k_march_mb<T, false, 4, true> : k_march_mb<T, false, 4, false>;
+}
+
 struct NodeGrid {
     i64 si;
     int sj;
@@ -713,8 +1000,10 @@ template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant, const T* gx,
-                        const T* gy, const T* gz, T* lap_out, const T* q, T* acc, int order, const int* mirror) {
+                        const T* gy, const T* gz, T* lap_out, const T* q, T* acc, int order, const int* mirror,
+                        const T* b) {
     W3D_REQUIRE(order == 2 || order == 4 || order == 8, "space order must be 2, 4 or 8, not " + std::to_string(order));
+    W3D_REQUIRE(!b || order == 2, "variable density (b) exists for space order 2 only");
     const int M = order / 2;
     const bool taper = gx || gy || gz;
     W3D_REQUIRE(!taper || (gx && gy && gz), "the sponge needs all three tables");
@@ -724,6 +1013,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     W3D_REQUIRE(gv.si > 0 && gv.si * i64(sizeof(T)) < (1ll << 31), "plane larger than a buffer descriptor's range");
     W3D_REQUIRE(gv.sj >= gv.Z + 2 * gv.G && gv.si >= i64(gv.Y + 2 * gv.G) * gv.sj, "strides smaller than the grid");
     if (variant < 0) variant = medium_variant();
+    W3D_REQUIRE(!b || variant == 1, "variable density (b) is instantiated for the default variant only (nt, 4 rows per lane)");
     const bool save = lap_out != nullptr, image = q || acc;
     W3D_REQUIRE(!image || (q && acc), "image mode needs both q and acc");
     W3D_REQUIRE(!(save && image), "save mode (lap_out) and image mode (q, acc) cannot be combined");
@@ -836,6 +1126,14 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
         HIP_OK(hipGetLastError());
         return;
     }
+    if (b) {
+        MediumParamsB<T> pb{};
+        static_cast<MediumParams<T>&>(pb) = p;
+        pb.b = b;
+        hipLaunchKernelGGL(march_mb_kernel<T>(first, taper, mode), dim3(total), dim3(kThreads), 0, s, pb);
+        HIP_OK(hipGetLastError());
+        return;
+    }
     void (*kern)(const MediumParams<T>) =
         taper ? (first ? march_m_kernel<T, true, true>(variant) : march_m_kernel<T, false, true>(variant))
               : (first ? march_m_kernel<T, true, false>(variant) : march_m_kernel<T, false, false>(variant));
@@ -864,7 +1162,7 @@ void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int
     template void launch_step_medium<T>(bool, const T*, const T*, const T*, T*, const GridView&,       \
                                         const Box*, int, int, int, const Wrap&, const double[3], u64*, \
                                         int, hipStream_t, int, const T*, const T*, const T*, T*,       \
-                                        const T*, T*, int, const int*);                                \
+                                        const T*, T*, int, const int*, const T*);                      \
     template void launch_inject<T>(T*, const T*, const GridView&, const int*, const T*, int,           \
                                    const Wrap&, hipStream_t);                                          \
     template void launch_record<T>(const T*, const GridView&, const int*, T*, int, hipStream_t);

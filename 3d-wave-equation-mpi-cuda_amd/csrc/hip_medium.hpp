@@ -41,6 +41,15 @@ namespace wave3d {
 // stored; the boxes lie strictly inside the faces, a pair of faces is at least M apart, and on a
 // side without a face the boxes keep M nodes from the storage edge. Every violation is rejected
 // before the launch, so no address outside a level's plane is formed.
+//
+// Variable density (b non-null; order 2 and the default variant 1 only, anything else is rejected
+// before the launch): b = 1 / rho is a level like u1, x ghost planes filled, and m = rho c^2 tau^2.
+// k_march_mb replaces lap(u1) in every form above (Taylor start, leapfrog, sponge, save, image) by
+// D_b u1 = div(b grad u1): per axis, with centre c, neighbours u_-, u_+ and buoyancies b_c, b_-, b_+,
+// f_+ = (0.5 (b_c + b_+)) (u_+ - c), f_- = (0.5 (b_c + b_-)) (c - u_-), t = f_+ - f_-, and
+// D_b u1 = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2, every operation rounded on its own, the
+// divisions correctly rounded (ops/reference.py laplace_density). Save mode stores D_b u1. b is read
+// at the box nodes and their six neighbours, never written. Per node in fp64: 40 B (20 B in fp32).
 constexpr int kNoMirror = -(1 << 29);
 template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
@@ -48,7 +57,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant = -1,
                         const T* gx = nullptr, const T* gy = nullptr, const T* gz = nullptr,
                         T* lap_out = nullptr, const T* q = nullptr, T* acc = nullptr, int order = 2,
-                        const int* mirror = nullptr);
+                        const int* mirror = nullptr, const T* b = nullptr);
 
 // Central second-derivative weight c_d of the star stencil of `order` (2, 4, 8), d = 0 .. order / 2:
 // the double quotient of its two integers (order 4: -5/2, 4/3, -1/12; order 8: -205/72, 8/5, -1/5,

@@ -1,4 +1,5 @@
-"""Variable-speed medium front-end: ``(1/c^2) u_tt = lap u + f`` with point sources and receivers.
+"""Variable-speed medium front-end: ``(1/c^2) u_tt = lap u + f`` with point sources and receivers,
+or with a density model ``(1/(rho c^2)) u_tt = div((1/rho) grad u) + f``.
 
 ``MediumProblem`` describes the box, the grid and the squared wave speed c^2(x, y, z) on the
 constant-speed solver's grid (``N+1`` nodes per axis, periodic in x with planes 0 and N both
@@ -35,11 +36,19 @@ class MediumProblem:
 
     ``space_order``: 2 (the 7-point Laplacian, the default), 4 or 8 (star stencils of half-width
     M = order / 2 with odd reflection at the Dirichlet faces; needs N >= 2 M). The stability limit
-    of the Courant number depends on it (:func:`cfl_limit`)."""
+    of the Courant number depends on it (:func:`cfl_limit`).
+
+    ``density``: rho as a float or an ``(N+1)^3`` array/tensor, finite, > 0 and periodic in x
+    (``space_order`` 2 only). The equation becomes ``(1/kappa) u_tt = div(b grad u) + f`` with the bulk
+    modulus ``kappa = rho c^2`` and the buoyancy ``b = 1/rho`` (``ops.reference.laplace_density``), so
+    impedance contrasts reflect. The Courant number is then ``sqrt(max_i kappa_i bhat_i) tau / h_min``
+    over the stencil nodes, ``bhat_i`` the largest of node i's six face buoyancies; by Gershgorin the
+    limit 1/sqrt(3) stays sufficient. A scalar density leaves it at ``c_max tau / h_min``. None: the
+    constant-density solver, unchanged."""
 
     def __init__(self, N: int, speed2, Lx: Any = "pi", Ly: Any = "pi", Lz: Any = "pi", T: float = 1.0,
                  timesteps: int = 20, dtype: str = "fp64", pi: str = "ref", strict_cfl: bool = True,
-                 space_order: int = 2):
+                 space_order: int = 2, density=None):
         if dtype not in _DTYPES:
             raise ValueError(f"dtype must be fp64 or fp32, not {dtype!r}")
         if N < 2 or timesteps < 1:
@@ -52,20 +61,17 @@ class MediumProblem:
         self.cfl_limit = cfl_limit(self.space_order)
         self.N, self.Lx, self.Ly, self.Lz = int(N), Lx, Ly, Lz
         self.T, self.timesteps, self.dtype, self.pi = float(T), int(timesteps), dtype, pi
-        s = torch.as_tensor(speed2, dtype=torch.float64).cpu()
-        n1 = self.N + 1
-        if s.dim() != 0 and tuple(s.shape) != (n1, n1, n1):
-            raise ValueError(f"speed2 must be a scalar or have shape {(n1, n1, n1)}, not {tuple(s.shape)}")
-        bad = ~(torch.isfinite(s) & (s > 0))
-        if bool(bad.any()):
-            v = s[bad].flatten()[0].item() if s.dim() else s.item()
-            raise ValueError(f"speed2 must be finite and > 0, found {v}")
-        if s.dim() != 0 and not torch.equal(s[0], s[self.N]):
-            j, k = (int(x) for x in (s[0] != s[self.N]).nonzero()[0])
-            raise ValueError(f"speed2 must be periodic in x: speed2[0,{j},{k}] = {s[0, j, k].item()} but "
-                             f"speed2[{self.N},{j},{k}] = {s[self.N, j, k].item()}")
+        s = self._field(speed2, "speed2")
         self.speed2 = s
         self.max_speed2 = float(s.max())
+        self.density = None
+        self._cfl_speed2 = self.max_speed2  # (Courant number h_min / tau)^2
+        if density is not None:
+            if self.space_order != 2:
+                raise ValueError(f"density needs space_order 2, not {self.space_order}")
+            self.density = self._field(density, "density")
+            if self.density.dim() != 0:
+                self._cfl_speed2 = self._max_kappa_bhat()
         if self.courant > self.cfl_limit:
             msg = (f"Courant number {self.courant:.4g} exceeds the stability limit {self.cfl_limit:.4g} of space "
                    f"order {self.space_order}: "
@@ -73,6 +79,41 @@ class MediumProblem:
             if strict_cfl:
                 raise ValueError(msg)
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
+
+    def _field(self, v, name: str) -> torch.Tensor:
+        """A model field as a float64 CPU tensor: a scalar or ``(N+1)^3``, finite, > 0, periodic in x."""
+        s = torch.as_tensor(v, dtype=torch.float64).cpu()
+        n1 = self.N + 1
+        if s.dim() != 0 and tuple(s.shape) != (n1, n1, n1):
+            raise ValueError(f"{name} must be a scalar or have shape {(n1, n1, n1)}, not {tuple(s.shape)}")
+        bad = ~(torch.isfinite(s) & (s > 0))
+        if bool(bad.any()):
+            v = s[bad].flatten()[0].item() if s.dim() else s.item()
+            raise ValueError(f"{name} must be finite and > 0, found {v}")
+        if s.dim() != 0 and not torch.equal(s[0], s[self.N]):
+            j, k = (int(x) for x in (s[0] != s[self.N]).nonzero()[0])
+            raise ValueError(f"{name} must be periodic in x: {name}[0,{j},{k}] = {s[0, j, k].item()} but "
+                             f"{name}[{self.N},{j},{k}] = {s[self.N, j, k].item()}")
+        return s
+
+    def _max_kappa_bhat(self) -> float:
+        """``max_i kappa_i bhat_i`` over the stencil nodes (every x plane, j and k in 1..N-1): kappa =
+        speed2 rho, bhat_i = the largest of node i's six face buoyancies, a face buoyancy being the mean
+        of its two nodes' 1/rho (x periodic: planes 0 and N are one plane)."""
+        N = self.N
+        rho = self.density
+        b = 1.0 / rho
+        bs = torch.cat([b[N - 1:N], b, b[1:2]])  # x ghost planes
+        own = (slice(1, N + 2), slice(1, N), slice(1, N))
+        nb = None
+        for axis in range(3):
+            for d in (-1, 1):
+                sl = list(own)
+                sl[axis] = slice(own[axis].start + d, own[axis].stop + d)
+                nb = bs[tuple(sl)] if nb is None else torch.maximum(nb, bs[tuple(sl)])
+        bhat = 0.5 * (bs[own] + nb)
+        kappa = (self.speed2 * rho).expand(N + 1, N + 1, N + 1)[:, 1:N, 1:N]
+        return float((kappa * bhat).max())
 
     def _pi(self) -> float:
         return PI_REF if self.pi == "ref" else math.pi
@@ -87,15 +128,15 @@ class MediumProblem:
 
     @property
     def courant(self) -> float:
-        return math.sqrt(self.max_speed2) * self.tau / (min(self.lengths()) / self.N)
+        return math.sqrt(self._cfl_speed2) * self.tau / (min(self.lengths()) / self.N)
 
     def stable(self) -> bool:
         return self.courant <= self.cfl_limit
 
     def min_stable_timesteps(self) -> int:
-        k = math.ceil(math.sqrt(self.max_speed2) * self.T * self.N / (min(self.lengths()) * self.cfl_limit))
+        k = math.ceil(math.sqrt(self._cfl_speed2) * self.T * self.N / (min(self.lengths()) * self.cfl_limit))
         # the quotient may round down onto the limit while the Courant number rounds up past it
-        while math.sqrt(self.max_speed2) * (self.T / k) / (min(self.lengths()) / self.N) > self.cfl_limit:
+        while math.sqrt(self._cfl_speed2) * (self.T / k) / (min(self.lengths()) / self.N) > self.cfl_limit:
             k += 1
         return k
 
@@ -177,6 +218,9 @@ class MediumSolver:
                 (an entry may be None: ones; see :func:`sponge_taper`). With G = gx[i] (gy[j] gz[k]) the
                 step becomes ``u = G ((2 u1 - G u2) + m lap u1)``; the source term is not damped in
                 its own step. gx[0] must equal gx[N] (one periodic plane).
+
+    With ``problem.density`` every step, forward, recomputed and adjoint, uses the density operator;
+    the source term stays ``m g`` with ``m = rho c^2 tau^2``, so f is a rate of volume injection.
     """
 
     def __init__(self, problem: MediumProblem, backend: str = "hip", *, u0=None, sources=(), wavelet=None,
@@ -270,8 +314,9 @@ class MediumSolver:
         tr, uf, mx = reference.solve_medium(p.N, p.timesteps, p.speed2, u0=self.u0, sources=self.sources,
                                             wavelet=self.wavelet, receivers=self.receivers,
                                             L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
-                                            taper=self.taper, order=p.space_order)
-        return self._result(tr, uf, mx, (time.perf_counter() - t0) * 1e3, extra=dict(space_order=p.space_order))
+                                            taper=self.taper, order=p.space_order, density=p.density)
+        return self._result(tr, uf, mx, (time.perf_counter() - t0) * 1e3,
+                            extra=dict(space_order=p.space_order, density=p.density is not None))
 
     def _run_hip(self) -> MediumResult:
         from ..ops import kernels, reference
@@ -287,7 +332,11 @@ class MediumSolver:
         with torch.cuda.device(dev):
             lv = [kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev) for _ in range(3)]
             m = kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev)
-            m.copy_(reference.medium_coefficient(p.speed2, c["tau"], N, dt, M))
+            m.copy_(reference.medium_coefficient(p.speed2, c["tau"], N, dt, M, p.density))
+            if p.density is not None:
+                bu = kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev)
+                bu.copy_(reference.buoyancy_field(p.density, N, dt, M))
+                step_kw = dict(step_kw, buoyancy=bu)
             taper = None
             if self.taper is not None:
                 taper = tuple(t.to(dev) for t in reference.taper_tables(self.taper, N, dt, M))
@@ -330,7 +379,7 @@ class MediumSolver:
             ms = ev0.elapsed_time(ev1)
             dec = kernels.decode_err(stat)  # the one read-back of the statistics
             mx = [mx0] + [dec[n][0] for n in range(1, done + 1)]
-            extra = dict(space_order=p.space_order)
+            extra = dict(space_order=p.space_order, density=p.density is not None)
             if not abort and any(d[2] for d in dec[1:]):  # ran to the end, but not on finite values
                 extra["nonfinite_layer"] = next(n for n in range(1, K + 1) if dec[n][2])
             uf = lv[done % 3][M:N + 1 + M].cpu()
@@ -378,10 +427,11 @@ class MediumSolver:
         J, gs, gw, tr = reference.gradient_medium(p.N, p.timesteps, p.speed2, obs, sources=self.sources,
                                                   wavelet=self.wavelet, receivers=self.receivers,
                                                   taper=self.taper, L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi,
-                                                  dtype=p.torch_dtype, order=p.space_order)
+                                                  dtype=p.torch_dtype, order=p.space_order, density=p.density)
         return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr,
                               total_ms=(time.perf_counter() - t0) * 1e3,
-                              extra=dict(segment=None, levels=None, recomputed_steps=0, space_order=p.space_order))
+                              extra=dict(segment=None, levels=None, recomputed_steps=0, space_order=p.space_order,
+                                         density=p.density is not None))
 
     def _gradient_hip(self, obs, segment) -> "MediumGradient":
         import time
@@ -405,7 +455,7 @@ class MediumSolver:
             else:
                 segment = int(segment)
                 what = f"the schedule of segment = {segment}"
-            nlev = gradient_levels(K, segment)
+            nlev = gradient_levels(K, segment, density=p.density is not None)
             if nlev * level_bytes > free:
                 raise RuntimeError(f"gradient(): {what} holds {nlev} levels = {nlev * level_bytes} bytes, but only "
                                    f"{free} bytes of device memory are free")
@@ -422,8 +472,12 @@ class MediumSolver:
             m, acc = level(), level()
             qb = [level() for _ in range(qlen)]
             ck = [(level(), level()) for _ in segs[:-1]]
-            mc = reference.medium_coefficient(p.speed2, c["tau"], N, dt, M)
+            mc = reference.medium_coefficient(p.speed2, c["tau"], N, dt, M, p.density)
             m.copy_(mc)
+            if p.density is not None:
+                bu = level()
+                bu.copy_(reference.buoyancy_field(p.density, N, dt, M))
+                step_kw = dict(step_kw, buoyancy=bu)
             tt = None if self.taper is None else reference.taper_tables(self.taper, N, dt, M)
             taper = None if tt is None else tuple(t.to(dev) for t in tt)
             ent = reference.source_entries(self.sources, N, M)
@@ -498,12 +552,12 @@ class MediumSolver:
             ev[3].record()
             check(astat, "adjoint")
             gs, gw = reference.finish_gradient_medium(acc.cpu(), a_dev.cpu(), gsrc, mc, tt, self.sources, N, c["tau"],
-                                                      c["hx"], c["hy"], c["hz"], M)
+                                                      c["hx"], c["hy"], c["hz"], M, p.density)
             torch.cuda.synchronize(dev)
             ms = (time.perf_counter() - t0) * 1e3
             return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr, total_ms=ms,
                                   extra=dict(segment=segment, levels=nlev, recomputed_steps=recomputed,
-                                             space_order=p.space_order,
+                                             space_order=p.space_order, density=p.density is not None,
                                              forward_ms=ev[0].elapsed_time(ev[1]), reverse_ms=ev[2].elapsed_time(ev[3])))
 
 
@@ -518,16 +572,17 @@ class MediumGradient:
     extra: dict = field(default_factory=dict)
 
 
-def gradient_levels(K: int, segment: int) -> int:
+def gradient_levels(K: int, segment: int, density: bool = False) -> int:
     """Number of grid levels the "hip" schedule of :meth:`MediumSolver.gradient` holds for K
     timesteps cut into segments of ``segment`` steps (steps 2..K): the forward ring (3), m, acc, the
     q buffer (one level per step of a segment), a checkpoint pair per segment but the last, and,
-    when there is anything to recompute, a second ring for the adjoint field."""
+    when there is anything to recompute, a second ring for the adjoint field. ``density``: one more
+    level, the buoyancy of a problem with a density model."""
     K, segment = int(K), int(segment)
     if K < 1 or segment < 1:
         raise ValueError(f"need K >= 1 and segment >= 1, not K={K} segment={segment}")
     nseg = -(-(K - 1) // segment)
-    return 5 + min(segment, K - 1) + (2 * (nseg - 1) + 3 if nseg > 1 else 0)
+    return 5 + bool(density) + min(segment, K - 1) + (2 * (nseg - 1) + 3 if nseg > 1 else 0)
 
 
 def best_gradient_segment(K: int) -> int:

@@ -355,7 +355,7 @@ def _check_taper(taper, u) -> list[int]:
 
 def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None, chunk: int = 0,
                 variant: str | None = None, taper=None, lap_out=None, image=None, order: int = 2,
-                mirror=None) -> None:
+                mirror=None, buoyancy=None) -> None:
     """One layer of ``u_tt = c^2 (lap u + f)`` over ``boxes``: ``u = (2 u1 - u2) + m lap(u1)``, on
     the Taylor start (``first``) ``u = u1 + (0.5 m) lap(u1)``, with ``m = c^2 tau^2`` per node.
 
@@ -388,12 +388,27 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     itself as stored. The boxes lie strictly inside their faces, a pair of faces is at least M
     apart, every reflected node exists in storage, and on a side without a face the boxes keep M
     nodes from the storage edge.
+
+    ``buoyancy``: a grid ``b = 1 / rho`` (variable density, ``k_march_mb``): ``lap(u1)`` becomes
+    ``div(b grad u1)`` (``ops.reference.laplace_density`` has the scheme) in every form above, the
+    sponge and both modes included (``lap_out`` then receives that value), and ``m = rho c^2 tau^2``. It
+    matches ``u`` in shape, dtype, device and strides, its ghost planes filled like those of ``u1``;
+    it is read at the box nodes and their six neighbours and never written. For ``order`` 2 and the
+    default variant only (``ValueError`` before any launch otherwise).
     """
     if order not in (2, 4, 8):
         raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
     if order != 2 and variant is not None:
         raise ValueError("the ablation variants exist for order 2 only")
     extra = []
+    if buoyancy is not None:
+        if order != 2:
+            raise ValueError(f"variable density (buoyancy) exists for space order 2 only, not {order!r}")
+        if variant not in (None, "nt"):
+            raise ValueError(f"variable density (buoyancy) exists for the default variant only, not {variant!r}")
+        if not isinstance(buoyancy, torch.Tensor):
+            raise ValueError("buoyancy must be a tensor")
+        variant = "nt"
     if lap_out is not None or image is not None:
         if lap_out is not None and image is not None:
             raise ValueError("save mode (lap_out) and image mode (image) cannot be combined")
@@ -411,6 +426,8 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
             extra = [lap_out]
         if not all(isinstance(t, torch.Tensor) for t in extra):
             raise ValueError("lap_out, q and acc must be tensors")
+    if buoyancy is not None:
+        extra = extra + [buoyancy]
     gv = _check_grid_strided(u1, u2, m, u, *extra)
     if isinstance(boxes[0], int):
         boxes = [boxes]
@@ -436,7 +453,8 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     fn(bool(first), u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, bl, int(stat_i[0]),
        int(stat_i[1]), w, [float(v) for v in h2], stat.data_ptr(), int(chunk), _stream(),
        _MEDIUM_VARIANTS[variant], *gp, lap_out.data_ptr() if lap_out is not None else 0,
-       *((image[0].data_ptr(), image[1].data_ptr()) if image is not None else (0, 0)), int(order), mir)
+       *((image[0].data_ptr(), image[1].data_ptr()) if image is not None else (0, 0)), int(order), mir,
+       buoyancy.data_ptr() if buoyancy is not None else 0)
 
 
 def inject(u, m, nodes, g, wrap=None) -> None:

@@ -270,9 +270,39 @@ def laplace_star(u, box, hx2, hy2, hz2, *, order: int, mirror=None) -> torch.Ten
     return ans
 
 
-def _lap_box(u1, box, hx2, hy2, hz2, order: int, mirror):
+def laplace_density(u: torch.Tensor, b: torch.Tensor, hx2, hy2, hz2) -> torch.Tensor:
+    """Variable-density operator ``D_b u = div(b grad u)`` on all interior nodes ``u[1:-1, 1:-1, 1:-1]``,
+    with the node-centred buoyancy ``b = 1 / rho`` (a grid like ``u``). A face value is the arithmetic
+    mean of the two adjacent nodes' buoyancies (the harmonic mean of the densities). Per axis, with
+    centre c, neighbours u_-, u_+ and buoyancies b_c, b_-, b_+:
+    ``f_+ = (0.5 (b_c + b_+)) (u_+ - c)``, ``f_- = (0.5 (b_c + b_-)) (c - u_-)``, ``t = f_+ - f_-``,
+    and ``D_b u = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2``, every operation rounded on its own.
+    The operator is symmetric on the unique nodes; ``b == 1`` gives the 7-point Laplacian up to
+    rounding."""
+    if b.shape != u.shape or b.dtype != u.dtype:
+        raise ValueError(f"buoyancy must match the grid: {tuple(u.shape)} {u.dtype}, not {tuple(b.shape)} {b.dtype}")
+    inner = slice(1, -1)
+    c = u[inner, inner, inner]
+    bc = b[inner, inner, inner]
+    ans = torch.zeros_like(c)
+    for axis, h2 in enumerate((hx2, hy2, hz2)):
+        lo, hi = [inner] * 3, [inner] * 3
+        lo[axis], hi[axis] = slice(None, -2), slice(2, None)
+        lo, hi = tuple(lo), tuple(hi)
+        fp = (0.5 * (bc + b[hi])) * (u[hi] - c)
+        fm = (0.5 * (bc + b[lo])) * (c - u[lo])
+        ans = ans + (fp - fm) / h2
+    return ans
+
+
+def _lap_box(u1, box, hx2, hy2, hz2, order: int, mirror, buoyancy=None):
     """lap(u1) on the nodes of ``box``: order 2 is ``laplace7`` (today's operations), 4 and 8
-    ``laplace_star``."""
+    ``laplace_star``; with ``buoyancy`` (order 2 only) ``laplace_density``."""
+    if buoyancy is not None:
+        if order != 2:
+            raise ValueError(f"variable density exists for space order 2 only, not {order!r}")
+        i0, i1, j0, j1, k0, k1 = box
+        return laplace_density(u1, buoyancy, hx2, hy2, hz2)[i0 - 1:i1, j0 - 1:j1, k0 - 1:k1]
     if order == 2:
         i0, i1, j0, j1, k0, k1 = box
         return laplace7(u1, hx2, hy2, hz2)[i0 - 1:i1, j0 - 1:j1, k0 - 1:k1]
@@ -280,12 +310,15 @@ def _lap_box(u1, box, hx2, hy2, hz2, order: int, mirror):
 
 
 def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None, order: int = 2,
-                mirror=None) -> torch.Tensor:
+                mirror=None, buoyancy=None) -> torch.Tensor:
     """Layer update on ``box`` with the per-node coefficient ``m = c^2 tau^2``: the Taylor start
     ``c + (0.5 m) lap`` or ``(2c - u2) + m lap``; returns the updated box values.
 
     order = 2: the 7-point Laplacian (``mirror`` is not used); 4 or 8: ``laplace_star`` with its box
     and ``mirror`` contract.
+
+    buoyancy: a grid ``b = 1 / rho`` like ``u1`` (order 2 only): ``laplace_density`` takes the place of
+    the Laplacian in every form below, and ``m = rho c^2 tau^2``. None: today's operations.
 
     taper = (gx, gy, gz), 1-D factors in (0, 1] per axis in storage indexing (the lengths of the
     grid's axes): the damped leapfrog of an absorbing sponge with ``G = gx (gy gz)`` per node,
@@ -293,7 +326,7 @@ def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None, order
     if order not in STAR_WEIGHTS:
         raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
     i0, i1, j0, j1, k0, k1 = box
-    lap = _lap_box(u1, box, hx2, hy2, hz2, order, mirror)
+    lap = _lap_box(u1, box, hx2, hy2, hz2, order, mirror, buoyancy)
     c = u1[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
     mb = m[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
     if taper is None:
@@ -324,18 +357,46 @@ def _wrap_x(u, N: int, ghost: int = 1) -> None:
         u[N + ghost + g] = u[ghost + g]
 
 
-def medium_coefficient(speed2, tau: float, N: int, dtype, ghost: int = 1) -> torch.Tensor:
-    """m = ((speed2 * tau) * tau), left to right in float64, then cast: ``[N+1+2 ghost][N+1][N+1]``
-    in ``solve()``'s storage with ``ghost`` x ghost planes per side, filled periodically."""
-    s = torch.as_tensor(speed2, dtype=torch.float64)
+def _node_field(v, N: int, name: str) -> torch.Tensor:
+    s = torch.as_tensor(v, dtype=torch.float64)
     if s.dim() == 0:
         s = s.expand(N + 1, N + 1, N + 1)
     if tuple(s.shape) != (N + 1, N + 1, N + 1):
-        raise ValueError(f"speed2 must be a scalar or have shape {(N + 1,) * 3}, not {tuple(s.shape)}")
+        raise ValueError(f"{name} must be a scalar or have shape {(N + 1,) * 3}, not {tuple(s.shape)}")
+    return s
+
+
+def medium_coefficient(speed2, tau: float, N: int, dtype, ghost: int = 1, density=None) -> torch.Tensor:
+    """m = ((speed2 * tau) * tau), left to right in float64, then cast: ``[N+1+2 ghost][N+1][N+1]``
+    in ``solve()``'s storage with ``ghost`` x ghost planes per side, filled periodically. With
+    ``density`` (a scalar or ``(N+1)^3``): m = (((speed2 * rho) * tau) * tau), the bulk modulus
+    ``rho c^2`` times ``tau^2``."""
+    s = _node_field(speed2, N, "speed2")
+    if density is not None:
+        s = s * _node_field(density, N, "density")
     m = torch.zeros(N + 1 + 2 * ghost, N + 1, N + 1, dtype=dtype)
     m[ghost:N + 1 + ghost] = ((s * tau) * tau).to(dtype)
     _wrap_x(m, N, ghost)
     return m
+
+
+def buoyancy_field(density, N: int, dtype, ghost: int = 1) -> torch.Tensor:
+    """b = 1 / rho in float64, then cast, for ``density`` a scalar or ``(N+1)^3``: stored like
+    ``medium_coefficient`` with the x ghost planes filled periodically."""
+    r = _node_field(density, N, "density")
+    b = torch.zeros(N + 1 + 2 * ghost, N + 1, N + 1, dtype=dtype)
+    b[ghost:N + 1 + ghost] = (1.0 / r).to(dtype)
+    _wrap_x(b, N, ghost)
+    return b
+
+
+def _buoyancy(density, N: int, dtype, order: int, ghost: int):
+    """The buoyancy grid of ``density`` for the medium solver, None without one."""
+    if density is None:
+        return None
+    if order != 2:
+        raise ValueError(f"variable density exists for space order 2 only, not {order!r}")
+    return buoyancy_field(density, N, dtype, ghost)
 
 
 def source_table(wavelet, K: int, S: int, hx: float, hy: float, hz: float, dtype) -> torch.Tensor:
@@ -383,7 +444,7 @@ def taper_tables(taper, N: int, dtype, ghost: int = 1) -> tuple[torch.Tensor, to
 
 def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, receivers=(),
                  L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, device="cpu",
-                 taper=None, order: int = 2):
+                 taper=None, order: int = 2, density=None):
     """Whole single-domain solve of ``(1/c^2) u_tt = lap u + f`` from rest in PyTorch, in
     ``solve()``'s storage (x ghosts, local = global + 1).
 
@@ -400,12 +461,19 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
     taper = (gx, gy, gz): sponge factors per axis, ``N+1`` values each in global indexing
     (``taper_tables``); every step is then the damped one of ``step_medium`` (the source term is
     not tapered in its own step). None: the undamped scheme.
+
+    density: rho, a scalar or ``(N+1)^3`` (order 2 only): ``(1/kappa) u_tt = div(b grad u) + f`` with
+    ``kappa = rho c^2`` and ``b = 1 / rho``; m becomes ``kappa tau^2`` (``medium_coefficient``) and every
+    step uses ``laplace_density``. None: the constant-density operations, unchanged.
     """
     c = tables(N, K, L, T, pi)[4]
     M, box, mirror = _medium_layout(N, order)
     if taper is not None:
         taper = tuple(t.to(device) for t in taper_tables(taper, N, dtype, M))
-    m = medium_coefficient(speed2, c["tau"], N, dtype, M).to(device)
+    m = medium_coefficient(speed2, c["tau"], N, dtype, M, density).to(device)
+    bu = _buoyancy(density, N, dtype, order, M)
+    if bu is not None:
+        bu = bu.to(device)
     ent = source_entries(sources, N, M)
     g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype).to(device)
     lv = [torch.zeros(N + 1 + 2 * M, N + 1, N + 1, dtype=dtype, device=device) for _ in range(3)]
@@ -432,7 +500,7 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
         u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
         u.zero_()
         vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=taper,
-                           order=order, mirror=mirror)
+                           order=order, mirror=mirror, buoyancy=bu)
         mx.append(max_abs_field(vals))
         u[M:N + 1 + M, 1:N, 1:N] = vals
         for nd, s in ent:
@@ -481,17 +549,19 @@ def taper_at(tt, node):
 
 def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None, receivers=(), taper=None,
                             L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
-                            keep_lap: bool = False, order: int = 2):
+                            keep_lap: bool = False, order: int = 2, density=None):
     """``solve_medium`` from rest, restated out of place: every level is a new tensor, so
     ``torch.autograd`` can differentiate the traces with respect to ``speed2`` (an ``(N+1)^3``
     tensor) and ``wavelet``. The operations and their order are those of ``solve_medium``: the traces
     ``[K+1, R]`` are equal bit for bit. ``keep_lap``: also return [q^1 .. q^{K-1}], q^n = lap u^n on
-    the stencil nodes (the value step n+1 uses)."""
+    the stencil nodes (the value step n+1 uses). ``density``: as in ``solve_medium`` (held fixed; q^n is
+    then ``laplace_density`` of u^n)."""
     c = tables(N, K, L, T, pi)[4]
     M, box, mirror = _medium_layout(N, order)
     shape = (N + 1 + 2 * M, N + 1, N + 1)
     tt = None if taper is None else taper_tables(taper, N, dtype, M)
-    m = medium_coefficient(speed2, c["tau"], N, dtype, M)
+    m = medium_coefficient(speed2, c["tau"], N, dtype, M, density)
+    bu = _buoyancy(density, N, dtype, order, M)
     ent = source_entries(sources, N, M)
     g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
     rec = [(i + M, j, k) for i, j, k in receivers]
@@ -501,9 +571,9 @@ def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None,
     laps = []
     for n in range(1, K + 1):
         if keep_lap and n >= 2:
-            laps.append(_lap_box(u1, box, c["hx2"], c["hy2"], c["hz2"], order, mirror))
+            laps.append(_lap_box(u1, box, c["hx2"], c["hy2"], c["hz2"], order, mirror, bu))
         vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt,
-                           order=order, mirror=mirror)
+                           order=order, mirror=mirror, buoyancy=bu)
         u = torch.zeros(shape, dtype=dtype)
         u[M:N + 1 + M, 1:N, 1:N] = vals
         for nd, s in ent:
@@ -556,11 +626,13 @@ def source_unique_nodes(sources, N: int, ghost: int = 1):
 
 
 def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: float, hy: float, hz: float,
-                           ghost: int = 1):
+                           ghost: int = 1, density=None):
     """The host-side end of the gradient. acc ``[N+1+2 ghost][N+1][N+1]`` = sum mu^{n+1} q^n in storage
     (faces 0), a ``[K, S]`` with ``a[n, s] = mu^{n+1}[x_s]``, g = the ``source_table``, m = the
     ``medium_coefficient``, all CPU tensors of the working dtype. Returns (dJ/dspeed2 ``(N+1)^3``
-    with respect to the unique nodes: plane N a copy of plane 0, faces 0; dJ/dwavelet ``[K, S]``)."""
+    with respect to the unique nodes: plane N a copy of plane 0, faces 0; dJ/dwavelet ``[K, S]``).
+    ``density`` (a scalar or ``(N+1)^3``): m = rho speed2 tau^2, so the gradient is multiplied by rho as
+    its last arithmetic operation: dJ/dspeed2 at fixed rho."""
     gm = acc[ghost:N + 1 + ghost] / m[ghost:N + 1 + ghost]
     nodes = source_unique_nodes(sources, N, ghost)
     if nodes:
@@ -569,6 +641,8 @@ def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: fl
             at = (nd[0] - ghost, nd[1], nd[2])
             gm[at] = gm[at] + dots[s] / (m[nd] * taper_at(tt, nd))
     grad = (gm * tau) * tau  # m = (speed2 tau) tau
+    if density is not None:
+        grad = grad * _node_field(density, N, "density").to(grad.dtype)
     grad[N] = grad[0]
     grad[:, 0, :] = 0
     grad[:, N, :] = 0
@@ -583,7 +657,8 @@ def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: fl
 
 
 def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,
-                    L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, order: int = 2):
+                    L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, order: int = 2,
+                    density=None):
     """Misfit J of the traces against ``observed`` ``[K+1, R]`` (row 0 ignored) and its gradients by
     the hand-written adjoint above: (J, dJ/dspeed2 ``(N+1)^3``, dJ/dwavelet ``[K, S]``, traces).
 
@@ -595,16 +670,21 @@ def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=Non
     ``(grad[:N] * d[:N]).sum()``.
 
     order: the space order of ``solve_medium``; the star Laplacian with periodic wrap and odd
-    reflection is symmetric on the unique nodes, so the adjoint recurrence keeps its form."""
+    reflection is symmetric on the unique nodes, so the adjoint recurrence keeps its form.
+
+    density: rho of ``solve_medium`` (order 2), held fixed: ``laplace_density`` is symmetric on the
+    unique nodes too, so the adjoint field runs on the same density step, and dJ/dspeed2 is the
+    derivative at fixed rho (``finish_gradient_medium``). dJ/drho is not computed."""
     with torch.no_grad():
         traces, laps = forward_medium_autograd(N, K, speed2, sources=sources, wavelet=wavelet,
                                                receivers=receivers, taper=taper, L=L, T=T, pi=pi, dtype=dtype,
-                                               keep_lap=True, order=order)
+                                               keep_lap=True, order=order, density=density)
         J, res = misfit_medium(traces, observed)
         c = tables(N, K, L, T, pi)[4]
         M, box, mirror = _medium_layout(N, order)
         tt = None if taper is None else taper_tables(taper, N, dtype, M)
-        m = medium_coefficient(speed2, c["tau"], N, dtype, M)
+        m = medium_coefficient(speed2, c["tau"], N, dtype, M, density)
+        bu = _buoyancy(density, N, dtype, order, M)
         g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
         anodes, atab = adjoint_source_table(res, receivers, N, tt, M)
         snodes = source_unique_nodes(sources, N, M)
@@ -625,11 +705,12 @@ def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=Non
         acc = torch.zeros(shape, dtype=dtype)
         for n in range(K - 1, 0, -1):
             vals = step_medium(mu1, mu2, m, box, first=False, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt,
-                               order=order, mirror=mirror)
+                               order=order, mirror=mirror, buoyancy=bu)
             acc[own] = acc[own] + mu1[own] * laps[n - 1]
             mu = torch.zeros(shape, dtype=dtype)
             mu[own] = vals
             finish_level(mu, n)
             mu2, mu1 = mu1, mu
-        grad, gw = finish_gradient_medium(acc, a, g, m, tt, sources, N, c["tau"], c["hx"], c["hy"], c["hz"], M)
+        grad, gw = finish_gradient_medium(acc, a, g, m, tt, sources, N, c["tau"], c["hx"], c["hy"], c["hz"], M,
+                                          density)
         return J, grad, gw, traces

@@ -3,9 +3,9 @@
 
     python tools/bench_medium.py [--N 512] [--steps 100] [--dtypes fp64,fp32]
                                  [--variants default,plain,r2,r2nt] [--repeat 3] [--no-yardstick]
-                                 [--taper WIDTH] [--order 2,4,8]
+                                 [--taper WIDTH] [--order 2,4,8] [--density]
     python tools/bench_medium.py --gradient [--N 512] [--steps 100] [--dtypes fp64,fp32] [--segment 10]
-                                 [--order 2,8] [--kernels-only]
+                                 [--order 2,8] [--kernels-only] [--density]
 
 For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
 and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
@@ -30,6 +30,14 @@ of its time to order 2's (`vs_order2`, when 2 is among the orders). The byte cou
 not depend on the order; the speed keeps the Courant number at 0.9 of the smallest limit among
 the orders. The ablation variants exist for order 2 only. With `--gradient` the kernel rounds and
 the schedules run at each order; `--kernels-only` skips the schedules.
+
+`--density` (order 2 must be among the orders) adds the variable-density step (k_march_mb) with a
+two-layer rho (1 above, 2 below the plane k = N / 2), alternating with the constant-density step
+inside each repeat. It reads one more stream, the buoyancy: 40 B per node in fp64 (20 B in fp32)
+against 32 (16), so the byte count predicts 1.25 times the constant-density time (`vs_constant`
+beside `expected_ratio`); with `--gradient` 48 B (save) and 64 B (image) against 40 and 56. The speed
+is lowered by the factor 1.5 that the two-layer interface adds to the Courant number's
+max kappa bhat. Works with `--taper` and `--gradient --kernels-only`.
 """
 import argparse
 import json
@@ -55,6 +63,15 @@ def smooth_speed2(N: int, lo: float, hi: float, seed: int = 7):
     return s.contiguous()
 
 
+def two_layer_density(N: int):
+    """rho = 1 above and 2 below the plane k = N / 2."""
+    import torch
+
+    rho = torch.ones((N + 1,) * 3, dtype=torch.float64)
+    rho[:, :, N // 2:] = 2.0
+    return rho
+
+
 def gradient_bench(a) -> int:
     import math
 
@@ -66,15 +83,22 @@ def gradient_bench(a) -> int:
     N, K = a.N, a.steps
     h = 3.1415926535 / N
     orders = [int(v) for v in a.order.split(",")]
-    hi = (0.9 * min(wave3d.cfl_limit(o) for o in orders) * h * K) ** 2
+    hi = (0.9 * min(wave3d.cfl_limit(o) for o in orders) * h * K) ** 2 / (1.5 if a.density else 1.0)
     speed2 = smooth_speed2(N, 0.5 * hi, hi)
+    rho = two_layer_density(N) if a.density else None
     nodes = float(N + 1) ** 3
     out = {"N": N, "steps": K, "orders": orders, "device": torch.cuda.get_device_name(0), "kernels": [],
            "gradient": []}
+    if a.density:
+        out["density"] = "two layers: 1, 2"
+        if not a.kernels_only:
+            raise SystemExit("--gradient --density: the kernel rounds only (add --kernels-only)")
+        orders = orders + ["2d"]  # the density step at order 2, a configuration of its own
     dev = torch.device("cuda", 0)
     for dtype in a.dtypes.split(","):
         es = 8 if dtype == "fp64" else 4
-        probs = {o: wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype, space_order=o) for o in orders}
+        probs = {o: wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype, space_order=o) for o in orders
+                 if o != "2d"}
         dt = probs[orders[0]].torch_dtype
         c = reference.tables(N, K)[4]
         h2 = (c["hx2"], c["hy2"], c["hz2"])
@@ -85,17 +109,20 @@ def gradient_bench(a) -> int:
         seed = torch.rand(N + 1, N + 1, generator=g, dtype=torch.float64).to(dt).to(dev)
         sets = {}
         for o in orders:
-            M = o // 2
+            M = 1 if o == "2d" else o // 2
             lv = [kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev) for _ in range(6)]
-            lv[2].copy_(reference.medium_coefficient(speed2, c["tau"], N, dt, M))
+            lv[2].copy_(reference.medium_coefficient(speed2, c["tau"], N, dt, M, rho if o == "2d" else None))
             for t in (lv[0], lv[1], lv[5]):
                 t[:, 1:N, 1:N] = seed[1:N, 1:N]
             wrap = []
             for gh in range(1, M + 1):
                 wrap += [N + M - gh, M - gh, M + gh, N + M + gh]
             sets[o] = dict(lv=lv, box=(M, N + M, 1, N - 1, 1, N - 1), wrap=wrap, stat_i=(M, N + M),
-                           kw={} if o == 2 else dict(order=o, mirror=(0, N, 0, N)),
+                           kw={} if o in (2, "2d") else dict(order=o, mirror=(0, N, 0, N)),
                            taper=tuple(t.to(dev) for t in reference.taper_tables(sponge, N, dt, M)))
+            if o == "2d":
+                sets[o]["kw"] = dict(buoyancy=kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev))
+                sets[o]["kw"]["buoyancy"].copy_(reference.buoyancy_field(rho, N, dt))
         stat = kernels.new_err(1, device=dev)
         reps = 20
         for tp_name in ("", "sponge"):
@@ -121,12 +148,18 @@ def gradient_bench(a) -> int:
             for o in orders:
                 for name, bpn in (("plain", 4), ("save", 5), ("image", 7)):
                     best = min(ms[(name, o)])
-                    row = {"dtype": dtype, "order": o, "mode": name, "sponge": bool(tp_name),
+                    if o == "2d":
+                        bpn += 1  # the buoyancy stream
+                    row = {"dtype": dtype, "order": 2 if o == "2d" else o, "mode": name, "sponge": bool(tp_name),
                            "ms_per_step": round(best, 4), "all_ms": [round(v, 4) for v in ms[(name, o)]],
-                           "bytes_per_node": bpn * es, "expected_ratio": bpn / 4,
+                           "bytes_per_node": bpn * es, "expected_ratio": bpn / (5 if o == "2d" else 4),
                            "ratio_to_plain": round(best / min(ms[("plain", o)]), 4),
                            "eff_tb_per_s": round(bpn * es * nodes / (best * 1e-3) / 1e12, 3)}
-                    if 2 in orders:
+                    if o == "2d":
+                        row["density"] = True
+                        row["vs_constant"] = round(best / min(ms[(name, 2)]), 4)
+                        row["expected_vs_constant"] = round(bpn / (bpn - 1), 4)
+                    elif 2 in orders:
                         row["vs_order2"] = round(best / min(ms[(name, 2)]), 4)
                     out["kernels"].append(row)
                     print(f"bench_medium: {dtype} order {o} {name} {tp_name}: {best:.4f} ms/step", file=sys.stderr,
@@ -189,6 +222,8 @@ def main(argv=None) -> int:
     ap.add_argument("--segment", type=int, default=10, help="--gradient: steps per checkpoint segment")
     ap.add_argument("--order", default="2", help="space orders to time, e.g. 2,4,8 (alternating inside each repeat)")
     ap.add_argument("--kernels-only", action="store_true", help="--gradient: the kernel rounds without the schedules")
+    ap.add_argument("--density", action="store_true",
+                    help="also time the variable-density step (two-layer rho), alternating with the constant-density one")
     a = ap.parse_args(argv)
 
     import math
@@ -204,33 +239,40 @@ def main(argv=None) -> int:
     orders = [int(v) for v in a.order.split(",")]
     if not orders or any(o not in (2, 4, 8) for o in orders):
         ap.error("--order: a comma-separated list of 2, 4, 8")
+    if a.density and 2 not in orders:
+        ap.error("--density: order 2 must be among the orders")
     if a.gradient:
         return gradient_bench(a)
     variants = a.variants.split(",")
     # speed2 <= hi keeps the Courant number at 0.9 of the limit for T = 1 (order 2: 1/sqrt(3); the
     # smallest limit among the orders)
     h = 3.1415926535 / N
-    hi = (0.9 * min(wave3d.cfl_limit(o) for o in orders) * h * K) ** 2
+    # (--density: the two-layer interface raises max kappa bhat by the factor 1.5)
+    hi = (0.9 * min(wave3d.cfl_limit(o) for o in orders) * h * K) ** 2 / (1.5 if a.density else 1.0)
     speed2 = smooth_speed2(N, 0.5 * hi, hi)
+    rho = two_layer_density(N) if a.density else None
     nodes = float(N + 1) ** 3
     out = {"N": N, "steps": K, "orders": orders, "device": torch.cuda.get_device_name(0), "runs": []}
     for dtype in a.dtypes.split(","):
         es = 8 if dtype == "fp64" else 4
         probs = {o: wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype, space_order=o) for o in orders}
         prob = probs[orders[0]]
+        dprob = wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype, density=rho) if a.density else None
         w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
         mid = N // 2
 
         sponge = wave3d.sponge_taper(prob, a.taper) if a.taper > 0 else None
 
-        def solver(v, tapered, order):
-            return wave3d.MediumSolver(probs[order], "hip", sources=[(mid, mid, mid)], wavelet=w,
+        def solver(v, tapered, order, dens=False):
+            return wave3d.MediumSolver(dprob if dens else probs[order], "hip", sources=[(mid, mid, mid)], wavelet=w,
                                        receivers=[(mid // 2, mid, mid)], variant=None if v == "default" else v,
                                        taper=sponge if tapered else None)
 
         # the ablation variants are k_march_m's: order 2 only
-        cfgs = [(v, t, o) for v in variants for t in ((False, True) if sponge is not None else (False,))
+        cfgs = [(v, t, o, False) for v in variants for t in ((False, True) if sponge is not None else (False,))
                 for o in orders if o == 2 or v == "default"]
+        # the density step follows its constant-density counterpart inside each repeat
+        cfgs = [d for c in cfgs for d in ((c, c[:3] + (True,)) if a.density and c[2] == 2 and c[0] == "default" else (c,))]
         ms = {c: [] for c in cfgs}
         for c in cfgs:
             solver(*c).run()  # warm-up
@@ -239,20 +281,26 @@ def main(argv=None) -> int:
                 r = solver(*c).run()
                 assert not r.aborted and math.isfinite(max(r.max_abs_u)), "the benchmark run diverged"
                 ms[c].append(r.total_ms)
-                print(f"bench_medium: {dtype} order {c[2]} {c[0]}{' taper' if c[1] else ''}: {r.total_ms:.2f} ms",
+                print(f"bench_medium: {dtype} order {c[2]} {c[0]}{' taper' if c[1] else ''}{' density' if c[3] else ''}: "
+                      f"{r.total_ms:.2f} ms",
                       file=sys.stderr, flush=True)
         for c in cfgs:
             best = min(ms[c])
-            row = {"kernel": "k_march_m" if c[2] == 2 else "k_march_mh", "order": c[2], "variant": c[0],
-                   "dtype": dtype, "courant": round(prob.courant, 4),
+            bpn = 5 if c[3] else 4
+            row = {"kernel": "k_march_mb" if c[3] else "k_march_m" if c[2] == 2 else "k_march_mh", "order": c[2],
+                   "variant": c[0], "dtype": dtype, "courant": round((dprob if c[3] else prob).courant, 4),
                    "loop_ms": [round(t, 3) for t in ms[c]], "ms_per_step": round(best / K, 4),
-                   "mpts_per_s": round(nodes * K / best / 1e3, 1), "bytes_per_node": 4 * es,
-                   "eff_tb_per_s": round(4 * es * nodes * K / (best * 1e-3) / 1e12, 3)}
+                   "mpts_per_s": round(nodes * K / best / 1e3, 1), "bytes_per_node": bpn * es,
+                   "eff_tb_per_s": round(bpn * es * nodes * K / (best * 1e-3) / 1e12, 3)}
             if c[1]:
                 row["taper"] = a.taper
-                row["vs_untapered"] = round(best / min(ms[(c[0], False, c[2])]), 4)
-            if (c[0], c[1], 2) in ms:
-                row["vs_order2"] = round(best / min(ms[(c[0], c[1], 2)]), 4)
+                row["vs_untapered"] = round(best / min(ms[(c[0], False, c[2], c[3])]), 4)
+            if c[3]:
+                row["density"] = True
+                row["vs_constant"] = round(best / min(ms[c[:3] + (False,)]), 4)
+                row["expected_vs_constant"] = 1.25
+            elif (c[0], c[1], 2, False) in ms:
+                row["vs_order2"] = round(best / min(ms[(c[0], c[1], 2, False)]), 4)
             out["runs"].append(row)
         if not a.no_yardstick:
             yp = wave3d.WaveProblem(N, timesteps=K, dtype=dtype)
@@ -262,7 +310,7 @@ def main(argv=None) -> int:
                                 "solve_ms": [round(t, 3) for t in r.solve_ms],
                                 "ms_per_step": round(nodes / mp / 1e3, 4), "mpts_per_s": round(mp, 1),
                                 "bytes_per_node": 3 * es, "eff_tb_per_s": round(3 * es * mp * 1e6 / 1e12, 3)})
-    for d in (x for x in out["runs"] if x["kernel"] in ("k_march_m", "k_march_mh")):
+    for d in (x for x in out["runs"] if x["kernel"] in ("k_march_m", "k_march_mh", "k_march_mb")):
         y = [x for x in out["runs"] if x["kernel"] == "k_march" and x["dtype"] == d["dtype"]]
         if y:
             d["bw_vs_k_march"] = round(d["eff_tb_per_s"] / y[0]["eff_tb_per_s"], 3)
