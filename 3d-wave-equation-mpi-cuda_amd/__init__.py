@@ -25,7 +25,7 @@ def __getattr__(name):
 
         return getattr(wave, name)
     if name in ("MediumProblem", "MediumSolver", "MediumResult", "MediumGradient", "ricker", "sponge_taper",
-                "gradient_levels", "cfl_limit"):
+                "gradient_levels", "best_gradient_segment", "cfl_limit"):
         from .models import medium
 
         return getattr(medium, name)

@@ -348,6 +348,19 @@ void k_step_medium(bool first, uintptr_t u1, uintptr_t u2, uintptr_t m, uintptr_
                           P<T>(b));
 }
 
+// Face correlation (k_face_corr): acc = acc + C(a, v) at the box nodes; grid view as above
+template <class T>
+void k_face_corr(uintptr_t a, uintptr_t v, uintptr_t acc, const std::vector<i64>& g,
+                 const std::vector<std::vector<int>>& boxes, const std::vector<double>& h2, int chunk,
+                 uintptr_t stream) {
+    std::vector<Box> bx;
+    for (auto& e : boxes) bx.push_back(tobox(e));
+    W3D_REQUIRE(h2.size() == 3, "h2 = (hx2, hy2, hz2)");
+    const double h[3] = {h2[0], h2[1], h2[2]};
+    launch_face_corr<T>(P<T>(a), P<T>(v), P<T>(acc), gview(g), bx.data(), int(bx.size()), h, chunk,
+                        (hipStream_t)stream);
+}
+
 // nodes: device int32 [n][3] of (i, j, k); g / out: n device values
 template <class T>
 void k_inject(uintptr_t u, uintptr_t m, const std::vector<i64>& g, uintptr_t nodes, uintptr_t vals, int n,
@@ -574,6 +587,8 @@ PYBIND11_MODULE(_wave3d_C, m) {
     m.def("k_step_medium_f64", &k_step_medium<double>, W3D_STEP_MEDIUM_ARGS);
     m.def("k_step_medium_f32", &k_step_medium<float>, W3D_STEP_MEDIUM_ARGS);
 #undef W3D_STEP_MEDIUM_ARGS
+    m.def("k_face_corr_f64", &k_face_corr<double>);
+    m.def("k_face_corr_f32", &k_face_corr<float>);
     m.def("k_inject_f64", &k_inject<double>);
     m.def("k_inject_f32", &k_inject<float>);
     m.def("k_record_f64", &k_record<double>);

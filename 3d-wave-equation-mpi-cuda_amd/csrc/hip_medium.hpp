@@ -75,6 +75,21 @@ void launch_inject(T* u, const T* m, const GridView& gv, const int* nodes, const
 template <class T>
 void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int n, hipStream_t s);
 
+// Face correlation (hip_medium_corr.hip, k_face_corr): acc = acc + C(a, v) at the nodes of `nbox`
+// boxes, the accumulation behind the density gradient dJ/drho of the adjoint pass (a = mu^{n+1},
+// v = u^n). Per axis, with centre values a_c, v_c and neighbours a_-, a_+, v_-, v_+:
+// p_+ = (a_+ - a_c) (v_+ - v_c), p_- = (a_c - a_-) (v_c - v_-), t = p_+ + p_-, and
+// C = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2, every operation rounded on its own, the divisions
+// correctly rounded (ops/reference.py face_correlation); C(a, v) == C(v, a) bit for bit. a, v and
+// acc are levels with the strides of `gv` (one ghost layer, x ghost planes of a and v filled); the
+// box contract is k_march_m's: boxes inside the owned region, so every box node has its six
+// neighbours in storage. a and v are never written and acc only at the box nodes. Rejected before
+// the launch: a box that touches a storage edge, strides smaller than the grid, and an acc that
+// shares memory with a or v. Per node in fp64: 32 B (a, v, acc read and written), 16 B in fp32.
+template <class T>
+void launch_face_corr(const T* a, const T* v, T* acc, const GridView& gv, const Box* boxes, int nbox,
+                      const double h2[3], int chunk, hipStream_t s);
+
 // default variant of launch_step_medium: 1 ("nt"), or env WAVE3D_MEDIUM_VARIANT = "plain" (0),
 // "r2" (2), "r2nt" (3) for ablation
 int medium_variant();

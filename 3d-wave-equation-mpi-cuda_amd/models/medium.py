@@ -387,7 +387,7 @@ class MediumSolver:
 
     # ---- misfit gradients (adjoint state; ops/reference.py has the mathematics) ------------
 
-    def gradient(self, observed, *, segment: int | None = None) -> "MediumGradient":
+    def gradient(self, observed, *, segment: int | None = None, wrt_density: bool = False) -> "MediumGradient":
         """Misfit ``J = 1/2 sum_{n=1..K} sum_r (trace[n, r] - observed[n, r])^2`` and its gradients
         with respect to ``speed2`` and the wavelet (full-waveform-inversion gradient / reverse-time
         migration image). ``observed``: ``[timesteps + 1, len(receivers)]``, row 0 is ignored.
@@ -401,6 +401,17 @@ class MediumSolver:
         reverse pass recomputes one segment at a time (``segment >= K - 1``: nothing is
         recomputed). The result does not depend on ``segment`` bit for bit. None: the segment
         with the fewest levels (:func:`gradient_levels`), checked against the free device memory.
+
+        ``wrt_density=True`` (needs ``problem.density``, a scalar is fine) also returns ``grad_density``,
+        dJ/drho at fixed ``speed2``, with the convention of ``grad_speed2``: the derivative with respect
+        to the densities of the stencil nodes (the unique x planes, j and k in 1..N-1), entry [0] for
+        the shared value of planes 0 and N, entry [N] a copy of it. The densities of the Dirichlet wall
+        nodes do enter the adjacent half-face averages; they are held fixed and reported as 0, like
+        the faces of ``grad_speed2``. ``grad_speed2`` stays the derivative at fixed rho, so any other
+        parametrisation follows from the pair by the chain rule (impedance and speed, bulk modulus
+        and density, ...). "hip": each segment then also keeps the levels u^n of its steps beside q,
+        ``min(segment, K - 1)`` more levels plus one accumulator, and every adjoint step is followed
+        by one ``k_face_corr`` call; the other results do not change by a bit.
         """
         p = self.problem
         K = p.timesteps
@@ -414,26 +425,32 @@ class MediumSolver:
                              f"not {tuple(obs.shape)}")
         if segment is not None and int(segment) < 1:
             raise ValueError(f"segment must be >= 1 step, not {segment}")
+        wrt_density = bool(wrt_density)
+        if wrt_density and p.density is None:
+            raise ValueError("gradient(wrt_density=True) needs a density model: build the MediumProblem with "
+                             "density=... (a scalar such as 1.0 is fine)")
         obs = obs.detach().cpu()
-        return self._gradient_cpu(obs) if self.backend == "cpu" else self._gradient_hip(obs, segment)
+        if self.backend == "cpu":
+            return self._gradient_cpu(obs, wrt_density)
+        return self._gradient_hip(obs, segment, wrt_density)
 
-    def _gradient_cpu(self, obs) -> "MediumGradient":
+    def _gradient_cpu(self, obs, wrt_density: bool = False) -> "MediumGradient":
         import time
 
         from ..ops import reference
 
         p = self.problem
         t0 = time.perf_counter()
-        J, gs, gw, tr = reference.gradient_medium(p.N, p.timesteps, p.speed2, obs, sources=self.sources,
-                                                  wavelet=self.wavelet, receivers=self.receivers,
-                                                  taper=self.taper, L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi,
-                                                  dtype=p.torch_dtype, order=p.space_order, density=p.density)
+        fn = reference.gradient_medium_density if wrt_density else reference.gradient_medium
+        J, gs, gw, tr, *gd = fn(p.N, p.timesteps, p.speed2, obs, sources=self.sources, wavelet=self.wavelet,
+                                receivers=self.receivers, taper=self.taper, L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi,
+                                dtype=p.torch_dtype, order=p.space_order, density=p.density)
         return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr,
-                              total_ms=(time.perf_counter() - t0) * 1e3,
+                              total_ms=(time.perf_counter() - t0) * 1e3, grad_density=gd[0] if gd else None,
                               extra=dict(segment=None, levels=None, recomputed_steps=0, space_order=p.space_order,
-                                         density=p.density is not None))
+                                         density=p.density is not None, wrt_density=wrt_density))
 
-    def _gradient_hip(self, obs, segment) -> "MediumGradient":
+    def _gradient_hip(self, obs, segment, wrt_density: bool = False) -> "MediumGradient":
         import time
 
         from ..ops import kernels, reference
@@ -450,12 +467,12 @@ class MediumSolver:
             level_bytes = kernels.level_bytes(N + 1 + 2 * M, N + 1, N + 1, dt)
             free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
             if segment is None:
-                segment = best_gradient_segment(K)
+                segment = best_gradient_segment(K, wrt_density=wrt_density)
                 what = "the smallest schedule"
             else:
                 segment = int(segment)
                 what = f"the schedule of segment = {segment}"
-            nlev = gradient_levels(K, segment, density=p.density is not None)
+            nlev = gradient_levels(K, segment, density=p.density is not None, wrt_density=wrt_density)
             if nlev * level_bytes > free:
                 raise RuntimeError(f"gradient(): {what} holds {nlev} levels = {nlev * level_bytes} bytes, but only "
                                    f"{free} bytes of device memory are free")
@@ -471,6 +488,10 @@ class MediumSolver:
             ad = [level() for _ in range(3)] if len(segs) > 1 else lv  # the adjoint's ring
             m, acc = level(), level()
             qb = [level() for _ in range(qlen)]
+            # wrt_density: ub[n - (a - 1)] = u^n for the steps n = a-1 .. b-1 of the segment [a, b] at hand
+            # (its own data: with one segment the adjoint ring overwrites the forward ring), and accb
+            ub = [level() for _ in range(qlen)] if wrt_density else None
+            accb = level() if wrt_density else None
             ck = [(level(), level()) for _ in segs[:-1]]
             mc = reference.medium_coefficient(p.speed2, c["tau"], N, dt, M, p.density)
             m.copy_(mc)
@@ -488,6 +509,10 @@ class MediumSolver:
             traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
             scratch = kernels.new_err(1, device=dev)  # statistics of the recomputed steps (those of `stat` again)
+
+            def keep_level(n, a):  # u^n, injected and wrapped, into the history of the segment from a
+                if wrt_density:
+                    ub[n - (a - 1)]._base.copy_(lv[n % 3]._base)
 
             def forward_step(n, slot, save):
                 u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
@@ -513,9 +538,13 @@ class MediumSolver:
                 if not last:
                     ck[si][0]._base.copy_(lv[(a - 1) % 3]._base)
                     ck[si][1]._base.copy_(lv[(a - 2) % 3]._base)
+                if last:
+                    keep_level(a - 1, a)
                 for n in range(a, b + 1):
                     forward_step(n, stat[3 * n:3 * n + 3], qb[n - a] if last else None)
                     kernels.record(lv[n % 3], rec, traces[n])
+                    if last and n < b:
+                        keep_level(n, a)
             ev[1].record()
             check(stat, "forward")
             tr = traces.cpu()
@@ -539,8 +568,11 @@ class MediumSolver:
                 if si != len(segs) - 1:
                     lv[(a - 1) % 3]._base.copy_(ck[si][0]._base)
                     lv[(a - 2) % 3]._base.copy_(ck[si][1]._base)
+                    keep_level(a - 1, a)
                     for n in range(a, b + 1):
                         forward_step(n, scratch, qb[n - a])
+                        if n < b:
+                            keep_level(n, a)
                     recomputed += b - a + 1
                 for n in range(b - 1, a - 2, -1):  # q^n is what forward step n + 1 saved
                     u1, u2, u = ad[(n + 1) % 3], ad[(n + 2) % 3], ad[n % 3]
@@ -549,15 +581,23 @@ class MediumSolver:
                                         **step_kw)
                     kernels.inject(u, m, adj, ag[n], wrap)
                     kernels.record(u, snodes, a_dev[n - 1])
+                    if wrt_density:  # u1 = mu^{n+1}, injected and wrapped; its level is reused two steps on
+                        kernels.face_correlation(u1, ub[n - (a - 1)], accb, box, h2=h2)
             ev[3].record()
             check(astat, "adjoint")
-            gs, gw = reference.finish_gradient_medium(acc.cpu(), a_dev.cpu(), gsrc, mc, tt, self.sources, N, c["tau"],
+            acc_c, a_c = acc.cpu(), a_dev.cpu()
+            gs, gw = reference.finish_gradient_medium(acc_c, a_c, gsrc, mc, tt, self.sources, N, c["tau"],
                                                       c["hx"], c["hy"], c["hz"], M, p.density)
+            gd = None
+            if wrt_density:
+                gd = reference.finish_gradient_density(acc_c, accb.cpu(), a_c, gsrc, mc, tt, self.sources, N,
+                                                       c["tau"], p.speed2, p.density, M)
             torch.cuda.synchronize(dev)
             ms = (time.perf_counter() - t0) * 1e3
-            return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr, total_ms=ms,
+            return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr, total_ms=ms, grad_density=gd,
                                   extra=dict(segment=segment, levels=nlev, recomputed_steps=recomputed,
                                              space_order=p.space_order, density=p.density is not None,
+                                             wrt_density=wrt_density,
                                              forward_ms=ev[0].elapsed_time(ev[1]), reverse_ms=ev[2].elapsed_time(ev[3])))
 
 
@@ -568,24 +608,30 @@ class MediumGradient:
     grad_wavelet: torch.Tensor  # [K, S]
     traces: torch.Tensor        # [K+1, R], those of run()
     total_ms: float             # wall time of the whole call
-    # segment, levels, recomputed_steps; "hip" also forward_ms / reverse_ms, the device time of the two passes
+    # segment, levels, recomputed_steps, wrt_density; "hip" also forward_ms / reverse_ms, the device time of the
+    # two passes
     extra: dict = field(default_factory=dict)
+    # gradient(wrt_density=True): (N+1)^3, dJ/drho at fixed speed2 on the stencil nodes (plane N = plane 0, faces 0)
+    grad_density: torch.Tensor | None = None
 
 
-def gradient_levels(K: int, segment: int, density: bool = False) -> int:
+def gradient_levels(K: int, segment: int, density: bool = False, wrt_density: bool = False) -> int:
     """Number of grid levels the "hip" schedule of :meth:`MediumSolver.gradient` holds for K
     timesteps cut into segments of ``segment`` steps (steps 2..K): the forward ring (3), m, acc, the
     q buffer (one level per step of a segment), a checkpoint pair per segment but the last, and,
     when there is anything to recompute, a second ring for the adjoint field. ``density``: one more
-    level, the buoyancy of a problem with a density model."""
+    level, the buoyancy of a problem with a density model. ``wrt_density``: the levels u^n of a segment's
+    steps beside its q buffer and the accumulator of the density gradient, ``min(segment, K - 1) + 1`` more."""
     K, segment = int(K), int(segment)
     if K < 1 or segment < 1:
         raise ValueError(f"need K >= 1 and segment >= 1, not K={K} segment={segment}")
     nseg = -(-(K - 1) // segment)
-    return 5 + bool(density) + min(segment, K - 1) + (2 * (nseg - 1) + 3 if nseg > 1 else 0)
+    nq = min(segment, K - 1)
+    return 5 + bool(density) + nq + (nq + 1 if wrt_density else 0) + (2 * (nseg - 1) + 3 if nseg > 1 else 0)
 
 
-def best_gradient_segment(K: int) -> int:
-    """The segment length with the fewest levels; every schedule recomputes less than one extra
-    forward pass, and of equal level counts the longer segment (less recomputation) wins."""
-    return min(range(1, max(K - 1, 1) + 1), key=lambda s: (gradient_levels(K, s), -s))
+def best_gradient_segment(K: int, wrt_density: bool = False) -> int:
+    """The segment length with the fewest levels (``wrt_density``: of the schedule with the density
+    gradient); every schedule recomputes less than one extra forward pass, and of equal level counts
+    the longer segment (less recomputation) wins."""
+    return min(range(1, max(K - 1, 1) + 1), key=lambda s: (gradient_levels(K, s, wrt_density=wrt_density), -s))

@@ -5,7 +5,7 @@ device; they are passed to the native kernels as raw pointers on torch's current
 Shapes are validated here *before* any launch (the kernels index with the boxes given).
 The solver itself uses an aligned, padded layout (``csrc/hip_kernels.hpp``); these entry
 points use pitch = nz, which the kernels accept as well; the medium ops (``step_medium``,
-``inject``, ``record``) also take views in that padded layout (``alloc_level``).
+``face_correlation``, ``inject``, ``record``) also take views in that padded layout (``alloc_level``).
 """
 from __future__ import annotations
 
@@ -455,6 +455,42 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
        _MEDIUM_VARIANTS[variant], *gp, lap_out.data_ptr() if lap_out is not None else 0,
        *((image[0].data_ptr(), image[1].data_ptr()) if image is not None else (0, 0)), int(order), mir,
        buoyancy.data_ptr() if buoyancy is not None else 0)
+
+
+def _grid_span(t: torch.Tensor) -> tuple[int, int]:
+    """[first byte, one past the last byte) of the memory a grid view covers."""
+    n = sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1
+    return t.data_ptr(), t.data_ptr() + n * t.element_size()
+
+
+def face_correlation(a, v, acc, boxes, *, h2, chunk: int = 0) -> None:
+    """``acc = acc + C(a, v)`` at the nodes of ``boxes`` (``k_face_corr``), the accumulation behind the
+    density gradient of the adjoint pass: ``C`` is the sum over a node's six faces of the products of
+    the two fields' differences across the face, per axis divided by h2 = (hx2, hy2, hz2)
+    (``ops.reference.face_correlation`` has the scheme; fp64 results are bitwise equal to it).
+
+    The grids are dense ``[nx][ny][nz]`` tensors or :func:`alloc_level` views with identical shapes,
+    dtypes, devices and strides; the boxes lie inside the owned region (``step_medium``'s contract at
+    order 2), so every box node has its six neighbours in storage. ``a`` and ``v`` are never written,
+    ``acc`` only at the box nodes, and it must not share memory with ``a`` or ``v``. Every violation is
+    a ``ValueError`` before any launch."""
+    if not all(isinstance(t, torch.Tensor) for t in (a, v, acc)):
+        raise ValueError("a, v and acc must be tensors")
+    gv = _check_grid_strided(a, v, acc)
+    c0, c1 = _grid_span(acc)
+    for t, name in ((a, "a"), (v, "v")):
+        t0, t1 = _grid_span(t)
+        if c0 < t1 and t0 < c1:
+            raise ValueError(f"acc shares memory with {name}")
+    if isinstance(boxes[0], int):
+        boxes = [boxes]
+    if not 1 <= len(boxes) <= 7:
+        raise ValueError("1..7 boxes per launch")
+    bl = [_check_box(b, gv) for b in boxes]
+    if len(h2) != 3 or not all(float(x) > 0 for x in h2):
+        raise ValueError("h2 = (hx2, hy2, hz2), all > 0")
+    getattr(_C(), "k_face_corr_" + _sfx(a))(a.data_ptr(), v.data_ptr(), acc.data_ptr(), gv, bl,
+                                           [float(x) for x in h2], int(chunk), _stream())
 
 
 def inject(u, m, nodes, g, wrap=None) -> None:

@@ -295,6 +295,37 @@ def laplace_density(u: torch.Tensor, b: torch.Tensor, hx2, hy2, hz2) -> torch.Te
     return ans
 
 
+def face_correlation(a: torch.Tensor, v: torch.Tensor, box, hx2, hy2, hz2) -> torch.Tensor:
+    """Face correlation ``C(a, v)`` of two grids on the nodes of ``box`` (storage indices, inclusive):
+    the sum over a node's six faces of the products of the two fields' differences across the face.
+    Per axis, with centre values a_c, v_c and neighbours a_-, a_+, v_-, v_+:
+    ``p_+ = (a_+ - a_c) (v_+ - v_c)``, ``p_- = (a_c - a_-) (v_c - v_-)``, ``t = p_+ + p_-``, and
+    ``C = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2``, every operation rounded on its own. Symmetric
+    in (a, v) bit for bit, and a face's product is the same number seen from either of its nodes.
+
+    It is the derivative of ``laplace_density`` with respect to the buoyancy: for a vanishing on the
+    boundary of the box's neighbourhood, ``d <a, D_b v> / d b_l = -C(a, v)_l / 2``. The box contract is
+    ``step_medium``'s at order 2: every box node has its six neighbours inside the storage."""
+    if a.dim() != 3 or v.shape != a.shape or v.dtype != a.dtype:
+        raise ValueError(f"the two grids must match: {tuple(a.shape)} {a.dtype}, not {tuple(v.shape)} {v.dtype}")
+    i0, i1, j0, j1, k0, k1 = (int(x) for x in box)
+    nx, ny, nz = a.shape
+    if not (1 <= i0 <= i1 <= nx - 2 and 1 <= j0 <= j1 <= ny - 2 and 1 <= k0 <= k1 <= nz - 2):
+        raise ValueError(f"box {tuple(box)} is empty or touches an edge of the {nx}x{ny}x{nz} storage")
+    ctr = [slice(i0, i1 + 1), slice(j0, j1 + 1), slice(k0, k1 + 1)]
+    ac, vc = a[tuple(ctr)], v[tuple(ctr)]
+    ans = torch.zeros_like(ac)
+    for axis, h2 in enumerate((hx2, hy2, hz2)):
+        lo, hi = list(ctr), list(ctr)
+        lo[axis] = slice(ctr[axis].start - 1, ctr[axis].stop - 1)
+        hi[axis] = slice(ctr[axis].start + 1, ctr[axis].stop + 1)
+        lo, hi = tuple(lo), tuple(hi)
+        pp = (a[hi] - ac) * (v[hi] - vc)
+        pm = (ac - a[lo]) * (vc - v[lo])
+        ans = ans + (pp + pm) / h2
+    return ans
+
+
 def _lap_box(u1, box, hx2, hy2, hz2, order: int, mirror, buoyancy=None):
     """lap(u1) on the nodes of ``box``: order 2 is ``laplace7`` (today's operations), 4 and 8
     ``laplace_star``; with ``buoyancy`` (order 2 only) ``laplace_density``."""
@@ -520,6 +551,10 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
 # rho^n the residuals scattered to the receiver nodes, and with q^n = L u^n
 #   dJ/dm = (sum_{n=K-1..1} mu^{n+1} q^n) / m + e_s (sum_n mu^{n+1}[x_s] g[n, s]) / (m[x_s] G[x_s]),
 #   dJ/dg[n, s] = mu^{n+1}[x_s] / G[x_s].
+# With a density, m = rho c^2 tau^2 and L = D_b with b = 1 / rho; summation by parts (mu is 0 on the
+# Dirichlet faces, x is periodic) gives dJ/db = -1/2 sum_{n=K-1..1} C(mu^{n+1}, u^n), C the
+# face_correlation, and dJ/drho at fixed c^2 = dJ/dm c^2 tau^2 + (1/2 sum_n C) / rho^2
+# (gradient_medium_density, finish_gradient_density).
 # The helpers below are the host-side arithmetic shared by gradient_medium and the HIP front-end
 # (models/medium.py): both call them on CPU tensors, so they round alike.
 
@@ -549,13 +584,15 @@ def taper_at(tt, node):
 
 def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None, receivers=(), taper=None,
                             L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
-                            keep_lap: bool = False, order: int = 2, density=None):
+                            keep_lap: bool = False, order: int = 2, density=None, keep_levels: bool = False):
     """``solve_medium`` from rest, restated out of place: every level is a new tensor, so
     ``torch.autograd`` can differentiate the traces with respect to ``speed2`` (an ``(N+1)^3``
     tensor) and ``wavelet``. The operations and their order are those of ``solve_medium``: the traces
     ``[K+1, R]`` are equal bit for bit. ``keep_lap``: also return [q^1 .. q^{K-1}], q^n = lap u^n on
-    the stencil nodes (the value step n+1 uses). ``density``: as in ``solve_medium`` (held fixed; q^n is
-    then ``laplace_density`` of u^n)."""
+    the stencil nodes (the value step n+1 uses). ``density``: as in ``solve_medium`` (a scalar, an
+    ``(N+1)^3`` tensor or a leaf to differentiate with respect to; q^n is then ``laplace_density`` of
+    u^n). ``keep_levels``: also return [u^1 .. u^{K-1}], whole levels in storage with their x ghosts
+    (after ``keep_lap``'s list if both are asked for)."""
     c = tables(N, K, L, T, pi)[4]
     M, box, mirror = _medium_layout(N, order)
     shape = (N + 1 + 2 * M, N + 1, N + 1)
@@ -568,10 +605,12 @@ def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None,
     u2 = torch.zeros(shape, dtype=dtype)
     u1 = torch.zeros(shape, dtype=dtype)
     rows = [torch.stack([u1[nd] for nd in rec]) if rec else torch.zeros(0, dtype=dtype)]
-    laps = []
+    laps, levels = [], []
     for n in range(1, K + 1):
         if keep_lap and n >= 2:
             laps.append(_lap_box(u1, box, c["hx2"], c["hy2"], c["hz2"], order, mirror, bu))
+        if keep_levels and n >= 2:
+            levels.append(u1)
         vals = step_medium(u1, u2, m, box, first=n == 1, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt,
                            order=order, mirror=mirror, buoyancy=bu)
         u = torch.zeros(shape, dtype=dtype)
@@ -582,7 +621,8 @@ def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None,
         rows.append(torch.stack([u[nd] for nd in rec]) if rec else torch.zeros(0, dtype=dtype))
         u2, u1 = u1, u
     traces = torch.stack(rows)
-    return (traces, laps) if keep_lap else traces
+    out = (traces,) + ((laps,) if keep_lap else ()) + ((levels,) if keep_levels else ())
+    return out if len(out) > 1 else traces
 
 
 def misfit_medium(traces, observed):
@@ -625,6 +665,29 @@ def source_unique_nodes(sources, N: int, ghost: int = 1):
     return [((i % N) + ghost, j, k) for i, j, k in sources]
 
 
+def _gradient_wrt_m(acc, a, g, m, tt, sources, N: int, ghost: int):
+    """dJ/dm on the planes 0 .. N: ``acc / m`` plus the source term at the source nodes; also returns
+    the sources' unique storage nodes."""
+    gm = acc[ghost:N + 1 + ghost] / m[ghost:N + 1 + ghost]
+    nodes = source_unique_nodes(sources, N, ghost)
+    if nodes:
+        dots = (a * g).sum(0)
+        for s, nd in enumerate(nodes):
+            at = (nd[0] - ghost, nd[1], nd[2])
+            gm[at] = gm[at] + dots[s] / (m[nd] * taper_at(tt, nd))
+    return gm, nodes
+
+
+def _unique_node_convention(grad, N: int):
+    """In place: plane N a copy of plane 0, the Dirichlet faces 0."""
+    grad[N] = grad[0]
+    grad[:, 0, :] = 0
+    grad[:, N, :] = 0
+    grad[:, :, 0] = 0
+    grad[:, :, N] = 0
+    return grad
+
+
 def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: float, hy: float, hz: float,
                            ghost: int = 1, density=None):
     """The host-side end of the gradient. acc ``[N+1+2 ghost][N+1][N+1]`` = sum mu^{n+1} q^n in storage
@@ -633,27 +696,84 @@ def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: fl
     with respect to the unique nodes: plane N a copy of plane 0, faces 0; dJ/dwavelet ``[K, S]``).
     ``density`` (a scalar or ``(N+1)^3``): m = rho speed2 tau^2, so the gradient is multiplied by rho as
     its last arithmetic operation: dJ/dspeed2 at fixed rho."""
-    gm = acc[ghost:N + 1 + ghost] / m[ghost:N + 1 + ghost]
-    nodes = source_unique_nodes(sources, N, ghost)
-    if nodes:
-        dots = (a * g).sum(0)
-        for s, nd in enumerate(nodes):
-            at = (nd[0] - ghost, nd[1], nd[2])
-            gm[at] = gm[at] + dots[s] / (m[nd] * taper_at(tt, nd))
+    gm, nodes = _gradient_wrt_m(acc, a, g, m, tt, sources, N, ghost)
     grad = (gm * tau) * tau  # m = (speed2 tau) tau
     if density is not None:
         grad = grad * _node_field(density, N, "density").to(grad.dtype)
-    grad[N] = grad[0]
-    grad[:, 0, :] = 0
-    grad[:, N, :] = 0
-    grad[:, :, 0] = 0
-    grad[:, :, N] = 0
+    _unique_node_convention(grad, N)
     gw = torch.zeros_like(a)
     for s, nd in enumerate(nodes):
         gw[:, s] = a[:, s] / taper_at(tt, nd) / (hx * hy * hz)
     if gw.shape[0] > 0:
         gw[0] = gw[0] * 0.5
     return grad, gw
+
+
+def finish_gradient_density(acc, accb, a, g, m, tt, sources, N: int, tau: float, speed2, density,
+                            ghost: int = 1):
+    """The host-side end of the density gradient, shared by both backends. acc, a, g, m, tt, sources as
+    in ``finish_gradient_medium``; accb ``[N+1+2 ghost][N+1][N+1]`` = sum_{n=K-1..1} C(mu^{n+1}, u^n)
+    (``face_correlation``) in storage. rho enters the step through ``m = rho speed2 tau^2`` and through
+    the buoyancy ``b = 1 / rho`` of ``laplace_density``; with gm = dJ/dm, in the working dtype and with
+    rho and speed2 cast to it:
+
+        dJ/drho = ((gm tau) tau) speed2 + (0.5 accb) / (rho rho)
+
+    at fixed speed2. Returns it as ``(N+1)^3`` with respect to the densities of the stencil nodes, the
+    unique x planes and j, k in 1 .. N-1: plane N a copy of plane 0 and the Dirichlet faces 0 (the wall
+    nodes' densities do enter the adjacent half-face averages; they are held fixed and reported as 0,
+    like the faces of dJ/dspeed2, which keeps the accumulation on ``step_medium``'s box)."""
+    gm, _ = _gradient_wrt_m(acc, a, g, m, tt, sources, N, ghost)
+    rho = _node_field(density, N, "density").to(gm.dtype)
+    part1 = ((gm * tau) * tau) * _node_field(speed2, N, "speed2").to(gm.dtype)
+    part2 = (0.5 * accb[ghost:N + 1 + ghost]) / (rho * rho)
+    return _unique_node_convention(part1 + part2, N)
+
+
+def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, receivers, taper, L, T, pi, dtype,
+                    order: int, density, wrt_density: bool):
+    """The forward run and the adjoint loop shared by ``gradient_medium`` and
+    ``gradient_medium_density``: everything their host-side ends need, as a dict."""
+    fwd = forward_medium_autograd(N, K, speed2, sources=sources, wavelet=wavelet, receivers=receivers,
+                                  taper=taper, L=L, T=T, pi=pi, dtype=dtype, keep_lap=True, order=order,
+                                  density=density, keep_levels=wrt_density)
+    traces, laps = fwd[0], fwd[1]
+    J, res = misfit_medium(traces, observed)
+    c = tables(N, K, L, T, pi)[4]
+    M, box, mirror = _medium_layout(N, order)
+    tt = None if taper is None else taper_tables(taper, N, dtype, M)
+    m = medium_coefficient(speed2, c["tau"], N, dtype, M, density)
+    bu = _buoyancy(density, N, dtype, order, M)
+    g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
+    anodes, atab = adjoint_source_table(res, receivers, N, tt, M)
+    snodes = source_unique_nodes(sources, N, M)
+    shape = (N + 1 + 2 * M, N + 1, N + 1)
+    own = (slice(M, N + 1 + M), slice(1, N), slice(1, N))
+    a = torch.zeros(K, len(snodes), dtype=dtype)
+
+    def finish_level(mu, n):  # inject G rho^n, wrap, sample mu^n at the sources
+        for e, nd in enumerate(anodes):
+            mu[nd] = mu[nd] + m[nd] * atab[n, e]
+        _wrap_x(mu, N, M)
+        for s, nd in enumerate(snodes):
+            a[n - 1, s] = mu[nd]
+
+    mu2 = torch.zeros(shape, dtype=dtype)
+    mu1 = torch.zeros(shape, dtype=dtype)
+    finish_level(mu1, K)
+    acc = torch.zeros(shape, dtype=dtype)
+    accb = torch.zeros(shape, dtype=dtype) if wrt_density else None
+    for n in range(K - 1, 0, -1):
+        vals = step_medium(mu1, mu2, m, box, first=False, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt,
+                           order=order, mirror=mirror, buoyancy=bu)
+        acc[own] = acc[own] + mu1[own] * laps[n - 1]
+        if wrt_density:  # mu1 = mu^{n+1}, injected and wrapped; fwd[2][n - 1] = u^n
+            accb[own] = accb[own] + face_correlation(mu1, fwd[2][n - 1], box, c["hx2"], c["hy2"], c["hz2"])
+        mu = torch.zeros(shape, dtype=dtype)
+        mu[own] = vals
+        finish_level(mu, n)
+        mu2, mu1 = mu1, mu
+    return dict(J=J, traces=traces, acc=acc, accb=accb, a=a, g=g, m=m, tt=tt, c=c, M=M)
 
 
 def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,
@@ -674,43 +794,40 @@ def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=Non
 
     density: rho of ``solve_medium`` (order 2), held fixed: ``laplace_density`` is symmetric on the
     unique nodes too, so the adjoint field runs on the same density step, and dJ/dspeed2 is the
-    derivative at fixed rho (``finish_gradient_medium``). dJ/drho is not computed."""
+    derivative at fixed rho (``finish_gradient_medium``). dJ/drho: ``gradient_medium_density``."""
     with torch.no_grad():
-        traces, laps = forward_medium_autograd(N, K, speed2, sources=sources, wavelet=wavelet,
-                                               receivers=receivers, taper=taper, L=L, T=T, pi=pi, dtype=dtype,
-                                               keep_lap=True, order=order, density=density)
-        J, res = misfit_medium(traces, observed)
-        c = tables(N, K, L, T, pi)[4]
-        M, box, mirror = _medium_layout(N, order)
-        tt = None if taper is None else taper_tables(taper, N, dtype, M)
-        m = medium_coefficient(speed2, c["tau"], N, dtype, M, density)
-        bu = _buoyancy(density, N, dtype, order, M)
-        g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
-        anodes, atab = adjoint_source_table(res, receivers, N, tt, M)
-        snodes = source_unique_nodes(sources, N, M)
-        shape = (N + 1 + 2 * M, N + 1, N + 1)
-        own = (slice(M, N + 1 + M), slice(1, N), slice(1, N))
-        a = torch.zeros(K, len(snodes), dtype=dtype)
+        r = _adjoint_medium(N, K, speed2, observed, sources=sources, wavelet=wavelet, receivers=receivers,
+                            taper=taper, L=L, T=T, pi=pi, dtype=dtype, order=order, density=density,
+                            wrt_density=False)
+        c = r["c"]
+        grad, gw = finish_gradient_medium(r["acc"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"], c["hx"],
+                                          c["hy"], c["hz"], r["M"], density)
+        return r["J"], grad, gw, r["traces"]
 
-        def finish_level(mu, n):  # inject G rho^n, wrap, sample mu^n at the sources
-            for e, nd in enumerate(anodes):
-                mu[nd] = mu[nd] + m[nd] * atab[n, e]
-            _wrap_x(mu, N, M)
-            for s, nd in enumerate(snodes):
-                a[n - 1, s] = mu[nd]
 
-        mu2 = torch.zeros(shape, dtype=dtype)
-        mu1 = torch.zeros(shape, dtype=dtype)
-        finish_level(mu1, K)
-        acc = torch.zeros(shape, dtype=dtype)
-        for n in range(K - 1, 0, -1):
-            vals = step_medium(mu1, mu2, m, box, first=False, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt,
-                               order=order, mirror=mirror, buoyancy=bu)
-            acc[own] = acc[own] + mu1[own] * laps[n - 1]
-            mu = torch.zeros(shape, dtype=dtype)
-            mu[own] = vals
-            finish_level(mu, n)
-            mu2, mu1 = mu1, mu
-        grad, gw = finish_gradient_medium(acc, a, g, m, tt, sources, N, c["tau"], c["hx"], c["hy"], c["hz"], M,
-                                          density)
-        return J, grad, gw, traces
+def gradient_medium_density(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,
+                            L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
+                            order: int = 2, density=None):
+    """``gradient_medium`` of a problem with a ``density`` (required; order 2), plus the gradient with
+    respect to it: (J, dJ/dspeed2 at fixed rho, dJ/dwavelet, traces, dJ/drho at fixed speed2). The
+    first four are those of ``gradient_medium`` bit for bit.
+
+    Beside ``acc`` the adjoint loop accumulates ``accb = accb + C(mu^{n+1}, u^n)`` (``face_correlation``)
+    for n = K-1 .. 1 in that order, mu^{n+1} injected and wrapped; by summation by parts (mu is 0 on
+    the Dirichlet faces and x is periodic) ``dJ/db_l = -accb_l / 2``. ``finish_gradient_density`` has the
+    rest and the face convention: the derivative with respect to the densities of the stencil nodes,
+    entry [0] for the shared value of planes 0 and N (autograd's ``g[0] + g[N]`` for a density leaf),
+    the Dirichlet faces reported as 0. Other parametrisations follow by the chain rule from the pair
+    (dJ/dspeed2 at fixed rho, dJ/drho at fixed speed2)."""
+    if density is None:
+        raise ValueError("gradient_medium_density needs a density (a scalar or an (N+1)^3 field)")
+    with torch.no_grad():
+        r = _adjoint_medium(N, K, speed2, observed, sources=sources, wavelet=wavelet, receivers=receivers,
+                            taper=taper, L=L, T=T, pi=pi, dtype=dtype, order=order, density=density,
+                            wrt_density=True)
+        c = r["c"]
+        grad, gw = finish_gradient_medium(r["acc"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"], c["hx"],
+                                          c["hy"], c["hz"], r["M"], density)
+        gd = finish_gradient_density(r["acc"], r["accb"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"],
+                                     speed2, density, r["M"])
+        return r["J"], grad, gw, r["traces"], gd

@@ -6,6 +6,7 @@
                                  [--taper WIDTH] [--order 2,4,8] [--density]
     python tools/bench_medium.py --gradient [--N 512] [--steps 100] [--dtypes fp64,fp32] [--segment 10]
                                  [--order 2,8] [--kernels-only] [--density]
+    python tools/bench_medium.py --gradient --density --wrt-density [--N 512] [--steps 100] [--segment 10]
 
 For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
 and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
@@ -38,6 +39,15 @@ against 32 (16), so the byte count predicts 1.25 times the constant-density time
 beside `expected_ratio`); with `--gradient` 48 B (save) and 64 B (image) against 40 and 56. The speed
 is lowered by the factor 1.5 that the two-layer interface adds to the Courant number's
 max kappa bhat. Works with `--taper` and `--gradient --kernels-only`.
+
+`--gradient --density --wrt-density` measures the density gradient dJ/drho (order 2), per dtype in
+one process: ms per call of k_face_corr (a, v read, acc read and written: 32 B per node in fp64, 16 B
+in fp32) beside the plain constant-density step k_march_m (the same byte count) and the plain density
+step k_march_mb, `--repeat` rounds of 20 launches each, the three alternating inside each round; then
+gradient() of the two-layer density problem with and without `wrt_density`, with every level stored
+(segment = steps) and with `--segment`, the four alternating inside each repeat: the device time of
+the two passes, the wall time, the levels held and their size. A schedule that does not fit the free
+device memory is reported as such.
 """
 import argparse
 import json
@@ -70,6 +80,118 @@ def two_layer_density(N: int):
     rho = torch.ones((N + 1,) * 3, dtype=torch.float64)
     rho[:, :, N // 2:] = 2.0
     return rho
+
+
+def density_gradient_bench(a) -> int:
+    import math
+
+    import torch
+
+    import wave3d
+    from wave3d.ops import kernels, reference
+
+    N, K = a.N, a.steps
+    h = 3.1415926535 / N
+    hi = (0.9 * wave3d.cfl_limit(2) * h * K) ** 2 / 1.5
+    speed2 = smooth_speed2(N, 0.5 * hi, hi)
+    rho = two_layer_density(N)
+    nodes = float(N + 1) ** 3
+    out = {"N": N, "steps": K, "device": torch.cuda.get_device_name(0), "density": "two layers: 1, 2",
+           "kernels": [], "gradient": []}
+    dev = torch.device("cuda", 0)
+    for dtype in a.dtypes.split(","):
+        es = 8 if dtype == "fp64" else 4
+        prob = wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype, density=rho)
+        dt = prob.torch_dtype
+        c = reference.tables(N, K)[4]
+        h2 = (c["hx2"], c["hy2"], c["hz2"])
+        box, wrap = (1, N + 1, 1, N - 1, 1, N - 1), [N, 0, 2, N + 2]
+
+        # the kernels on one set of levels (smooth values, nothing denormal)
+        g = torch.Generator().manual_seed(1)
+        seed = torch.rand(N + 1, N + 1, generator=g, dtype=torch.float64).to(dt).to(dev)
+        u1, u2, m, u, acc, bu = (kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(6))
+        m.copy_(reference.medium_coefficient(speed2, c["tau"], N, dt, 1, rho))
+        bu.copy_(reference.buoyancy_field(rho, N, dt))
+        for t in (u1, u2):
+            t[:, 1:N, 1:N] = seed[1:N, 1:N]
+        stat = kernels.new_err(1, device=dev)
+        step = dict(first=False, h2=h2, stat=stat, stat_i=(1, N + 1), wrap=wrap)
+        arms = {"k_march_m": (4, lambda: kernels.step_medium(u1, u2, m, u, box, **step)),
+                "k_march_mb": (5, lambda: kernels.step_medium(u1, u2, m, u, box, buoyancy=bu, **step)),
+                "k_face_corr": (4, lambda: kernels.face_correlation(u1, u2, acc, box, h2=h2))}
+        reps = 20
+        ms = {k: [] for k in arms}
+        for rnd in range(a.repeat + 1):  # round 0 warms up
+            for name, (_, fn) in arms.items():  # the arms alternate inside each round
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                acc.zero_()
+                e0.record()
+                for _ in range(reps):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                if rnd:
+                    ms[name].append(e0.elapsed_time(e1) / reps)
+        for name, (bpn, _) in arms.items():
+            best = min(ms[name])
+            out["kernels"].append({"dtype": dtype, "kernel": name, "ms_per_call": round(best, 4),
+                                   "all_ms": [round(v, 4) for v in ms[name]], "bytes_per_node": bpn * es,
+                                   "eff_tb_per_s": round(bpn * es * nodes / (best * 1e-3) / 1e12, 3),
+                                   "vs_k_march_m": round(best / min(ms["k_march_m"]), 4),
+                                   "expected_vs_k_march_m": bpn / 4})
+            print(f"bench_medium: {dtype} {name}: {best:.4f} ms/call", file=sys.stderr, flush=True)
+        del u1, u2, m, u, acc, bu, arms, step
+        torch.cuda.empty_cache()
+        if a.kernels_only:
+            continue
+
+        w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
+        mid = N // 2
+        sol = wave3d.MediumSolver(prob, "hip", sources=[(mid, mid, mid)], wavelet=w,
+                                  receivers=[(mid - K // 5, mid, mid), (mid, mid - K // 4, mid + 3)],
+                                  taper=wave3d.sponge_taper(prob, 16))
+        obs = 0.9 * sol.run().traces  # warm-up
+        lb = kernels.level_bytes(N + 3, N + 1, N + 1, dt)
+        cfgs = [(f"{n}{'_wrt_density' if wd else ''}", seg, wd) for n, seg in (("all_stored", K), (f"segment_{a.segment}",
+                a.segment)) for wd in (False, True)]
+        rows = {n: [] for n, _, _ in cfgs}
+        for _ in range(a.repeat):
+            for name, seg, wd in cfgs:
+                levels = wave3d.gradient_levels(K, seg, density=True, wrt_density=wd)
+                try:
+                    r = sol.gradient(obs, segment=seg, wrt_density=wd)
+                except RuntimeError as e:
+                    if "bytes of device memory are free" not in str(e):
+                        raise
+                    rows[name].append({"levels": levels, "gb": round(levels * lb / 1e9, 1), "fits": False})
+                    print(f"bench_medium: {dtype} {name}: does not fit", file=sys.stderr, flush=True)
+                    continue
+                assert math.isfinite(r.misfit) and r.misfit > 0 and r.extra["levels"] == levels
+                assert (r.grad_density is not None) == wd
+                rows[name].append({"wall_ms": round(r.total_ms, 1), "forward_ms": round(r.extra["forward_ms"], 2),
+                                   "reverse_ms": round(r.extra["reverse_ms"], 2), "levels": levels,
+                                   "gb": round(levels * lb / 1e9, 1), "recomputed_steps": r.extra["recomputed_steps"],
+                                   "fits": True})
+                print(f"bench_medium: {dtype} {name}: {rows[name][-1]}", file=sys.stderr, flush=True)
+                del r
+                torch.cuda.empty_cache()
+        for name, seg, wd in cfgs:
+            ok = [v for v in rows[name] if v["fits"]]
+            if not ok:
+                out["gradient"].append({"dtype": dtype, "schedule": name, **rows[name][0]})
+                continue
+            best = min(ok, key=lambda v: v["forward_ms"] + v["reverse_ms"])
+            row = {"dtype": dtype, "schedule": name, **best, "passes_ms": round(best["forward_ms"] + best["reverse_ms"], 2),
+                   "wall_ms_all": [v["wall_ms"] for v in ok]}
+            base = [x for x in out["gradient"] if x["dtype"] == dtype and x["schedule"] == name[:-len("_wrt_density")]]
+            if wd and base and base[0]["fits"]:
+                row["passes_vs_without"] = round(row["passes_ms"] / base[0]["passes_ms"], 3)
+            out["gradient"].append(row)
+        del sol
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+    return 0
 
 
 def gradient_bench(a) -> int:
@@ -224,6 +346,8 @@ def main(argv=None) -> int:
     ap.add_argument("--kernels-only", action="store_true", help="--gradient: the kernel rounds without the schedules")
     ap.add_argument("--density", action="store_true",
                     help="also time the variable-density step (two-layer rho), alternating with the constant-density one")
+    ap.add_argument("--wrt-density", action="store_true",
+                    help="--gradient --density: time k_face_corr and gradient(wrt_density=True) instead")
     a = ap.parse_args(argv)
 
     import math
@@ -241,6 +365,10 @@ def main(argv=None) -> int:
         ap.error("--order: a comma-separated list of 2, 4, 8")
     if a.density and 2 not in orders:
         ap.error("--density: order 2 must be among the orders")
+    if a.wrt_density:
+        if not (a.gradient and a.density) or orders != [2]:
+            ap.error("--wrt-density goes with --gradient --density at order 2")
+        return density_gradient_bench(a)
     if a.gradient:
         return gradient_bench(a)
     variants = a.variants.split(",")
