@@ -24,8 +24,8 @@ def __getattr__(name):
         from .models import wave
 
         return getattr(wave, name)
-    if name in ("MediumProblem", "MediumSolver", "MediumResult", "MediumGradient", "ricker", "sponge_taper",
-                "gradient_levels", "best_gradient_segment", "cfl_limit"):
+    if name in ("MediumProblem", "MediumSolver", "MediumResult", "MediumGradient", "MediumBorn", "ricker",
+                "sponge_taper", "gradient_levels", "best_gradient_segment", "born_levels", "cfl_limit"):
         from .models import medium
 
         return getattr(medium, name)

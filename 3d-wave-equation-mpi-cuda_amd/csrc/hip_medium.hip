@@ -17,6 +17,8 @@
 //  * k_march_mb: k_march_m with a variable density: the operator div(b grad u) with the buoyancy
 //    b = 1 / rho as a fifth stream that rolls through registers and LDS like u^{n-1} (described at
 //    the kernel).
+//  * all three march kernels have the save, image and Born modes of the adjoint-state gradient and
+//    of Born modelling (MarchMode below; hip_medium.hpp has the contract).
 //  * k_inject / k_record: one thread per source entry / receiver.
 //
 // FP contraction is off (-ffp-contract=off + the pragmas in stencil_math.hpp): every operation
@@ -24,6 +26,7 @@
 // bitwise those of the PyTorch oracle, and a uniform m == coef gives k_march's bits.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdlib>
 
 #include <algorithm>
@@ -56,11 +59,14 @@ struct MediumParams {
     T* lap_out;             // kSave: receives lap(u1) at the box nodes (strides of u)
     const T* q;             // kImage: the grid multiplied with the centre value of u1 ...
     T* acc;                 // ... and the grid the product is added to, at the box nodes
+    const T* dm;            // kBorn: the coefficient perturbation; u receives + dm * q (q as above)
 };
 
 // k_march_m modes: the plain step; kSave also stores the Laplacian that entered the update; kImage
-// also accumulates acc = acc + u1 * q (the imaging condition of the adjoint-state gradient).
-enum MarchMode { kPlain = 0, kSave = 1, kImage = 2 };
+// also accumulates acc = acc + u1 * q (the imaging condition of the adjoint-state gradient); kBorn
+// adds the scattering term dm * q to the update itself (Born / linearised modelling, image mode's
+// transpose): u = G (((2 u1 - G u2) + m lap) + dm q).
+enum MarchMode { kPlain = 0, kSave = 1, kImage = 2, kBorn = 3 };
 
 // R = rows (j) per lane; the workgroup tile is (4R) x 64. NTM = non-temporal loads of m.
 // Register slots as in k_march: u1(x) -> (x - ib + 1) & 3; u2(x), m(x), halo(x) and the LDS
@@ -69,7 +75,8 @@ enum MarchMode { kPlain = 0, kSave = 1, kImage = 2 };
 // MODE (kSave / kImage: FIRST = false only) adds, likewise behind `if constexpr`, one write-once
 // stream (lap_out), or a read-once stream (q) and a read-modify-write one (acc), both prefetched
 // one plane ahead in two-slot rings like m; all at the lane's own nodes, masked like the stores
-// of u and without the periodic wrap.
+// of u and without the periodic wrap. kBorn (FIRST = false only) has two read-once streams in the
+// same two rings, q and dm in acc's place, and no store beside u's.
 template <class T, bool FIRST, int R, bool NTM, bool TAPER, int MODE = kPlain>
 __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
     constexpr int kTJ = kWaves * R;
@@ -139,13 +146,14 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
     constexpr int kMAux = NTM ? 2 : 0;  // non-temporal m (read once per step)
     constexpr int kStAux = 2;           // non-temporal stores (write-once stream)
 
-    static_assert(MODE == kPlain || !FIRST, "save / image modes: leapfrog steps only");
-    constexpr bool kImg = MODE == kImage;
+    static_assert(MODE == kPlain || !FIRST, "save / image / Born modes: leapfrog steps only");
+    constexpr bool kImg = MODE == kImage, kBrn = MODE == kBorn;
+    constexpr bool kTwo = kImg || kBrn;  // the two extra rings: q and acc (image) or q and dm (Born)
     T u1[4][R], u2[2][R], mm[2][R];
-    T qq[kImg ? 2 : 1][kImg ? R : 1], aa[kImg ? 2 : 1][kImg ? R : 1];
+    T qq[kTwo ? 2 : 1][kTwo ? R : 1], aa[kTwo ? 2 : 1][kTwo ? R : 1];
     T hv[2];
-    if constexpr (kImg) {
-        const auto rQ = prs(p.q, ib), rA = prs(p.acc, ib);
+    if constexpr (kTwo) {
+        const auto rQ = prs(p.q, ib), rA = prs(kBrn ? p.dm : p.acc, ib);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             qq[0][r] = bld<T, 2>(rQ, os[r]);
@@ -210,9 +218,9 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
                 mm[H1][r] = bld<T, kMAux>(rM, os[r]);
             }
             hv[H1] = bld<T>(rH, hoff);
-            if constexpr (kImg) {
+            if constexpr (kTwo) {
                 const auto rQ = plane_rsrc(p.q + (i64(i + d1) * si - p.poff), nb);
-                const auto rA = plane_rsrc(p.acc + (i64(i + d1) * si - p.poff), nb);
+                const auto rA = plane_rsrc((kBrn ? p.dm : p.acc) + (i64(i + d1) * si - p.poff), nb);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     qq[H1][r] = bld<T, 2>(rQ, os[r]);
@@ -231,7 +239,7 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
         const T gxi = gxn;
         if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
         T vv[R];
-        T xv[MODE == kPlain ? 1 : R];  // kSave: lap; kImage: the new acc
+        T xv[MODE == kSave || kImg ? R : 1];  // kSave: lap; kImage: the new acc
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int lr = 1 + w * R + r;
@@ -252,6 +260,15 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
                 const T half_m = T(0.5) * mm[H0][r];  // exact
                 vv[r] = taylor_first(c, lap, half_m);
                 if constexpr (TAPER) vv[r] = (gxi * gyz[r]) * vv[r];
+            } else if constexpr (kBrn) {
+#pragma clang fp contract(off)
+                const T pr = aa[H0][r] * qq[H0][r];  // dm q, rounded before the add
+                if constexpr (TAPER) {
+                    const T g = gxi * gyz[r];
+                    vv[r] = g * (leapfrog(c, g * u2[H0][r], lap, mm[H0][r]) + pr);
+                } else {
+                    vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]) + pr;
+                }
             } else if constexpr (TAPER) {
 #pragma clang fp contract(off)
                 const T g = gxi * gyz[r];
@@ -272,7 +289,7 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
 #pragma unroll
                     for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
                 }
-            if constexpr (MODE != kPlain) {
+            if constexpr (MODE == kSave || kImg) {
                 const auto rx = prs(MODE == kSave ? p.lap_out : p.acc, i);
 #pragma unroll
                 for (int r = 0; r < R; ++r) bst<kStAux>(xv[r], rx, os[r]);
@@ -415,14 +432,15 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
     constexpr int kMAux = 2;   // non-temporal m (read once per step)
     constexpr int kStAux = 2;  // non-temporal stores (write-once stream)
 
-    static_assert(MODE == kPlain || !FIRST, "save / image modes: leapfrog steps only");
+    static_assert(MODE == kPlain || !FIRST, "save / image / Born modes: leapfrog steps only");
     static_assert(M == 2 || M == 4, "orders 4 and 8");
-    constexpr bool kImg = MODE == kImage;
+    constexpr bool kImg = MODE == kImage, kBrn = MODE == kBorn;
+    constexpr bool kTwo = kImg || kBrn;  // the two extra rings: q and acc (image) or q and dm (Born)
     T u1[NS][R], u2[2][R], mm[2][R];
-    T qq[kImg ? 2 : 1][kImg ? R : 1], aa[kImg ? 2 : 1][kImg ? R : 1];
+    T qq[kTwo ? 2 : 1][kTwo ? R : 1], aa[kTwo ? 2 : 1][kTwo ? R : 1];
     T hv[2][NH];
-    if constexpr (kImg) {
-        const auto rQ = prs(p.q, ib), rA = prs(p.acc, ib);
+    if constexpr (kTwo) {
+        const auto rQ = prs(p.q, ib), rA = prs(kBrn ? p.dm : p.acc, ib);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             qq[0][r] = bld<T, 2>(rQ, os[r]);
@@ -494,9 +512,9 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
             }
 #pragma unroll
             for (int h = 0; h < NH; ++h) hv[H1][h] = bld<T>(rH, hoff[h]);
-            if constexpr (kImg) {
+            if constexpr (kTwo) {
                 const auto rQ = plane_rsrc(p.q + (i64(i + d1) * si - p.poff), nb);
-                const auto rA = plane_rsrc(p.acc + (i64(i + d1) * si - p.poff), nb);
+                const auto rA = plane_rsrc((kBrn ? p.dm : p.acc) + (i64(i + d1) * si - p.poff), nb);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     qq[H1][r] = bld<T, 2>(rQ, os[r]);
@@ -521,7 +539,7 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
         const T gxi = gxn;
         if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
         T vv[R];
-        T xv[MODE == kPlain ? 1 : R];  // kSave: lap; kImage: the new acc
+        T xv[MODE == kSave || kImg ? R : 1];  // kSave: lap; kImage: the new acc
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int lr = M + w * R + r;
@@ -549,6 +567,14 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
                 const T half_m = T(0.5) * mm[H0][r];  // exact
                 vv[r] = taylor_first(c, lap, half_m);
                 if constexpr (TAPER) vv[r] = (gxi * gyz[r]) * vv[r];
+            } else if constexpr (kBrn) {
+                const T pr = aa[H0][r] * qq[H0][r];  // dm q, rounded before the add
+                if constexpr (TAPER) {
+                    const T g = gxi * gyz[r];
+                    vv[r] = g * (leapfrog(c, g * u2[H0][r], lap, mm[H0][r]) + pr);
+                } else {
+                    vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]) + pr;
+                }
             } else if constexpr (TAPER) {
                 const T g = gxi * gyz[r];
                 vv[r] = g * leapfrog(c, g * u2[H0][r], lap, mm[H0][r]);
@@ -567,7 +593,7 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
 #pragma unroll
                     for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
                 }
-            if constexpr (MODE != kPlain) {
+            if constexpr (MODE == kSave || kImg) {
                 const auto rx = prs(MODE == kSave ? p.lap_out : p.acc, i);
 #pragma unroll
                 for (int r = 0; r < R; ++r) bst<kStAux>(xv[r], rx, os[r]);
@@ -622,6 +648,9 @@ void (*march_mh_kernel(bool first, bool taper, int mode))(const MediumParamsH<T>
     if (mode == kImage)
         return taper ? k_march_mh<T, M, false, mh_rows<T, M, kImage>(), true, kImage>
                      : k_march_mh<T, M, false, mh_rows<T, M, kImage>(), false, kImage>;
+    if (mode == kBorn)
+        return taper ? k_march_mh<T, M, false, mh_rows<T, M, kBorn>(), true, kBorn>
+                     : k_march_mh<T, M, false, mh_rows<T, M, kBorn>(), false, kBorn>;
     constexpr int RP = mh_rows<T, M, kPlain>();
     if (first) return taper ? k_march_mh<T, M, true, RP, true> : k_march_mh<T, M, true, RP, false>;
     return taper ? k_march_mh<T, M, false, RP, true> : k_march_mh<T, M, false, RP, false>;
@@ -629,7 +658,10 @@ void (*march_mh_kernel(bool first, bool taper, int mode))(const MediumParamsH<T>
 
 template <class T, int M>
 int march_mh_rows(int mode) {
-    return mode == kSave ? mh_rows<T, M, kSave>() : mode == kImage ? mh_rows<T, M, kImage>() : mh_rows<T, M, kPlain>();
+    return mode == kSave    ? mh_rows<T, M, kSave>()
+           : mode == kImage ? mh_rows<T, M, kImage>()
+           : mode == kBorn  ? mh_rows<T, M, kBorn>()
+                            : mh_rows<T, M, kPlain>();
 }
 
 // ---- variable density: k_march_mb ----------------------------------------------------------
@@ -729,13 +761,14 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
     constexpr int kMAux = 2;   // non-temporal m (read once per step)
     constexpr int kStAux = 2;  // non-temporal stores (write-once stream)
 
-    static_assert(MODE == kPlain || !FIRST, "save / image modes: leapfrog steps only");
-    constexpr bool kImg = MODE == kImage;
+    static_assert(MODE == kPlain || !FIRST, "save / image / Born modes: leapfrog steps only");
+    constexpr bool kImg = MODE == kImage, kBrn = MODE == kBorn;
+    constexpr bool kTwo = kImg || kBrn;  // the two extra rings: q and acc (image) or q and dm (Born)
     T u1[4][R], bb[4][R], u2[2][R], mm[2][R];
-    T qq[kImg ? 2 : 1][kImg ? R : 1], aa[kImg ? 2 : 1][kImg ? R : 1];
+    T qq[kTwo ? 2 : 1][kTwo ? R : 1], aa[kTwo ? 2 : 1][kTwo ? R : 1];
     T hv[2], hb[2];
-    if constexpr (kImg) {
-        const auto rQ = prs(p.q, ib), rA = prs(p.acc, ib);
+    if constexpr (kTwo) {
+        const auto rQ = prs(p.q, ib), rA = prs(kBrn ? p.dm : p.acc, ib);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             qq[0][r] = bld<T, 2>(rQ, os[r]);
@@ -807,9 +840,9 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
             }
             hv[H1] = bld<T>(rH, hoff);
             hb[H1] = bld<T>(bH, hoff);
-            if constexpr (kImg) {
+            if constexpr (kTwo) {
                 const auto rQ = plane_rsrc(p.q + (i64(i + d1) * si - p.poff), nb);
-                const auto rA = plane_rsrc(p.acc + (i64(i + d1) * si - p.poff), nb);
+                const auto rA = plane_rsrc((kBrn ? p.dm : p.acc) + (i64(i + d1) * si - p.poff), nb);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     qq[H1][r] = bld<T, 2>(rQ, os[r]);
@@ -834,7 +867,7 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
         const T gxi = gxn;
         if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
         T vv[R];
-        T xv[MODE == kPlain ? 1 : R];  // kSave: D_b u1; kImage: the new acc
+        T xv[MODE == kSave || kImg ? R : 1];  // kSave: D_b u1; kImage: the new acc
 #pragma unroll
         for (int r = 0; r < R; ++r) {
 #pragma clang fp contract(off)
@@ -861,6 +894,14 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
                 const T half_m = T(0.5) * mm[H0][r];  // exact
                 vv[r] = taylor_first(c, lap, half_m);
                 if constexpr (TAPER) vv[r] = (gxi * gyz[r]) * vv[r];
+            } else if constexpr (kBrn) {
+                const T pr = aa[H0][r] * qq[H0][r];  // dm q, rounded before the add
+                if constexpr (TAPER) {
+                    const T g = gxi * gyz[r];
+                    vv[r] = g * (leapfrog(c, g * u2[H0][r], lap, mm[H0][r]) + pr);
+                } else {
+                    vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]) + pr;
+                }
             } else if constexpr (TAPER) {
                 const T g = gxi * gyz[r];
                 vv[r] = g * leapfrog(c, g * u2[H0][r], lap, mm[H0][r]);
@@ -880,7 +921,7 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
 #pragma unroll
                     for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
                 }
-            if constexpr (MODE != kPlain) {
+            if constexpr (MODE == kSave || kImg) {
                 const auto rx = prs(MODE == kSave ? p.lap_out : p.acc, i);
 #pragma unroll
                 for (int r = 0; r < R; ++r) bst<kStAux>(xv[r], rx, os[r]);
@@ -912,6 +953,7 @@ template <class T>
 void (*march_mb_kernel(bool first, bool taper, int mode))(const MediumParamsB<T>) {
     if (mode == kSave) return taper ? k_march_mb<T, false, 4, true, kSave> : k_march_mb<T, false, 4, false, kSave>;
     if (mode == kImage) return taper ? k_march_mb<T, false, 4, true, kImage> : k_march_mb<T, false, 4, false, kImage>;
+    if (mode == kBorn) return taper ? k_march_mb<T, false, 4, true, kBorn> : k_march_mb<T, false, 4, false, kBorn>;
     if (first) return taper ? k_march_mb<T, true, 4, true> : k_march_mb<T, true, 4, false>;
     return taper ? k_march_mb<T, false, 4, true> : k_march_mb<T, false, 4, false>;
 }
@@ -1001,7 +1043,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant, const T* gx,
                         const T* gy, const T* gz, T* lap_out, const T* q, T* acc, int order, const int* mirror,
-                        const T* b) {
+                        const T* b, const T* dm) {
     W3D_REQUIRE(order == 2 || order == 4 || order == 8, "space order must be 2, 4 or 8, not " + std::to_string(order));
     W3D_REQUIRE(!b || order == 2, "variable density (b) exists for space order 2 only");
     const int M = order / 2;
@@ -1014,13 +1056,26 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     W3D_REQUIRE(gv.sj >= gv.Z + 2 * gv.G && gv.si >= i64(gv.Y + 2 * gv.G) * gv.sj, "strides smaller than the grid");
     if (variant < 0) variant = medium_variant();
     W3D_REQUIRE(!b || variant == 1, "variable density (b) is instantiated for the default variant only (nt, 4 rows per lane)");
-    const bool save = lap_out != nullptr, image = q || acc;
+    // Born mode: q and dm without acc; q with neither acc nor dm stays an incomplete image mode
+    const bool born = dm != nullptr;
+    W3D_REQUIRE(!born || q, "Born mode needs q beside dm");
+    W3D_REQUIRE(!born || (!lap_out && !acc), "Born mode (q, dm) cannot be combined with save or image mode");
+    const bool save = lap_out != nullptr, image = !born && (q || acc);
     W3D_REQUIRE(!image || (q && acc), "image mode needs both q and acc");
     W3D_REQUIRE(!(save && image), "save mode (lap_out) and image mode (q, acc) cannot be combined");
-    W3D_REQUIRE(!(save || image) || !first, "save / image modes: not on the Taylor start (first)");
-    W3D_REQUIRE(!(save || image) || variant == 1 || M > 1,
-                "save / image modes are instantiated for the default variant only (nt, 4 rows per lane)");
-    const int mode = save ? kSave : image ? kImage : kPlain;
+    W3D_REQUIRE(!(save || image || born) || !first, "save / image / Born modes: not on the Taylor start (first)");
+    W3D_REQUIRE(!(save || image || born) || variant == 1 || M > 1,
+                "save / image / Born modes are instantiated for the default variant only (nt, 4 rows per lane)");
+    if (born) {
+        // q and dm are read while u is written (own plane and wrap planes): no shared memory
+        const i64 span = i64(gv.X + 2 * gv.G - 1) * gv.si + i64(gv.Y + 2 * gv.G - 1) * gv.sj + gv.Z + 2 * gv.G;
+        auto overlaps = [&](const T* x) {
+            const std::uintptr_t u0 = std::uintptr_t(u), x0 = std::uintptr_t(x), n = std::uintptr_t(span) * sizeof(T);
+            return u0 < x0 + n && x0 < u0 + n;
+        };
+        W3D_REQUIRE(!overlaps(q) && !overlaps(dm), "Born mode: q or dm shares memory with u");
+    }
+    const int mode = save ? kSave : image ? kImage : born ? kBorn : kPlain;
     // reflecting faces of k_march_mh: (j_lo, j_hi, k_lo, k_hi), +-2^29 where there is none
     int mir[4] = {kNoMirror, -kNoMirror, kNoMirror, -kNoMirror};
     bool has[4] = {false, false, false, false};
@@ -1070,6 +1125,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     p.lap_out = lap_out;
     p.q = q;
     p.acc = acc;
+    p.dm = dm;
     const int tj_rows = kWaves * (M == 2   ? march_mh_rows<T, 2>(mode)
                                   : M == 4 ? march_mh_rows<T, 4>(mode)
                                   : (variant & 2) ? 2
@@ -1139,6 +1195,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
               : (first ? march_m_kernel<T, true, false>(variant) : march_m_kernel<T, false, false>(variant));
     if (save) kern = taper ? k_march_m<T, false, 4, true, true, kSave> : k_march_m<T, false, 4, true, false, kSave>;
     if (image) kern = taper ? k_march_m<T, false, 4, true, true, kImage> : k_march_m<T, false, 4, true, false, kImage>;
+    if (born) kern = taper ? k_march_m<T, false, 4, true, true, kBorn> : k_march_m<T, false, 4, true, false, kBorn>;
     hipLaunchKernelGGL(kern, dim3(total), dim3(kThreads), 0, s, p);
     HIP_OK(hipGetLastError());
 }
@@ -1162,7 +1219,7 @@ void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int
     template void launch_step_medium<T>(bool, const T*, const T*, const T*, T*, const GridView&,       \
                                         const Box*, int, int, int, const Wrap&, const double[3], u64*, \
                                         int, hipStream_t, int, const T*, const T*, const T*, T*,       \
-                                        const T*, T*, int, const int*, const T*);                      \
+                                        const T*, T*, int, const int*, const T*, const T*);            \
     template void launch_inject<T>(T*, const T*, const GridView&, const int*, const T*, int,           \
                                    const Wrap&, hipStream_t);                                          \
     template void launch_record<T>(const T*, const GridView&, const int*, T*, int, hipStream_t);

@@ -23,11 +23,20 @@ namespace wave3d {
 // damped values.
 //
 // Modes for the adjoint-state gradient (leapfrog steps with variant 1 only; every other
-// combination is rejected): save (lap_out non-null) also stores lap(u1), the value that entered
+// combination is rejected; q alone is an incomplete image mode): save (lap_out non-null) also stores lap(u1), the value that entered
 // the update, at the box nodes of lap_out; image (q and acc non-null) also does
 // acc = acc + u1 * q at the box nodes, the product rounded before the add. lap_out, q and acc
 // have the strides of u; nothing outside the boxes is written and the wrap applies to u alone.
 // u and err are those of the plain step bit for bit. Per node in fp64: 40 B (save), 56 B (image).
+//
+// Born mode (q and dm non-null, lap_out and acc null; leapfrog steps with variant 1 only, like
+// save / image): the step of linearised (Born) modelling, image mode's transpose. u1 and u2 are
+// levels of the perturbation field, q = lap of the background field (what save mode stored) and dm
+// the perturbation of the coefficient, both read once at the box nodes with the strides of u and
+// never written: u = ((2 u1 - u2) + m lap(u1)) + dm q, with the sponge
+// u = G (((2 u1 - G u2) + m lap(u1)) + dm q), the product dm q rounded before its add. The wrap,
+// err[0] and the non-finite flag are those of the plain step, of the Born-updated values; no store
+// beside u's. q and dm must not share memory with u. Per node in fp64: 48 B (56 B with b).
 //
 // Space order (order = 2, 4 or 8; half-width M = order / 2). Order 2 is the 7-point kernel above
 // and ignores `mirror`. Orders 4 and 8 run k_march_mh, a star stencil of 2M + 1 points per axis with
@@ -57,7 +66,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant = -1,
                         const T* gx = nullptr, const T* gy = nullptr, const T* gz = nullptr,
                         T* lap_out = nullptr, const T* q = nullptr, T* acc = nullptr, int order = 2,
-                        const int* mirror = nullptr, const T* b = nullptr);
+                        const int* mirror = nullptr, const T* b = nullptr, const T* dm = nullptr);
 
 // Central second-derivative weight c_d of the star stencil of `order` (2, 4, 8), d = 0 .. order / 2:
 // the double quotient of its two integers (order 4: -5/2, 4/3, -1/12; order 8: -205/72, 8/5, -1/5,

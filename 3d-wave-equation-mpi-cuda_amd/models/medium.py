@@ -601,6 +601,177 @@ class MediumSolver:
                                              forward_ms=ev[0].elapsed_time(ev[1]), reverse_ms=ev[2].elapsed_time(ev[3])))
 
 
+    # ---- Born (linearised) modelling and Gauss-Newton products -------------------------------
+
+    def born(self, dspeed2=None, dwavelet=None) -> "MediumBorn":
+        """Born (linearised) modelling, the Jacobian that :meth:`gradient` transposes: the change of the
+        traces, to first order, for a perturbation ``dspeed2`` of ``speed2`` (a scalar or ``(N+1)^3``,
+        finite, periodic in x, of any sign; the density stays fixed) and ``dwavelet``
+        ``[timesteps, len(sources)]`` of the wavelet. At least one of the two.
+
+        The background field and the perturbation field ``du`` run in lock step from rest
+        (``ops.reference.born_medium`` has the recurrence): ``dtraces[n, r] = du^n[x_r]``, row 0 is 0.
+        For any ``r`` of the traces' shape, ``(dtraces[1:] * r[1:]).sum()`` equals
+        ``(grad_speed2[:N] * dspeed2[:N]).sum() + (grad_wavelet * dwavelet).sum()`` of
+        ``gradient(traces - r)`` up to rounding.
+
+        "hip": nine levels (the rings of u and du, m, dm and one q level; ten with a density), checked
+        against the free device memory. Per step the background step runs in save mode into q and
+        the step of du reads it back in Born mode (``ops.kernels.step_medium``)."""
+        from ..ops import reference
+
+        p = self.problem
+        N, K = p.N, p.timesteps
+        if self.u0 is not None:
+            raise ValueError("born() starts from rest: u0 is not supported")
+        if not self.receivers:
+            raise ValueError("born() needs at least one receiver")
+        if dspeed2 is None and dwavelet is None:
+            raise ValueError("born() needs a perturbation: dspeed2, dwavelet or both")
+        ds = None if dspeed2 is None else reference.perturbation_field(dspeed2, N, "dspeed2")
+        dw = None
+        if dwavelet is not None:
+            if not self.sources:
+                raise ValueError("dwavelet needs sources")
+            dw = torch.as_tensor(dwavelet, dtype=torch.float64).detach().cpu()
+            if tuple(dw.shape) != (K, len(self.sources)):
+                raise ValueError(f"dwavelet must have shape {(K, len(self.sources))} (timesteps x sources), "
+                                 f"not {tuple(dw.shape)}")
+            if not bool(torch.isfinite(dw).all()):
+                raise ValueError("dwavelet must be finite")
+        return self._born_cpu(ds, dw) if self.backend == "cpu" else self._born_hip(ds, dw)
+
+    def _born_cpu(self, ds, dw) -> "MediumBorn":
+        import time
+
+        from ..ops import reference
+
+        p = self.problem
+        t0 = time.perf_counter()
+        tr, dtr, duf, mx = reference.born_medium(p.N, p.timesteps, p.speed2, ds, dw, sources=self.sources,
+                                                 wavelet=self.wavelet, receivers=self.receivers, taper=self.taper,
+                                                 L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
+                                                 order=p.space_order, density=p.density)
+        return MediumBorn(traces=tr, dtraces=dtr, du_final=duf, max_abs_du=mx,
+                          total_ms=(time.perf_counter() - t0) * 1e3,
+                          extra=dict(levels=None, space_order=p.space_order, density=p.density is not None))
+
+    def _born_hip(self, ds, dw) -> "MediumBorn":
+        import time
+
+        from ..ops import kernels, reference
+
+        p = self.problem
+        N, K, dt = p.N, p.timesteps, p.torch_dtype
+        if not torch.cuda.is_available():
+            raise RuntimeError("the hip backend needs a HIP device")
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else self.device)
+        c = reference.tables(N, K, (p.Lx, p.Ly, p.Lz), p.T, p.pi)[4]
+        h2 = (c["hx2"], c["hy2"], c["hz2"])
+        M, box, wrap, step_kw = self._layout()
+        with torch.cuda.device(dev):
+            level_bytes = kernels.level_bytes(N + 1 + 2 * M, N + 1, N + 1, dt)
+            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            nlev = born_levels(density=p.density is not None)
+            if nlev * level_bytes > free:
+                raise RuntimeError(f"born(): the schedule holds {nlev} levels = {nlev * level_bytes} bytes, but only "
+                                   f"{free} bytes of device memory are free")
+            t0 = time.perf_counter()
+
+            def level():
+                return kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev)
+
+            lv = [level() for _ in range(3)]
+            dl = [level() for _ in range(3)]
+            m, dm, q = level(), level(), level()
+            m.copy_(reference.medium_coefficient(p.speed2, c["tau"], N, dt, M, p.density))
+            if ds is not None:  # None: dm = 0, the scattering term adds zeros
+                dm.copy_(reference.medium_coefficient(ds, c["tau"], N, dt, M, p.density))
+            if p.density is not None:
+                bu = level()
+                bu.copy_(reference.buoyancy_field(p.density, N, dt, M))
+                step_kw = dict(step_kw, buoyancy=bu)
+            taper = None
+            if self.taper is not None:
+                taper = tuple(t.to(dev) for t in reference.taper_tables(self.taper, N, dt, M))
+            ent = reference.source_entries(self.sources, N, M)
+            S = len(self.sources)
+            cols = [s for _, s in ent]
+            g = reference.source_table(self.wavelet, K, S, c["hx"], c["hy"], c["hz"], dt)[:, cols].contiguous().to(dev)
+            dg = None
+            if dw is not None:
+                dg = reference.source_table(dw, K, S, c["hx"], c["hy"], c["hz"], dt)[:, cols].contiguous().to(dev)
+            src = kernels.source_nodes([nd for nd, _ in ent], lv[0])
+            rec = kernels.receiver_nodes([(i + M, j, k) for i, j, k in self.receivers], lv[0])
+            traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
+            dtraces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
+            stat = kernels.new_err(K + 1, device=dev)
+            dstat = kernels.new_err(K + 1, device=dev)
+            common = dict(h2=h2, stat_i=(M, N + M), wrap=wrap, taper=taper, **step_kw)
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            for n in range(1, K + 1):
+                u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
+                d1, d2, d = dl[(n + 2) % 3], dl[(n + 1) % 3], dl[n % 3]
+                first = n == 1
+                # the background step, saving q = lap u^{n-1} (save mode: the default variant)
+                kernels.step_medium(u1, u2, m, u, box, first=first, stat=stat[3 * n:3 * n + 3],
+                                    variant=self.variant if first else None, lap_out=None if first else q, **common)
+                kernels.inject(u, m, src, g[n - 1], wrap)
+                # the step of du with the scattering term dm q, then the perturbed source terms
+                kernels.step_medium(d1, d2, m, d, box, first=first, stat=dstat[3 * n:3 * n + 3],
+                                    variant=self.variant if first else None, born=None if first else (q, dm), **common)
+                kernels.inject(d, dm, src, g[n - 1], wrap)
+                if dg is not None:
+                    kernels.inject(d, m, src, dg[n - 1], wrap)
+                kernels.record(u, rec, traces[n])
+                kernels.record(d, rec, dtraces[n])
+            ev1.record()
+            ev1.synchronize()
+            for st, name in ((stat, "background"), (dstat, "perturbation")):  # the one read-back of the flags
+                flags = st[2::3].cpu()
+                if bool((flags != 0).any()):
+                    raise RuntimeError(f"born(): non-finite values in the {name} field at layer "
+                                       f"{int((flags != 0).nonzero()[0])}")
+            dec = kernels.decode_err(dstat)
+            mx = [0.0] + [dec[n][0] for n in range(1, K + 1)]  # du^0 = 0
+            duf = dl[K % 3][M:N + 1 + M].cpu()
+            tr, dtr = traces.cpu(), dtraces.cpu()
+            return MediumBorn(traces=tr, dtraces=dtr, du_final=duf, max_abs_du=mx,
+                              total_ms=(time.perf_counter() - t0) * 1e3,
+                              extra=dict(levels=nlev, space_order=p.space_order, density=p.density is not None,
+                                         loop_ms=ev0.elapsed_time(ev1)))
+
+    def gauss_newton(self, dspeed2=None, dwavelet=None, *, segment: int | None = None) -> "MediumGradient":
+        """The Gauss-Newton Hessian applied to a perturbation: one :meth:`born` run, then
+        :meth:`gradient` with ``observed = traces - dtraces``, so that the residuals are ``dtraces`` and
+        ``grad_speed2``, ``grad_wavelet`` are ``J^T J [dspeed2; dwavelet]`` (``misfit`` is
+        ``1/2 |dtraces[1:]|^2``). ``segment``: the checkpoint schedule of :meth:`gradient`. ``extra``
+        also carries the Born run's ``dtraces``. Both backends form ``observed`` on the host alike."""
+        b = self.born(dspeed2, dwavelet)
+        r = self.gradient(b.traces - b.dtraces, segment=segment)
+        r.extra["dtraces"] = b.dtraces
+        r.extra["born_ms"] = b.total_ms
+        return r
+
+
+@dataclass
+class MediumBorn:
+    traces: torch.Tensor     # [K+1, R], those of run()
+    dtraces: torch.Tensor    # [K+1, R], the first-order change of the traces; row 0 is 0
+    du_final: torch.Tensor   # (N+1)^3, the perturbation field at the last layer
+    max_abs_du: list         # [K+1]: max |du| over the stencil nodes, before the step's source terms
+    total_ms: float          # wall time of the whole call
+    extra: dict = field(default_factory=dict)  # levels; "hip" also loop_ms, the device time of the time loop
+
+
+def born_levels(density: bool = False) -> int:
+    """Number of grid levels the "hip" schedule of :meth:`MediumSolver.born` holds: the rings of the
+    background and the perturbation field (3 each), m, dm and one q level; ``density``: one more, the
+    buoyancy."""
+    return 9 + bool(density)
+
+
 @dataclass
 class MediumGradient:
     misfit: float               # J = 1/2 sum_{n >= 1} sum_r (trace - observed)^2

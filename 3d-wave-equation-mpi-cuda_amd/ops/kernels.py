@@ -355,7 +355,7 @@ def _check_taper(taper, u) -> list[int]:
 
 def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None, chunk: int = 0,
                 variant: str | None = None, taper=None, lap_out=None, image=None, order: int = 2,
-                mirror=None, buoyancy=None) -> None:
+                mirror=None, buoyancy=None, born=None) -> None:
     """One layer of ``u_tt = c^2 (lap u + f)`` over ``boxes``: ``u = (2 u1 - u2) + m lap(u1)``, on
     the Taylor start (``first``) ``u = u1 + (0.5 m) lap(u1)``, with ``m = c^2 tau^2`` per node.
 
@@ -377,6 +377,15 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     nodes, the product rounded before the add. These grids match ``u`` in shape, dtype, device and
     strides; nothing outside the boxes is written and the wrap applies to ``u`` alone. Both modes
     exist for leapfrog steps (``first=False``) of the default variant only and cannot be combined.
+
+    ``born = (q, dm)`` (Born mode, image mode's transpose): the step of linearised modelling on the
+    levels ``u1``, ``u2`` of a perturbation field, ``u = ((2 u1 - u2) + m lap(u1)) + dm q``, with the
+    sponge ``u = G (((2 u1 - G u2) + m lap(u1)) + dm q)``; ``q`` is the Laplacian of the background
+    field (what ``lap_out`` received) and ``dm`` the perturbation of ``m``, the product rounded before
+    its add. Both are read at the box nodes and never written; the wrap and ``stat`` are those of the
+    plain step, of the updated values. They match ``u`` in shape, dtype, device and strides and must
+    not share memory with it. For leapfrog steps of the default variant only, and not together with
+    ``lap_out`` or ``image``.
 
     ``order`` = 2 (the 7-point Laplacian: the kernels above, ``mirror`` is not used), 4 or 8: the star
     stencil of half-width M = order / 2 (``k_march_mh``; ``ops.reference.laplace_star`` has the
@@ -409,6 +418,20 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
         if not isinstance(buoyancy, torch.Tensor):
             raise ValueError("buoyancy must be a tensor")
         variant = "nt"
+    if born is not None:
+        if lap_out is not None or image is not None:
+            raise ValueError("Born mode (born) cannot be combined with save mode (lap_out) or image mode (image)")
+        if first:
+            raise ValueError("Born mode: not on the Taylor start (first=True)")
+        if variant not in (None, "nt"):
+            raise ValueError(f"Born mode exists for the default variant only, not {variant!r}")
+        if order == 2:
+            variant = "nt"
+        if len(born) != 2:
+            raise ValueError("born = (q, dm)")
+        if not all(isinstance(t, torch.Tensor) for t in born):
+            raise ValueError("q and dm must be tensors")
+        extra = list(born)
     if lap_out is not None or image is not None:
         if lap_out is not None and image is not None:
             raise ValueError("save mode (lap_out) and image mode (image) cannot be combined")
@@ -429,6 +452,12 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     if buoyancy is not None:
         extra = extra + [buoyancy]
     gv = _check_grid_strided(u1, u2, m, u, *extra)
+    if born is not None:
+        u_0, u_1 = _grid_span(u)
+        for t, name in zip(born, ("q", "dm")):
+            t0, t1 = _grid_span(t)
+            if u_0 < t1 and t0 < u_1:
+                raise ValueError(f"Born mode: {name} shares memory with u")
     if isinstance(boxes[0], int):
         boxes = [boxes]
     if not 1 <= len(boxes) <= 7:
@@ -453,8 +482,10 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     fn(bool(first), u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, bl, int(stat_i[0]),
        int(stat_i[1]), w, [float(v) for v in h2], stat.data_ptr(), int(chunk), _stream(),
        _MEDIUM_VARIANTS[variant], *gp, lap_out.data_ptr() if lap_out is not None else 0,
-       *((image[0].data_ptr(), image[1].data_ptr()) if image is not None else (0, 0)), int(order), mir,
-       buoyancy.data_ptr() if buoyancy is not None else 0)
+       *((image[0].data_ptr(), image[1].data_ptr()) if image is not None
+         else (born[0].data_ptr(), 0) if born is not None else (0, 0)), int(order), mir,
+       buoyancy.data_ptr() if buoyancy is not None else 0,
+       born[1].data_ptr() if born is not None else 0)
 
 
 def _grid_span(t: torch.Tensor) -> tuple[int, int]:

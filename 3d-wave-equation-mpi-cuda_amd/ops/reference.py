@@ -341,7 +341,7 @@ def _lap_box(u1, box, hx2, hy2, hz2, order: int, mirror, buoyancy=None):
 
 
 def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None, order: int = 2,
-                mirror=None, buoyancy=None) -> torch.Tensor:
+                mirror=None, buoyancy=None, born=None) -> torch.Tensor:
     """Layer update on ``box`` with the per-node coefficient ``m = c^2 tau^2``: the Taylor start
     ``c + (0.5 m) lap`` or ``(2c - u2) + m lap``; returns the updated box values.
 
@@ -353,17 +353,33 @@ def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None, order
 
     taper = (gx, gy, gz), 1-D factors in (0, 1] per axis in storage indexing (the lengths of the
     grid's axes): the damped leapfrog of an absorbing sponge with ``G = gx (gy gz)`` per node,
-    ``G (c + (0.5 m) lap)`` or ``G ((2c - G u2) + m lap)``, every operation rounded on its own."""
+    ``G (c + (0.5 m) lap)`` or ``G ((2c - G u2) + m lap)``, every operation rounded on its own.
+
+    born = (q_box, dm): the step of Born (linearised) modelling on a perturbation field, leapfrog
+    steps only: ``((2c - u2) + m lap) + dm q`` or ``G (((2c - G u2) + m lap) + dm q)``, the product
+    rounded before its add. ``q_box`` = the Laplacian of the background field on the box, as
+    ``_lap_box`` returns it; ``dm`` = the perturbation of m, a grid like m."""
     if order not in STAR_WEIGHTS:
         raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
     i0, i1, j0, j1, k0, k1 = box
+    sc = None
+    if born is not None:
+        if first:
+            raise ValueError("Born mode: not on the Taylor start (first=True)")
+        q_box, dm = born
+        want = (i1 - i0 + 1, j1 - j0 + 1, k1 - k0 + 1)
+        if tuple(q_box.shape) != want or tuple(dm.shape) != tuple(u1.shape):
+            raise ValueError(f"born = (q_box, dm): q_box must have the box's shape {want} and dm the grid's "
+                             f"{tuple(u1.shape)}, not {tuple(q_box.shape)} and {tuple(dm.shape)}")
+        sc = dm[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1] * q_box
     lap = _lap_box(u1, box, hx2, hy2, hz2, order, mirror, buoyancy)
     c = u1[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
     mb = m[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]
     if taper is None:
         if first:
             return c + (0.5 * mb) * lap
-        return (2 * c - u2[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]) + mb * lap
+        v = (2 * c - u2[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]) + mb * lap
+        return v if sc is None else v + sc
     gx, gy, gz = taper
     for t, n in zip(taper, u1.shape):
         if t.dim() != 1 or t.numel() != n or t.dtype != u1.dtype:
@@ -371,7 +387,8 @@ def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None, order
     G = gx[i0:i1 + 1, None, None] * (gy[None, j0:j1 + 1, None] * gz[None, None, k0:k1 + 1])
     if first:
         return G * (c + (0.5 * mb) * lap)
-    return G * ((2 * c - G * u2[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]) + mb * lap)
+    v = (2 * c - G * u2[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1]) + mb * lap
+    return G * (v if sc is None else v + sc)
 
 
 def max_abs_field(u: torch.Tensor, init: float = -100.0) -> float:
@@ -831,3 +848,102 @@ def gradient_medium_density(N: int, K: int, speed2, observed, *, sources=(), wav
         gd = finish_gradient_density(r["acc"], r["accb"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"],
                                      speed2, density, r["M"])
         return r["J"], grad, gw, r["traces"], gd
+
+
+# ---- Born (linearised) modelling of the medium solver ---------------------------------------
+#
+# The Jacobian itself, where the adjoint above is its transpose. With the forward scheme
+#   u^1 = m g[0] e_s,   u^n = G ((2 u^{n-1} - G u^{n-2}) + m L u^{n-1}) + m g[n-1] e_s,
+# a perturbation ds of speed2 at fixed density changes m by dm = medium_coefficient(ds, ...) (m is
+# linear in speed2) and a perturbation dw of the wavelet changes g by dg = source_table(dw, ...).
+# To first order, with q^{n-1} = L u^{n-1} (q^0 = 0 from rest),
+#   du^1 = dm g[0] e_s + m dg[0] e_s,
+#   du^n = G (((2 du^{n-1} - G du^{n-2}) + m L du^{n-1}) + dm q^{n-1}) + dm g[n-1] e_s + m dg[n-1] e_s:
+# the forward step on du with the scattering term dm q inside the sponge factor (step_medium's
+# ``born``) and the perturbed source terms outside, like the source term itself. dtraces[n, r] =
+# du^n[x_r] is the directional derivative of the traces, and for any r [K+1, R]
+#   (dtraces[1:] * r[1:]).sum() == (grad_speed2[:N] * ds[:N]).sum() + (grad_wavelet * dw).sum()
+# with the gradients of gradient_medium(observed = traces - r), in exact arithmetic.
+
+def perturbation_field(v, N: int, name: str) -> torch.Tensor:
+    """A model perturbation as a float64 CPU tensor: a scalar or ``(N+1)^3``, finite, of any sign,
+    periodic in x."""
+    s = torch.as_tensor(v, dtype=torch.float64).cpu()
+    n1 = N + 1
+    if s.dim() != 0 and tuple(s.shape) != (n1, n1, n1):
+        raise ValueError(f"{name} must be a scalar or have shape {(n1, n1, n1)}, not {tuple(s.shape)}")
+    bad = ~torch.isfinite(s)
+    if bool(bad.any()):
+        v = s[bad].flatten()[0].item() if s.dim() else s.item()
+        raise ValueError(f"{name} must be finite, found {v}")
+    if s.dim() != 0 and not torch.equal(s[0], s[N]):
+        j, k = (int(x) for x in (s[0] != s[N]).nonzero()[0])
+        raise ValueError(f"{name} must be periodic in x: {name}[0,{j},{k}] = {s[0, j, k].item()} but "
+                         f"{name}[{N},{j},{k}] = {s[N, j, k].item()}")
+    return s
+
+
+def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=(), wavelet=None, receivers=(),
+                taper=None, L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
+                order: int = 2, density=None):
+    """Born modelling from rest: ``solve_medium``'s run and, in lock step, the first-order change of
+    its field for the perturbations ``dspeed2`` of speed2 (a scalar or ``(N+1)^3``, finite, periodic
+    in x, of any sign; the density stays fixed) and ``dwavelet`` ``[K, S]`` of the wavelet; at least
+    one of the two. Returns (traces ``[K+1, R]``, those of ``solve_medium`` bit for bit; dtraces
+    ``[K+1, R]``, row 0 zero; du^K ``(N+1)^3``; max |du| per layer ``[K+1]`` like ``solve_medium``'s).
+
+    Per step: the background step, the Born step ``step_medium(born=(q, dm))`` with q the Laplacian
+    of the background level it started from, then per source node ``du += dm g[n-1, s]`` and
+    ``du += m dg[n-1, s]`` (each a rounded product, then the add), the wrap, the sample. Step 1 has
+    no Born term."""
+    if dspeed2 is None and dwavelet is None:
+        raise ValueError("born_medium needs a perturbation: dspeed2, dwavelet or both")
+    c = tables(N, K, L, T, pi)[4]
+    M, box, mirror = _medium_layout(N, order)
+    tt = None if taper is None else taper_tables(taper, N, dtype, M)
+    m = medium_coefficient(speed2, c["tau"], N, dtype, M, density)
+    if dspeed2 is None:
+        dm = torch.zeros_like(m)
+    else:
+        dm = medium_coefficient(perturbation_field(dspeed2, N, "dspeed2"), c["tau"], N, dtype, M, density)
+    bu = _buoyancy(density, N, dtype, order, M)
+    ent = source_entries(sources, N, M)
+    S = len(sources)
+    g = source_table(wavelet, K, S, c["hx"], c["hy"], c["hz"], dtype)
+    dg = None
+    if dwavelet is not None:
+        dw = torch.as_tensor(dwavelet, dtype=torch.float64)
+        if tuple(dw.shape) != (K, S):
+            raise ValueError(f"dwavelet must have shape {(K, S)} (timesteps x sources), not {tuple(dw.shape)}")
+        dg = source_table(dw, K, S, c["hx"], c["hy"], c["hz"], dtype)
+    shape = (N + 1 + 2 * M, N + 1, N + 1)
+    own = (slice(M, N + 1 + M), slice(1, N), slice(1, N))
+    lv = [torch.zeros(shape, dtype=dtype) for _ in range(3)]
+    dl = [torch.zeros(shape, dtype=dtype) for _ in range(3)]
+    rec = [(i + M, j, k) for i, j, k in receivers]
+    traces = torch.zeros(K + 1, len(rec), dtype=dtype)
+    dtraces = torch.zeros(K + 1, len(rec), dtype=dtype)
+    kw = dict(hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt, order=order, mirror=mirror, buoyancy=bu)
+    mx = [0.0]  # du^0 = 0
+    for n in range(1, K + 1):
+        u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
+        d1, d2, d = dl[(n + 2) % 3], dl[(n + 1) % 3], dl[n % 3]
+        q = _lap_box(u1, box, c["hx2"], c["hy2"], c["hz2"], order, mirror, bu) if n >= 2 else None
+        u.zero_()
+        u[own] = step_medium(u1, u2, m, box, first=n == 1, **kw)
+        for nd, s in ent:
+            u[nd] = u[nd] + m[nd] * g[n - 1, s]
+        _wrap_x(u, N, M)
+        dvals = step_medium(d1, d2, m, box, first=n == 1, born=None if n == 1 else (q, dm), **kw)
+        mx.append(max_abs_field(dvals))
+        d.zero_()
+        d[own] = dvals
+        for nd, s in ent:
+            d[nd] = d[nd] + dm[nd] * g[n - 1, s]
+            if dg is not None:
+                d[nd] = d[nd] + m[nd] * dg[n - 1, s]
+        _wrap_x(d, N, M)
+        for r, nd in enumerate(rec):
+            traces[n, r] = u[nd]
+            dtraces[n, r] = d[nd]
+    return traces, dtraces, dl[K % 3][M:N + 1 + M].clone(), mx

@@ -7,6 +7,8 @@
     python tools/bench_medium.py --gradient [--N 512] [--steps 100] [--dtypes fp64,fp32] [--segment 10]
                                  [--order 2,8] [--kernels-only] [--density]
     python tools/bench_medium.py --gradient --density --wrt-density [--N 512] [--steps 100] [--segment 10]
+    python tools/bench_medium.py --born [--N 512] [--steps 100] [--dtypes fp64,fp32] [--order 2,4,8]
+                                 [--kernels-only] [--density]
 
 For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
 and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
@@ -24,6 +26,13 @@ the image step (+ q, acc read, acc written: 56 B), `--repeat` rounds of 20 launc
 alternating inside each round, with and without a sponge of 16 nodes; then, alternating as well,
 one forward run() and gradient() with every q stored (segment = steps) and with `--segment`: the
 device time of the passes beside run()'s time loop, and the wall time of the whole call.
+
+`--born` measures Born (linearised) modelling instead (MediumSolver.born), with `--gradient`'s layout:
+ms/step of the plain step, the save step and the Born step (+ q, dm read: 48 B per node in fp64
+against 32, so the byte count predicts 1.5 times the plain step), the three alternating inside each
+round, with and without the sponge; then, alternating as well, one forward run() and one born()
+(per step a save step, a Born step, the injections and two records): the device time of the time
+loops. `--kernels-only` skips the runs; `--order` and `--density` as for `--gradient`.
 
 `--order 2,4,8` runs every configuration at each of the space orders (4 and 8: k_march_mh), the
 orders alternating inside each repeat in the one job, and reports per row the order and the ratio
@@ -210,11 +219,12 @@ def gradient_bench(a) -> int:
     rho = two_layer_density(N) if a.density else None
     nodes = float(N + 1) ** 3
     out = {"N": N, "steps": K, "orders": orders, "device": torch.cuda.get_device_name(0), "kernels": [],
-           "gradient": []}
+           "born" if a.born else "gradient": []}
+    third = "born" if a.born else "image"
     if a.density:
         out["density"] = "two layers: 1, 2"
         if not a.kernels_only:
-            raise SystemExit("--gradient --density: the kernel rounds only (add --kernels-only)")
+            raise SystemExit("--gradient / --born with --density: the kernel rounds only (add --kernels-only)")
         orders = orders + ["2d"]  # the density step at order 2, a configuration of its own
     dev = torch.device("cuda", 0)
     for dtype in a.dtypes.split(","):
@@ -248,16 +258,19 @@ def gradient_bench(a) -> int:
         stat = kernels.new_err(1, device=dev)
         reps = 20
         for tp_name in ("", "sponge"):
-            modes = ("plain", "save", "image")
+            modes = ("plain", "save", third)
             ms = {(k, o): [] for k in modes for o in orders}
             for rnd in range(a.repeat + 1):  # round 0 warms up
                 for name in modes:
                     for o in orders:  # the orders alternate inside each round
                         S = sets[o]
                         u1, u2, m, u, x, q = S["lv"]
-                        kw = {"plain": {}, "save": {"lap_out": x}, "image": {"image": (q, x)}}[name]
+                        kw = {"plain": {}, "save": {"lap_out": x}, "image": {"image": (q, x)},
+                              "born": {"born": (q, x)}}[name]
                         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         x.zero_()
+                        if name == "born":  # x is dm here: smooth values instead of zeros
+                            x.copy_(q)
                         e0.record()
                         for _ in range(reps):
                             kernels.step_medium(u1, u2, m, u, S["box"], first=False, h2=h2, stat=stat,
@@ -268,7 +281,7 @@ def gradient_bench(a) -> int:
                         if rnd:
                             ms[(name, o)].append(e0.elapsed_time(e1) / reps)
             for o in orders:
-                for name, bpn in (("plain", 4), ("save", 5), ("image", 7)):
+                for name, bpn in (("plain", 4), ("save", 5), ("born", 6) if a.born else ("image", 7)):
                     best = min(ms[(name, o)])
                     if o == "2d":
                         bpn += 1  # the buoyancy stream
@@ -289,6 +302,35 @@ def gradient_bench(a) -> int:
         del sets, lv, u1, u2, m, u, x, q, S
         torch.cuda.empty_cache()
         if a.kernels_only:
+            continue
+
+        if a.born:  # born() beside one forward run(), per order
+            w = wave3d.ricker(4.0, 0.25, K, probs[orders[0]].tau).reshape(K, 1)
+            mid = N // 2
+            sols = {o: wave3d.MediumSolver(probs[o], "hip", sources=[(mid, mid, mid)], wavelet=w,
+                                           receivers=[(mid - K // 5, mid, mid), (mid, mid - K // 4, mid + 3)],
+                                           taper=sponge) for o in orders}
+            ds = 0.01 * speed2
+            rows = {(n, o): [] for n in ("run", "born") for o in orders}
+            for rnd in range(a.repeat + 1):  # round 0 warms up
+                for name in ("run", "born"):
+                    for o in orders:
+                        if name == "run":
+                            ms_loop = sols[o].run().total_ms
+                        else:
+                            r = sols[o].born(ds)
+                            assert math.isfinite(float(r.dtraces.abs().max())) and float(r.dtraces.abs().max()) > 0
+                            ms_loop = r.extra["loop_ms"]
+                            del r
+                        if rnd:
+                            rows[(name, o)].append(round(ms_loop, 2))
+                        print(f"bench_medium: {dtype} order {o} {name}: {ms_loop:.2f} ms", file=sys.stderr, flush=True)
+                        torch.cuda.empty_cache()
+            for o in orders:
+                run_ms, born_ms = min(rows[("run", o)]), min(rows[("born", o)])
+                out["born"].append({"dtype": dtype, "order": o, "run_loop_ms": run_ms, "born_loop_ms": born_ms,
+                                    "born_vs_run": round(born_ms / run_ms, 3), "levels": wave3d.born_levels(),
+                                    "born_loop_ms_all": rows[("born", o)]})
             continue
 
         # gradient() beside one forward run(), per order
@@ -341,6 +383,7 @@ def main(argv=None) -> int:
     ap.add_argument("--taper", type=int, default=0, metavar="WIDTH",
                     help="also time the step with sponge_taper(prob, WIDTH)")
     ap.add_argument("--gradient", action="store_true", help="time the gradient's kernels and schedules instead")
+    ap.add_argument("--born", action="store_true", help="time the Born step and born() instead")
     ap.add_argument("--segment", type=int, default=10, help="--gradient: steps per checkpoint segment")
     ap.add_argument("--order", default="2", help="space orders to time, e.g. 2,4,8 (alternating inside each repeat)")
     ap.add_argument("--kernels-only", action="store_true", help="--gradient: the kernel rounds without the schedules")
@@ -369,7 +412,9 @@ def main(argv=None) -> int:
         if not (a.gradient and a.density) or orders != [2]:
             ap.error("--wrt-density goes with --gradient --density at order 2")
         return density_gradient_bench(a)
-    if a.gradient:
+    if a.born and a.gradient:
+        ap.error("--born and --gradient are separate measurements")
+    if a.gradient or a.born:
         return gradient_bench(a)
     variants = a.variants.split(",")
     # speed2 <= hi keeps the Courant number at 0.9 of the limit for T = 1 (order 2: 1/sqrt(3); the
