@@ -18,12 +18,14 @@
 //    b = 1 / rho as a fifth stream that rolls through registers and LDS like u^{n-1} (described at
 //    the kernel).
 //  * all three march kernels have the save, image and Born modes of the adjoint-state gradient and
-//    of Born modelling (MarchMode below; hip_medium.hpp has the contract).
+//    of Born modelling (MarchMode below; hip_medium.hpp has the contract), and are built from the
+//    tile skeleton of march_tile.hpp and the per-mode pieces below, each written once.
 //  * k_inject / k_record: one thread per source entry / receiver.
 //
-// FP contraction is off (-ffp-contract=off + the pragmas in stencil_math.hpp): every operation
-// is rounded on its own in the order of ops/reference.py step_medium, so fp64 results are
-// bitwise those of the PyTorch oracle, and a uniform m == coef gives k_march's bits.
+// FP contraction is off (-ffp-contract=off + the pragmas in stencil_math.hpp and in every helper
+// here that does arithmetic: the pragma is lexical): every operation is rounded on its own in the
+// order of ops/reference.py step_medium, so fp64 results are bitwise those of the PyTorch oracle,
+// and a uniform m == coef gives k_march's bits.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -33,27 +35,19 @@
 
 #include "device_common.hpp"
 #include "hip_medium.hpp"
+#include "march_tile.hpp"
 
 namespace wave3d {
 namespace {
 
 template <class T>
-struct MediumParams {
-    int xcd;  // XCD-aware tile order (xcd_swizzle)
+struct MediumParams : TileParams<T> {
     const T* u1;
     const T* u2;
     const T* m;
     T* u;
-    i64 si;
-    int sj;
-    int poff;        // see GridView::poff
-    int jmax, kmax;  // largest valid j / k index in storage
-    int nbox;
-    BoxLaunch box[kMaxBoxes];
     int ei0, ei1;
     int w_lo[2], w_hi[2], w_sh[2];  // wrap_ranges
-    T hx2, hy2, hz2;
-    T yx2, yy2, yz2;  // RN(1/h^2) in T for the correctly rounded constant division
     u64* err;
     const T *gx, *gy, *gz;  // TAPER: sponge factors per axis, storage indexing (X+2, Y+2, Z+2 values)
     T* lap_out;             // kSave: receives lap(u1) at the box nodes (strides of u)
@@ -62,108 +56,205 @@ struct MediumParams {
     const T* dm;            // kBorn: the coefficient perturbation; u receives + dm * q (q as above)
 };
 
-// k_march_m modes: the plain step; kSave also stores the Laplacian that entered the update; kImage
-// also accumulates acc = acc + u1 * q (the imaging condition of the adjoint-state gradient); kBorn
-// adds the scattering term dm * q to the update itself (Born / linearised modelling, image mode's
-// transpose): u = G (((2 u1 - G u2) + m lap) + dm q).
+// Modes of the march kernels: the plain step; kSave also stores the Laplacian that entered the
+// update; kImage also accumulates acc = acc + u1 * q (the imaging condition of the adjoint-state
+// gradient); kBorn adds the scattering term dm * q to the update itself (Born / linearised
+// modelling, image mode's transpose): u = G (((2 u1 - G u2) + m lap) + dm q).
+// A MODE other than kPlain (FIRST = false only) adds, behind `if constexpr`, one write-once stream
+// (kSave: lap_out), or a read-once stream (q) and a read-modify-write one (kImage: acc), or two
+// read-once streams (kBorn: q and dm, no store beside u's); all at the lane's own nodes, masked
+// like the stores of u and without the periodic wrap.
 enum MarchMode { kPlain = 0, kSave = 1, kImage = 2, kBorn = 3 };
+
+constexpr int kNt = 2;  // cache policy of the read-once and write-once streams: non-temporal
+
+// The two extra streams of image mode (q and acc) and Born mode (q and dm), at the lane's own
+// nodes: two-slot register rings prefetched one plane ahead like m; plane x in slot (x - ib) & 1.
+template <class T, int R, int MODE>
+struct AuxRings {
+    static constexpr bool kOn = MODE == kImage || MODE == kBorn;
+    T q[kOn ? 2 : 1][kOn ? R : 1], a[kOn ? 2 : 1][kOn ? R : 1];
+
+    static __device__ __forceinline__ const T* second(const MediumParams<T>& p) {
+        return MODE == kBorn ? p.dm : p.acc;
+    }
+    // plane ib into slot 0
+    __device__ __forceinline__ void prime(const Tile<T, R>& t, const MediumParams<T>& p, const unsigned (&os)[R]) {
+        if constexpr (kOn) {
+            const auto rQ = t.prs(p.q, t.ib), rA = t.prs(second(p), t.ib);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                q[0][r] = bld<T, kNt>(rQ, os[r]);
+                a[0][r] = bld<T, kNt>(rA, os[r]);
+                q[1][r] = a[1][r] = T(0);
+            }
+        }
+    }
+    // plane i + 1 into slot H1
+    template <int H1>
+    __device__ __forceinline__ void prefetch(Ph<H1>, const Tile<T, R>& t, const MediumParams<T>& p, int i,
+                                             bool more, const unsigned (&os)[R]) {
+        if constexpr (kOn) {
+            const auto rQ = t.next_rsrc(p.q, i, 1, more), rA = t.next_rsrc(second(p), i, 1, more);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                q[H1][r] = bld<T, kNt>(rQ, os[r]);
+                a[H1][r] = bld<T, kNt>(rA, os[r]);
+            }
+        }
+    }
+    // the values of the current plane (slot H0) at row r; 0, and unused, in the other modes
+    template <int H0>
+    __device__ __forceinline__ T qv(Ph<H0>, int r) const {
+        if constexpr (kOn) return q[H0][r];
+        else return T(0);
+    }
+    template <int H0>
+    __device__ __forceinline__ T av(Ph<H0>, int r) const {
+        if constexpr (kOn) return a[H0][r];
+        else return T(0);
+    }
+};
+
+// Sponge: gyz[r] = gy[j] gz[k] (rounded) of the lane's rows; lanes and rows past the grid read
+// the last table entry (their stores are masked). gxn = gx of the next plane to compute:
+// i + 1 <= X + 1 is always inside the table. TAPER = false: no table is touched, factors of 1
+// that medium_update never uses.
+template <class T, int R, bool TAPER>
+struct Sponge {
+    T gyz[TAPER ? R : 1];
+    T gxn = T(1);
+
+    __device__ __forceinline__ Sponge(const Tile<T, R>& t, const MediumParams<T>& p) {
+        if constexpr (TAPER) {
+#pragma clang fp contract(off)
+            const T gzk = p.gz[min(t.k, p.kmax)];
+#pragma unroll
+            for (int r = 0; r < R; ++r) gyz[r] = ldconst(p.gy, min(t.row(r), p.jmax)) * gzk;
+            gxn = ldconst(p.gx, t.ib);
+        }
+    }
+    // gx of plane i; fetches plane i + 1's
+    __device__ __forceinline__ T next(const MediumParams<T>& p, int i) {
+        const T gxi = gxn;
+        if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
+        return gxi;
+    }
+    __device__ __forceinline__ T yz(int r) const {
+        if constexpr (TAPER) return gyz[r];
+        else return T(1);
+    }
+};
+
+// The new value of a node: centre c = u1, u2, the (density-weighted) Laplacian, m; sponge factors
+// gxi, gyz (TAPER); Born mode's a = dm and q.
+template <class T, bool FIRST, bool TAPER, int MODE>
+__device__ __forceinline__ T medium_update(T c, T u2, T lap, T m, T gxi, T gyz, T a, T q) {
+#pragma clang fp contract(off)
+    static_assert(MODE == kPlain || !FIRST, "save / image / Born modes: leapfrog steps only");
+    if constexpr (FIRST) {
+        const T half_m = T(0.5) * m;  // exact
+        const T v = taylor_first(c, lap, half_m);
+        if constexpr (TAPER) return (gxi * gyz) * v;
+        else return v;
+    } else if constexpr (MODE == kBorn) {
+        const T pr = a * q;  // dm q, rounded before the add
+        if constexpr (TAPER) {
+            const T g = gxi * gyz;
+            return g * (leapfrog(c, g * u2, lap, m) + pr);
+        } else {
+            return leapfrog(c, u2, lap, m) + pr;
+        }
+    } else if constexpr (TAPER) {
+        const T g = gxi * gyz;
+        return g * leapfrog(c, g * u2, lap, m);
+    } else {
+        return leapfrog(c, u2, lap, m);
+    }
+}
+
+// What a mode stores beside u: kSave the Laplacian, kImage the new acc = a + c q (a = acc)
+template <class T, int MODE>
+__device__ __forceinline__ T side_value(T c, T lap, T a, T q) {
+#pragma clang fp contract(off)
+    if constexpr (MODE == kSave) {
+        return lap;
+    } else if constexpr (MODE == kImage) {
+        const T pr = c * q;
+        return a + pr;
+    } else {
+        return T(0);
+    }
+}
+
+// stores of plane i: own plane + fused periodic wrap (buffer stores, masked lanes dropped), and
+// the mode's side stream xv (side_value)
+template <int MODE, class T, int R>
+__device__ __forceinline__ void store_plane(const Tile<T, R>& t, const MediumParams<T>& p, int i, const T (&vv)[R],
+                                            const T (&xv)[R], const unsigned (&os)[R]) {
+    const auto rs = t.prs(p.u, i);
+#pragma unroll
+    for (int r = 0; r < R; ++r) bst<kNt>(vv[r], rs, os[r]);
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+        if (i >= p.w_lo[g] && i <= p.w_hi[g]) {
+            const auto rw = t.prs(p.u, i + p.w_sh[g]);
+#pragma unroll
+            for (int r = 0; r < R; ++r) bst<kNt>(vv[r], rw, os[r]);
+        }
+    if constexpr (MODE == kSave || MODE == kImage) {
+        const auto rx = t.prs(MODE == kSave ? p.lap_out : p.acc, i);
+#pragma unroll
+        for (int r = 0; r < R; ++r) bst<kNt>(xv[r], rx, os[r]);
+    }
+}
+
+// the step's statistic over the box nodes of plane i: ma = max |u| on the planes [ei0, ei1], chk =
+// the sum of the values (commit_errors: nonfinite flag)
+template <class T, int R>
+__device__ __forceinline__ void plane_stats(const MediumParams<T>& p, int i, const T (&vv)[R],
+                                            const bool (&valid)[R], T& chk, T& ma) {
+#pragma clang fp contract(off)
+    const bool erow = i >= p.ei0 && i <= p.ei1;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (!valid[r]) continue;
+        chk += vv[r];
+        if (erow) ma = max_abs(ma, vv[r]);
+    }
+}
 
 // R = rows (j) per lane; the workgroup tile is (4R) x 64. NTM = non-temporal loads of m.
 // Register slots as in k_march: u1(x) -> (x - ib + 1) & 3; u2(x), m(x), halo(x) and the LDS
 // buffer -> (x - ib) & 1; the i loop is unrolled by 4 with the phase as a constant.
 // TAPER = false compiles to the undamped kernel (every use of the tables is `if constexpr`).
-// MODE (kSave / kImage: FIRST = false only) adds, likewise behind `if constexpr`, one write-once
-// stream (lap_out), or a read-once stream (q) and a read-modify-write one (acc), both prefetched
-// one plane ahead in two-slot rings like m; all at the lane's own nodes, masked like the stores
-// of u and without the periodic wrap. kBorn (FIRST = false only) has two read-once streams in the
-// same two rings, q and dm in acc's place, and no store beside u's.
 template <class T, bool FIRST, int R, bool NTM, bool TAPER, int MODE = kPlain>
 __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
     constexpr int kTJ = kWaves * R;
-    constexpr unsigned ES = sizeof(T);
     __shared__ T lds[2][kTJ + 2][kLW];
-
-    const int bid = xcd_swizzle(blockIdx.x, gridDim.x, p.xcd);
-    const int b = find_box(p, bid);
-    const BoxLaunch B = p.box[b];
-    int local = bid - B.block_begin;
-    const int tk = local % B.tiles_k;
-    local /= B.tiles_k;
-    const int tj = local % B.tiles_j;
-    const int ci = local / B.tiles_j;
-
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int kb = B.kbase + tk * kTK;
-    const int k = kb + lane;
-    const int jt = B.j0 + tj * kTJ;
-    const int ib = B.i0 + ci * B.chunk;
-    const int ie = min(B.i1, ib + B.chunk - 1);
-
-    const bool kload = k <= p.kmax;
-    const bool kin = k >= B.k0 && k <= B.k1;
-    const i64 si = p.si;
-    const unsigned pbytes = unsigned(si) * ES;
-    // byte offset of (j,k) in a plane block (kOOB = masked: loads give 0, stores dropped)
-    auto boff = [&](int j, int kk, bool ok) { return ok ? unsigned(j * p.sj + kk + p.poff) * ES : kOOB; };
-    auto prs = [&](const T* base, int i) { return plane_rsrc(base + (i64(i) * si - p.poff), pbytes); };
+    const Tile<T, R> t(p);
+    const int lane = t.lane, w = t.w, ib = t.ib;
 
     unsigned oa[R], ou2[R], os[R];
     bool valid[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int j = jt + w * R + r;
-        valid[r] = kin && j <= B.j1;
-        oa[r] = boff(j, k, kload && j <= p.jmax);
-        ou2[r] = boff(j, k, !FIRST && valid[r]);
-        os[r] = boff(j, k, valid[r]);  // stores, and the loads of m
+        const int j = t.row(r);
+        valid[r] = t.owns(j);
+        oa[r] = t.boff(j, t.k, t.kload && j <= p.jmax);
+        ou2[r] = t.boff(j, t.k, !FIRST && valid[r]);
+        os[r] = t.boff(j, t.k, valid[r]);  // stores, and the loads of m
     }
+    const HaloCell h = halo_cell(t);
+    constexpr int kMAux = NTM ? kNt : 0;
 
-    // halo role of this lane: one LDS cell per plane
-    int hrow = 0, hcol = 0;
-    unsigned hoff = kOOB;
-    bool hon = false;
-    if (w == 0) {  // row jt-1
-        hon = true;
-        hoff = boff(jt - 1, k, kload);
-        hrow = 0;
-        hcol = 1 + lane;
-    } else if (w == kWaves - 1) {  // row jt+TJ
-        const int j = jt + kTJ;
-        hon = true;
-        hoff = boff(j, k, kload && j <= p.jmax);
-        hrow = kTJ + 1;
-        hcol = 1 + lane;
-    } else if (w == 1) {  // columns kb-1 (lanes 0..TJ-1) and kb+64 (lanes 32..32+TJ-1)
-        const int side = lane >> 5, rr = lane & 31;
-        const int j = jt + rr;
-        const int kk = side ? kb + kTK : kb - 1;
-        hon = rr < kTJ;
-        hoff = boff(j, kk, hon && j <= p.jmax && kk <= p.kmax);
-        hrow = 1 + rr;
-        hcol = side ? kTK + 1 : 0;
-    }
-    constexpr int kMAux = NTM ? 2 : 0;  // non-temporal m (read once per step)
-    constexpr int kStAux = 2;           // non-temporal stores (write-once stream)
-
-    static_assert(MODE == kPlain || !FIRST, "save / image / Born modes: leapfrog steps only");
-    constexpr bool kImg = MODE == kImage, kBrn = MODE == kBorn;
-    constexpr bool kTwo = kImg || kBrn;  // the two extra rings: q and acc (image) or q and dm (Born)
     T u1[4][R], u2[2][R], mm[2][R];
-    T qq[kTwo ? 2 : 1][kTwo ? R : 1], aa[kTwo ? 2 : 1][kTwo ? R : 1];
     T hv[2];
-    if constexpr (kTwo) {
-        const auto rQ = prs(p.q, ib), rA = prs(kBrn ? p.dm : p.acc, ib);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            qq[0][r] = bld<T, 2>(rQ, os[r]);
-            aa[0][r] = bld<T, 2>(rA, os[r]);
-            qq[1][r] = aa[1][r] = T(0);
-        }
-    }
+    AuxRings<T, R, MODE> aux;
+    aux.prime(t, p, os);
     {
-        const auto r0 = prs(p.u1, ib - 1), r1 = prs(p.u1, ib), r2 = prs(p.u1, ib + 1);
-        const auto q0 = prs(p.u2, ib), m0 = prs(p.m, ib);
+        const auto r0 = t.prs(p.u1, ib - 1), r1 = t.prs(p.u1, ib), r2 = t.prs(p.u1, ib + 1);
+        const auto q0 = t.prs(p.u2, ib), m0 = t.prs(p.m, ib);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             u1[0][r] = bld<T>(r0, oa[r]);
@@ -175,71 +266,39 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
             mm[0][r] = bld<T, kMAux>(m0, os[r]);
             mm[1][r] = T(0);
         }
-        hv[0] = bld<T>(r1, hoff);
+        hv[0] = bld<T>(r1, h.hoff);
         hv[1] = T(0);
     }
-    const T hx2 = p.hx2, hy2 = p.hy2, hz2 = p.hz2;
-    const T yx2 = p.yx2, yy2 = p.yy2, yz2 = p.yz2;
-
-    // sponge: gyz[r] = gy[j] gz[k] (rounded) of the lane's rows; lanes and rows past the grid read
-    // the last table entry (their stores are masked). gxn = gx of the next plane to compute:
-    // i + 1 <= X + 1 is always inside the table.
-    T gyz[TAPER ? R : 1];
-    T gxn = T(1);
-    if constexpr (TAPER) {
-#pragma clang fp contract(off)
-        const T gzk = p.gz[min(k, p.kmax)];
-#pragma unroll
-        for (int r = 0; r < R; ++r) gyz[r] = ldconst(p.gy, min(jt + w * R + r, p.jmax)) * gzk;
-        gxn = ldconst(p.gx, ib);
-    }
-
-    T ma = T(kErrInit);
-    T chk = T(0);  // sum of the values (commit_errors: nonfinite flag)
+    Sponge<T, R, TAPER> sponge(t, p);
+    T ma = T(kErrInit), chk = T(0);
 
     auto plane = [&](auto phase, const int i) {
         constexpr int P = decltype(phase)::value;
         constexpr int S0 = P & 3, S1 = (P + 1) & 3, S2 = (P + 2) & 3, S3 = (P + 3) & 3;
         constexpr int H0 = P & 1, H1 = (P + 1) & 1;
-        // prefetch u1(i+2) (own rows), u1(i+1) (halo), u2(i+1), m(i+1); 0-record descriptors on
-        // the last plane (loads return 0 without touching memory)
+        // prefetch u1(i+2) (own rows), u1(i+1) (halo), u2(i+1), m(i+1)
         {
-            const bool more = i < ie;
-            const unsigned nb = more ? pbytes : 0u;
-            const int d2 = more ? 2 : 0, d1 = more ? 1 : 0;
-            const auto rN = plane_rsrc(p.u1 + (i64(i + d2) * si - p.poff), nb);
-            const auto rH = plane_rsrc(p.u1 + (i64(i + d1) * si - p.poff), nb);
-            const auto rU = plane_rsrc(p.u2 + (i64(i + d1) * si - p.poff), nb);
-            const auto rM = plane_rsrc(p.m + (i64(i + d1) * si - p.poff), nb);
+            const bool more = i < t.ie;
+            const auto rN = t.next_rsrc(p.u1, i, 2, more), rH = t.next_rsrc(p.u1, i, 1, more);
+            const auto rU = t.next_rsrc(p.u2, i, 1, more), rM = t.next_rsrc(p.m, i, 1, more);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 u1[S3][r] = bld<T>(rN, oa[r]);
                 if (!FIRST) u2[H1][r] = bld<T>(rU, ou2[r]);
                 mm[H1][r] = bld<T, kMAux>(rM, os[r]);
             }
-            hv[H1] = bld<T>(rH, hoff);
-            if constexpr (kTwo) {
-                const auto rQ = plane_rsrc(p.q + (i64(i + d1) * si - p.poff), nb);
-                const auto rA = plane_rsrc((kBrn ? p.dm : p.acc) + (i64(i + d1) * si - p.poff), nb);
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    qq[H1][r] = bld<T, 2>(rQ, os[r]);
-                    aa[H1][r] = bld<T, 2>(rA, os[r]);
-                }
-            }
+            hv[H1] = bld<T>(rH, h.hoff);
+            aux.prefetch(Ph<H1>{}, t, p, i, more, os);
         }
 
         // stage plane i
 #pragma unroll
         for (int r = 0; r < R; ++r) lds[H0][1 + w * R + r][1 + lane] = u1[S1][r];
-        if (hon) lds[H0][hrow][hcol] = hv[H0];
+        if (h.hon) lds[H0][h.hrow][h.hcol] = hv[H0];
         __syncthreads();
 
-        const bool erow = i >= p.ei0 && i <= p.ei1;
-        const T gxi = gxn;
-        if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
-        T vv[R];
-        T xv[MODE == kSave || kImg ? R : 1];  // kSave: lap; kImage: the new acc
+        const T gxi = sponge.next(p, i);
+        T vv[R], xv[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int lr = 1 + w * R + r;
@@ -248,71 +307,16 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
             const T jp = r == R - 1 ? lds[H0][lr + 1][1 + lane] : u1[S1][r + 1];
             const T km = lds[H0][lr][lane];
             const T kp = lds[H0][lr][lane + 2];
-            const T lap = laplace7_cr(c, u1[S0][r], u1[S2][r], jm, jp, km, kp, hx2, hy2, hz2, yx2, yy2, yz2);
-            if constexpr (MODE == kSave) xv[r] = lap;
-            if constexpr (kImg) {
-#pragma clang fp contract(off)
-                const T pr = c * qq[H0][r];
-                xv[r] = aa[H0][r] + pr;
-            }
-            if constexpr (FIRST) {
-#pragma clang fp contract(off)
-                const T half_m = T(0.5) * mm[H0][r];  // exact
-                vv[r] = taylor_first(c, lap, half_m);
-                if constexpr (TAPER) vv[r] = (gxi * gyz[r]) * vv[r];
-            } else if constexpr (kBrn) {
-#pragma clang fp contract(off)
-                const T pr = aa[H0][r] * qq[H0][r];  // dm q, rounded before the add
-                if constexpr (TAPER) {
-                    const T g = gxi * gyz[r];
-                    vv[r] = g * (leapfrog(c, g * u2[H0][r], lap, mm[H0][r]) + pr);
-                } else {
-                    vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]) + pr;
-                }
-            } else if constexpr (TAPER) {
-#pragma clang fp contract(off)
-                const T g = gxi * gyz[r];
-                vv[r] = g * leapfrog(c, g * u2[H0][r], lap, mm[H0][r]);
-            } else {
-                vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]);
-            }
+            const T lap =
+                laplace7_cr(c, u1[S0][r], u1[S2][r], jm, jp, km, kp, p.hx2, p.hy2, p.hz2, p.yx2, p.yy2, p.yz2);
+            const T a = aux.av(Ph<H0>{}, r), q = aux.qv(Ph<H0>{}, r);
+            xv[r] = side_value<T, MODE>(c, lap, a, q);
+            vv[r] = medium_update<T, FIRST, TAPER, MODE>(c, u2[H0][r], lap, mm[H0][r], gxi, sponge.yz(r), a, q);
         }
-        // stores: own plane + fused periodic wrap (buffer stores, masked lanes dropped)
-        {
-            const auto rs = prs(p.u, i);
-#pragma unroll
-            for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rs, os[r]);
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-                if (i >= p.w_lo[g] && i <= p.w_hi[g]) {
-                    const auto rw = prs(p.u, i + p.w_sh[g]);
-#pragma unroll
-                    for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
-                }
-            if constexpr (MODE == kSave || kImg) {
-                const auto rx = prs(MODE == kSave ? p.lap_out : p.acc, i);
-#pragma unroll
-                for (int r = 0; r < R; ++r) bst<kStAux>(xv[r], rx, os[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (!valid[r]) continue;
-            chk += vv[r];
-            if (erow) ma = max_abs(ma, vv[r]);
-        }
+        store_plane<MODE>(t, p, i, vv, xv, os);
+        plane_stats(p, i, vv, valid, chk, ma);
     };
-
-    for (int i = ib;;) {
-        plane(Ph<0>{}, i);
-        if (++i > ie) break;
-        plane(Ph<1>{}, i);
-        if (++i > ie) break;
-        plane(Ph<2>{}, i);
-        if (++i > ie) break;
-        plane(Ph<3>{}, i);
-        if (++i > ie) break;
-    }
+    march_planes<4>(ib, t.ie, plane);
     // slot 1 keeps its initial key: atomicMax with that same key
     commit_errors(ma, T(kErrInit), chk, p.err);
 }
@@ -357,31 +361,11 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
     constexpr int LR = kTJ + 2 * M, LC = kTK + 2 * M;
     constexpr int kHaloJ = 2 * M * kTK, kHaloK = kTJ * 2 * M;
     constexpr int NH = (kHaloJ + kHaloK + kThreads - 1) / kThreads;
-    constexpr unsigned ES = sizeof(T);
+    static_assert(M == 2 || M == 4, "orders 4 and 8");
     __shared__ T lds[2][LR][LC];
+    const Tile<T, R> t(p);
+    const int lane = t.lane, w = t.w, ib = t.ib, kb = t.kb, jt = t.jt;
 
-    const int bid = xcd_swizzle(blockIdx.x, gridDim.x, p.xcd);
-    const int b = find_box(p, bid);
-    const BoxLaunch B = p.box[b];
-    int local = bid - B.block_begin;
-    const int tk = local % B.tiles_k;
-    local /= B.tiles_k;
-    const int tj = local % B.tiles_j;
-    const int ci = local / B.tiles_j;
-
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int kb = B.kbase + tk * kTK;
-    const int k = kb + lane;
-    const int jt = B.j0 + tj * kTJ;
-    const int ib = B.i0 + ci * B.chunk;
-    const int ie = min(B.i1, ib + B.chunk - 1);
-
-    const bool kin = k >= B.k0 && k <= B.k1;
-    const i64 si = p.si;
-    const unsigned pbytes = unsigned(si) * ES;
-    auto boff = [&](int j, int kk, bool ok) { return ok ? unsigned(j * p.sj + kk + p.poff) * ES : kOOB; };
-    auto prs = [&](const T* base, int i) { return plane_rsrc(base + (i64(i) * si - p.poff), pbytes); };
     // byte offset of the source of u1(j, kk) in a plane block and whether it is negated
     auto src = [&](int j, int kk, bool& neg) {
         neg = false;
@@ -389,18 +373,18 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
         else if (j > p.mj1) j = 2 * p.mj1 - j, neg = !neg;
         if (kk < p.mk0) kk = 2 * p.mk0 - kk, neg = !neg;
         else if (kk > p.mk1) kk = 2 * p.mk1 - kk, neg = !neg;
-        return boff(j, kk, j >= 0 && j <= p.jmax && kk >= 0 && kk <= p.kmax);
+        return t.boff(j, kk, j >= 0 && j <= p.jmax && kk >= 0 && kk <= p.kmax);
     };
 
     unsigned oa[R], ou2[R], os[R];
     bool valid[R], ng[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int j = jt + w * R + r;
-        valid[r] = kin && j <= B.j1;
-        oa[r] = src(j, k, ng[r]);
-        ou2[r] = boff(j, k, !FIRST && valid[r]);
-        os[r] = boff(j, k, valid[r]);  // stores, and the loads of m
+        const int j = t.row(r);
+        valid[r] = t.owns(j);
+        oa[r] = src(j, t.k, ng[r]);
+        ou2[r] = t.boff(j, t.k, !FIRST && valid[r]);
+        os[r] = t.boff(j, t.k, valid[r]);  // stores, and the loads of m
     }
 
     // halo cells of this thread: cell c = h 256 + tid; the first 2M 64 are the rows jt-M .. jt-1 and
@@ -429,30 +413,16 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
         }
         if (hidx[h] >= 0) hoff[h] = src(j, kk, hng[h]);
     }
-    constexpr int kMAux = 2;   // non-temporal m (read once per step)
-    constexpr int kStAux = 2;  // non-temporal stores (write-once stream)
 
-    static_assert(MODE == kPlain || !FIRST, "save / image / Born modes: leapfrog steps only");
-    static_assert(M == 2 || M == 4, "orders 4 and 8");
-    constexpr bool kImg = MODE == kImage, kBrn = MODE == kBorn;
-    constexpr bool kTwo = kImg || kBrn;  // the two extra rings: q and acc (image) or q and dm (Born)
     T u1[NS][R], u2[2][R], mm[2][R];
-    T qq[kTwo ? 2 : 1][kTwo ? R : 1], aa[kTwo ? 2 : 1][kTwo ? R : 1];
     T hv[2][NH];
-    if constexpr (kTwo) {
-        const auto rQ = prs(p.q, ib), rA = prs(kBrn ? p.dm : p.acc, ib);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            qq[0][r] = bld<T, 2>(rQ, os[r]);
-            aa[0][r] = bld<T, 2>(rA, os[r]);
-            qq[1][r] = aa[1][r] = T(0);
-        }
-    }
+    AuxRings<T, R, MODE> aux;
+    aux.prime(t, p, os);
     {
         // planes ib-M .. ib+M into slots 0 .. 2M (the host keeps the boxes M planes inside)
 #pragma unroll
         for (int s = 0; s <= 2 * M; ++s) {
-            const auto rp = prs(p.u1, ib - M + s);
+            const auto rp = t.prs(p.u1, ib - M + s);
 #pragma unroll
             for (int r = 0; r < R; ++r) u1[s][r] = bld<T>(rp, oa[r]);
             if (s == M) {
@@ -463,31 +433,18 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
                 }
             }
         }
-        const auto q0 = prs(p.u2, ib), m0 = prs(p.m, ib);
+        const auto q0 = t.prs(p.u2, ib), m0 = t.prs(p.m, ib);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             u1[NS - 1][r] = T(0);
             u2[0][r] = FIRST ? T(0) : bld<T>(q0, ou2[r]);
             u2[1][r] = T(0);
-            mm[0][r] = bld<T, kMAux>(m0, os[r]);
+            mm[0][r] = bld<T, kNt>(m0, os[r]);
             mm[1][r] = T(0);
         }
     }
-    const T hx2 = p.hx2, hy2 = p.hy2, hz2 = p.hz2;
-    const T yx2 = p.yx2, yy2 = p.yy2, yz2 = p.yz2;
-
-    T gyz[TAPER ? R : 1];
-    T gxn = T(1);
-    if constexpr (TAPER) {
-#pragma clang fp contract(off)
-        const T gzk = p.gz[min(k, p.kmax)];
-#pragma unroll
-        for (int r = 0; r < R; ++r) gyz[r] = ldconst(p.gy, min(jt + w * R + r, p.jmax)) * gzk;
-        gxn = ldconst(p.gx, ib);
-    }
-
-    T ma = T(kErrInit);
-    T chk = T(0);
+    Sponge<T, R, TAPER> sponge(t, p);
+    T ma = T(kErrInit), chk = T(0);
     T* const lds0 = &lds[0][0][0];
 
     auto plane = [&](auto phase, const int i) {
@@ -497,30 +454,18 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
         constexpr int SN = (P + 2 * M + 1) % NS;  // plane i+M+1, prefetched here
         constexpr int H0 = P & 1, H1 = (P + 1) & 1;
         {
-            const bool more = i < ie;
-            const unsigned nb = more ? pbytes : 0u;
-            const int dn = more ? M + 1 : 0, d1 = more ? 1 : 0;
-            const auto rN = plane_rsrc(p.u1 + (i64(i + dn) * si - p.poff), nb);
-            const auto rH = plane_rsrc(p.u1 + (i64(i + d1) * si - p.poff), nb);
-            const auto rU = plane_rsrc(p.u2 + (i64(i + d1) * si - p.poff), nb);
-            const auto rM = plane_rsrc(p.m + (i64(i + d1) * si - p.poff), nb);
+            const bool more = i < t.ie;
+            const auto rN = t.next_rsrc(p.u1, i, M + 1, more), rH = t.next_rsrc(p.u1, i, 1, more);
+            const auto rU = t.next_rsrc(p.u2, i, 1, more), rM = t.next_rsrc(p.m, i, 1, more);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 u1[SN][r] = bld<T>(rN, oa[r]);
                 if (!FIRST) u2[H1][r] = bld<T>(rU, ou2[r]);
-                mm[H1][r] = bld<T, kMAux>(rM, os[r]);
+                mm[H1][r] = bld<T, kNt>(rM, os[r]);
             }
 #pragma unroll
             for (int h = 0; h < NH; ++h) hv[H1][h] = bld<T>(rH, hoff[h]);
-            if constexpr (kTwo) {
-                const auto rQ = plane_rsrc(p.q + (i64(i + d1) * si - p.poff), nb);
-                const auto rA = plane_rsrc((kBrn ? p.dm : p.acc) + (i64(i + d1) * si - p.poff), nb);
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    qq[H1][r] = bld<T, 2>(rQ, os[r]);
-                    aa[H1][r] = bld<T, 2>(rA, os[r]);
-                }
-            }
+            aux.prefetch(Ph<H1>{}, t, p, i, more, os);
         }
 
         // stage plane i, reflected nodes negated
@@ -535,11 +480,8 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
             if (hidx[h] >= 0) lds0[H0 * (LR * LC) + hidx[h]] = hng[h] ? -hv[H0][h] : hv[H0][h];
         __syncthreads();
 
-        const bool erow = i >= p.ei0 && i <= p.ei1;
-        const T gxi = gxn;
-        if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
-        T vv[R];
-        T xv[MODE == kSave || kImg ? R : 1];  // kSave: lap; kImage: the new acc
+        const T gxi = sponge.next(p, i);
+        T vv[R], xv[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int lr = M + w * R + r;
@@ -554,114 +496,16 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
                 ty = ty + wd * (jm + jp);
                 tz = tz + wd * (lds[H0][lr][M + lane - d] + lds[H0][lr][M + lane + d]);
             }
-            T lap = T(0);
-            lap = lap + div_const(tx, hx2, yx2);
-            lap = lap + div_const(ty, hy2, yy2);
-            lap = lap + div_const(tz, hz2, yz2);
-            if constexpr (MODE == kSave) xv[r] = lap;
-            if constexpr (kImg) {
-                const T pr = c * qq[H0][r];
-                xv[r] = aa[H0][r] + pr;
-            }
-            if constexpr (FIRST) {
-                const T half_m = T(0.5) * mm[H0][r];  // exact
-                vv[r] = taylor_first(c, lap, half_m);
-                if constexpr (TAPER) vv[r] = (gxi * gyz[r]) * vv[r];
-            } else if constexpr (kBrn) {
-                const T pr = aa[H0][r] * qq[H0][r];  // dm q, rounded before the add
-                if constexpr (TAPER) {
-                    const T g = gxi * gyz[r];
-                    vv[r] = g * (leapfrog(c, g * u2[H0][r], lap, mm[H0][r]) + pr);
-                } else {
-                    vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]) + pr;
-                }
-            } else if constexpr (TAPER) {
-                const T g = gxi * gyz[r];
-                vv[r] = g * leapfrog(c, g * u2[H0][r], lap, mm[H0][r]);
-            } else {
-                vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]);
-            }
+            const T lap = sum_div<T>(tx, ty, tz, p);
+            const T a = aux.av(Ph<H0>{}, r), q = aux.qv(Ph<H0>{}, r);
+            xv[r] = side_value<T, MODE>(c, lap, a, q);
+            vv[r] = medium_update<T, FIRST, TAPER, MODE>(c, u2[H0][r], lap, mm[H0][r], gxi, sponge.yz(r), a, q);
         }
-        {
-            const auto rs = prs(p.u, i);
-#pragma unroll
-            for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rs, os[r]);
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-                if (i >= p.w_lo[g] && i <= p.w_hi[g]) {
-                    const auto rw = prs(p.u, i + p.w_sh[g]);
-#pragma unroll
-                    for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
-                }
-            if constexpr (MODE == kSave || kImg) {
-                const auto rx = prs(MODE == kSave ? p.lap_out : p.acc, i);
-#pragma unroll
-                for (int r = 0; r < R; ++r) bst<kStAux>(xv[r], rx, os[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (!valid[r]) continue;
-            chk += vv[r];
-            if (erow) ma = max_abs(ma, vv[r]);
-        }
+        store_plane<MODE>(t, p, i, vv, xv, os);
+        plane_stats(p, i, vv, valid, chk, ma);
     };
-
-    for (int i = ib;;) {
-        plane(Ph<0>{}, i);
-        if (++i > ie) break;
-        plane(Ph<1>{}, i);
-        if (++i > ie) break;
-        plane(Ph<2>{}, i);
-        if (++i > ie) break;
-        plane(Ph<3>{}, i);
-        if (++i > ie) break;
-        plane(Ph<4>{}, i);
-        if (++i > ie) break;
-        plane(Ph<5>{}, i);
-        if (++i > ie) break;
-        if constexpr (NS > 6) {
-            plane(Ph<6>{}, i);
-            if (++i > ie) break;
-            plane(Ph<7>{}, i);
-            if (++i > ie) break;
-            plane(Ph<8>{}, i);
-            if (++i > ie) break;
-            plane(Ph<9>{}, i);
-            if (++i > ie) break;
-        }
-    }
+    march_planes<NS>(ib, t.ie, plane);
     commit_errors(ma, T(kErrInit), chk, p.err);
-}
-
-// rows per lane of the k_march_mh instantiations (`make resources`: no scratch in any of them)
-template <class T, int M, int MODE>
-constexpr int mh_rows() {
-    return 4;
-}
-
-template <class T, int M>
-void (*march_mh_kernel(bool first, bool taper, int mode))(const MediumParamsH<T>) {
-    if (mode == kSave)
-        return taper ? k_march_mh<T, M, false, mh_rows<T, M, kSave>(), true, kSave>
-                     : k_march_mh<T, M, false, mh_rows<T, M, kSave>(), false, kSave>;
-    if (mode == kImage)
-        return taper ? k_march_mh<T, M, false, mh_rows<T, M, kImage>(), true, kImage>
-                     : k_march_mh<T, M, false, mh_rows<T, M, kImage>(), false, kImage>;
-    if (mode == kBorn)
-        return taper ? k_march_mh<T, M, false, mh_rows<T, M, kBorn>(), true, kBorn>
-                     : k_march_mh<T, M, false, mh_rows<T, M, kBorn>(), false, kBorn>;
-    constexpr int RP = mh_rows<T, M, kPlain>();
-    if (first) return taper ? k_march_mh<T, M, true, RP, true> : k_march_mh<T, M, true, RP, false>;
-    return taper ? k_march_mh<T, M, false, RP, true> : k_march_mh<T, M, false, RP, false>;
-}
-
-template <class T, int M>
-int march_mh_rows(int mode) {
-    return mode == kSave    ? mh_rows<T, M, kSave>()
-           : mode == kImage ? mh_rows<T, M, kImage>()
-           : mode == kBorn  ? mh_rows<T, M, kBorn>()
-                            : mh_rows<T, M, kPlain>();
 }
 
 // ---- variable density: k_march_mb ----------------------------------------------------------
@@ -695,91 +539,31 @@ __device__ __forceinline__ T flux_diff(T c, T um, T up, T bc, T bm, T bp) {
 template <class T, bool FIRST, int R, bool TAPER, int MODE = kPlain>
 __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p) {
     constexpr int kTJ = kWaves * R;
-    constexpr unsigned ES = sizeof(T);
     __shared__ T lds[2][kTJ + 2][kLW];
     __shared__ T ldb[2][kTJ + 2][kLW];
-
-    const int bid = xcd_swizzle(blockIdx.x, gridDim.x, p.xcd);
-    const int b = find_box(p, bid);
-    const BoxLaunch B = p.box[b];
-    int local = bid - B.block_begin;
-    const int tk = local % B.tiles_k;
-    local /= B.tiles_k;
-    const int tj = local % B.tiles_j;
-    const int ci = local / B.tiles_j;
-
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int kb = B.kbase + tk * kTK;
-    const int k = kb + lane;
-    const int jt = B.j0 + tj * kTJ;
-    const int ib = B.i0 + ci * B.chunk;
-    const int ie = min(B.i1, ib + B.chunk - 1);
-
-    const bool kload = k <= p.kmax;
-    const bool kin = k >= B.k0 && k <= B.k1;
-    const i64 si = p.si;
-    const unsigned pbytes = unsigned(si) * ES;
-    auto boff = [&](int j, int kk, bool ok) { return ok ? unsigned(j * p.sj + kk + p.poff) * ES : kOOB; };
-    auto prs = [&](const T* base, int i) { return plane_rsrc(base + (i64(i) * si - p.poff), pbytes); };
+    const Tile<T, R> t(p);
+    const int lane = t.lane, w = t.w, ib = t.ib;
 
     unsigned oa[R], ou2[R], os[R];
     bool valid[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int j = jt + w * R + r;
-        valid[r] = kin && j <= B.j1;
-        oa[r] = boff(j, k, kload && j <= p.jmax);  // u1 and b
-        ou2[r] = boff(j, k, !FIRST && valid[r]);
-        os[r] = boff(j, k, valid[r]);  // stores, and the loads of m
+        const int j = t.row(r);
+        valid[r] = t.owns(j);
+        oa[r] = t.boff(j, t.k, t.kload && j <= p.jmax);  // u1 and b
+        ou2[r] = t.boff(j, t.k, !FIRST && valid[r]);
+        os[r] = t.boff(j, t.k, valid[r]);  // stores, and the loads of m
     }
+    const HaloCell h = halo_cell(t);  // one cell per plane and tile
 
-    // halo role of this lane (k_march_m's): one LDS cell per plane and tile
-    int hrow = 0, hcol = 0;
-    unsigned hoff = kOOB;
-    bool hon = false;
-    if (w == 0) {  // row jt-1
-        hon = true;
-        hoff = boff(jt - 1, k, kload);
-        hrow = 0;
-        hcol = 1 + lane;
-    } else if (w == kWaves - 1) {  // row jt+TJ
-        const int j = jt + kTJ;
-        hon = true;
-        hoff = boff(j, k, kload && j <= p.jmax);
-        hrow = kTJ + 1;
-        hcol = 1 + lane;
-    } else if (w == 1) {  // columns kb-1 (lanes 0..TJ-1) and kb+64 (lanes 32..32+TJ-1)
-        const int side = lane >> 5, rr = lane & 31;
-        const int j = jt + rr;
-        const int kk = side ? kb + kTK : kb - 1;
-        hon = rr < kTJ;
-        hoff = boff(j, kk, hon && j <= p.jmax && kk <= p.kmax);
-        hrow = 1 + rr;
-        hcol = side ? kTK + 1 : 0;
-    }
-    constexpr int kMAux = 2;   // non-temporal m (read once per step)
-    constexpr int kStAux = 2;  // non-temporal stores (write-once stream)
-
-    static_assert(MODE == kPlain || !FIRST, "save / image / Born modes: leapfrog steps only");
-    constexpr bool kImg = MODE == kImage, kBrn = MODE == kBorn;
-    constexpr bool kTwo = kImg || kBrn;  // the two extra rings: q and acc (image) or q and dm (Born)
     T u1[4][R], bb[4][R], u2[2][R], mm[2][R];
-    T qq[kTwo ? 2 : 1][kTwo ? R : 1], aa[kTwo ? 2 : 1][kTwo ? R : 1];
     T hv[2], hb[2];
-    if constexpr (kTwo) {
-        const auto rQ = prs(p.q, ib), rA = prs(kBrn ? p.dm : p.acc, ib);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            qq[0][r] = bld<T, 2>(rQ, os[r]);
-            aa[0][r] = bld<T, 2>(rA, os[r]);
-            qq[1][r] = aa[1][r] = T(0);
-        }
-    }
+    AuxRings<T, R, MODE> aux;
+    aux.prime(t, p, os);
     {
-        const auto r0 = prs(p.u1, ib - 1), r1 = prs(p.u1, ib), r2 = prs(p.u1, ib + 1);
-        const auto b0 = prs(p.b, ib - 1), b1 = prs(p.b, ib), b2 = prs(p.b, ib + 1);
-        const auto q0 = prs(p.u2, ib), m0 = prs(p.m, ib);
+        const auto r0 = t.prs(p.u1, ib - 1), r1 = t.prs(p.u1, ib), r2 = t.prs(p.u1, ib + 1);
+        const auto b0 = t.prs(p.b, ib - 1), b1 = t.prs(p.b, ib), b2 = t.prs(p.b, ib + 1);
+        const auto q0 = t.prs(p.u2, ib), m0 = t.prs(p.m, ib);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             u1[0][r] = bld<T>(r0, oa[r]);
@@ -792,63 +576,36 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
             bb[3][r] = T(0);
             u2[0][r] = FIRST ? T(0) : bld<T>(q0, ou2[r]);
             u2[1][r] = T(0);
-            mm[0][r] = bld<T, kMAux>(m0, os[r]);
+            mm[0][r] = bld<T, kNt>(m0, os[r]);
             mm[1][r] = T(0);
         }
-        hv[0] = bld<T>(r1, hoff);
-        hb[0] = bld<T>(b1, hoff);
+        hv[0] = bld<T>(r1, h.hoff);
+        hb[0] = bld<T>(b1, h.hoff);
         hv[1] = hb[1] = T(0);
     }
-    const T hx2 = p.hx2, hy2 = p.hy2, hz2 = p.hz2;
-    const T yx2 = p.yx2, yy2 = p.yy2, yz2 = p.yz2;
-
-    T gyz[TAPER ? R : 1];
-    T gxn = T(1);
-    if constexpr (TAPER) {
-#pragma clang fp contract(off)
-        const T gzk = p.gz[min(k, p.kmax)];
-#pragma unroll
-        for (int r = 0; r < R; ++r) gyz[r] = ldconst(p.gy, min(jt + w * R + r, p.jmax)) * gzk;
-        gxn = ldconst(p.gx, ib);
-    }
-
-    T ma = T(kErrInit);
-    T chk = T(0);
+    Sponge<T, R, TAPER> sponge(t, p);
+    T ma = T(kErrInit), chk = T(0);
 
     auto plane = [&](auto phase, const int i) {
         constexpr int P = decltype(phase)::value;
         constexpr int S0 = P & 3, S1 = (P + 1) & 3, S2 = (P + 2) & 3, S3 = (P + 3) & 3;
         constexpr int H0 = P & 1, H1 = (P + 1) & 1;
-        // prefetch u1, b (i+2, own rows), u1, b (i+1, halo), u2(i+1), m(i+1); 0-record descriptors
-        // on the last plane (loads return 0 without touching memory)
+        // prefetch u1, b (i+2, own rows), u1, b (i+1, halo), u2(i+1), m(i+1)
         {
-            const bool more = i < ie;
-            const unsigned nb = more ? pbytes : 0u;
-            const int d2 = more ? 2 : 0, d1 = more ? 1 : 0;
-            const auto rN = plane_rsrc(p.u1 + (i64(i + d2) * si - p.poff), nb);
-            const auto rH = plane_rsrc(p.u1 + (i64(i + d1) * si - p.poff), nb);
-            const auto bN = plane_rsrc(p.b + (i64(i + d2) * si - p.poff), nb);
-            const auto bH = plane_rsrc(p.b + (i64(i + d1) * si - p.poff), nb);
-            const auto rU = plane_rsrc(p.u2 + (i64(i + d1) * si - p.poff), nb);
-            const auto rM = plane_rsrc(p.m + (i64(i + d1) * si - p.poff), nb);
+            const bool more = i < t.ie;
+            const auto rN = t.next_rsrc(p.u1, i, 2, more), rH = t.next_rsrc(p.u1, i, 1, more);
+            const auto bN = t.next_rsrc(p.b, i, 2, more), bH = t.next_rsrc(p.b, i, 1, more);
+            const auto rU = t.next_rsrc(p.u2, i, 1, more), rM = t.next_rsrc(p.m, i, 1, more);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 u1[S3][r] = bld<T>(rN, oa[r]);
                 bb[S3][r] = bld<T>(bN, oa[r]);
                 if (!FIRST) u2[H1][r] = bld<T>(rU, ou2[r]);
-                mm[H1][r] = bld<T, kMAux>(rM, os[r]);
+                mm[H1][r] = bld<T, kNt>(rM, os[r]);
             }
-            hv[H1] = bld<T>(rH, hoff);
-            hb[H1] = bld<T>(bH, hoff);
-            if constexpr (kTwo) {
-                const auto rQ = plane_rsrc(p.q + (i64(i + d1) * si - p.poff), nb);
-                const auto rA = plane_rsrc((kBrn ? p.dm : p.acc) + (i64(i + d1) * si - p.poff), nb);
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    qq[H1][r] = bld<T, 2>(rQ, os[r]);
-                    aa[H1][r] = bld<T, 2>(rA, os[r]);
-                }
-            }
+            hv[H1] = bld<T>(rH, h.hoff);
+            hb[H1] = bld<T>(bH, h.hoff);
+            aux.prefetch(Ph<H1>{}, t, p, i, more, os);
         }
 
         // stage plane i of u1 and b: one barrier for both tiles
@@ -857,20 +614,16 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
             lds[H0][1 + w * R + r][1 + lane] = u1[S1][r];
             ldb[H0][1 + w * R + r][1 + lane] = bb[S1][r];
         }
-        if (hon) {
-            lds[H0][hrow][hcol] = hv[H0];
-            ldb[H0][hrow][hcol] = hb[H0];
+        if (h.hon) {
+            lds[H0][h.hrow][h.hcol] = hv[H0];
+            ldb[H0][h.hrow][h.hcol] = hb[H0];
         }
         __syncthreads();
 
-        const bool erow = i >= p.ei0 && i <= p.ei1;
-        const T gxi = gxn;
-        if constexpr (TAPER) gxn = ldconst(p.gx, i + 1);
-        T vv[R];
-        T xv[MODE == kSave || kImg ? R : 1];  // kSave: D_b u1; kImage: the new acc
+        const T gxi = sponge.next(p, i);
+        T vv[R], xv[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-#pragma clang fp contract(off)
             const int lr = 1 + w * R + r;
             const T c = u1[S1][r], bc = bb[S1][r];
             const T jm = r == 0 ? lds[H0][lr - 1][1 + lane] : u1[S1][r - 1];
@@ -881,81 +634,34 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
             const T ty = flux_diff(c, jm, jp, bc, bjm, bjp);
             const T tz = flux_diff(c, lds[H0][lr][lane], lds[H0][lr][lane + 2], bc, ldb[H0][lr][lane],
                                    ldb[H0][lr][lane + 2]);
-            T lap = T(0);
-            lap = lap + div_const(tx, hx2, yx2);
-            lap = lap + div_const(ty, hy2, yy2);
-            lap = lap + div_const(tz, hz2, yz2);
-            if constexpr (MODE == kSave) xv[r] = lap;
-            if constexpr (kImg) {
-                const T pr = c * qq[H0][r];
-                xv[r] = aa[H0][r] + pr;
-            }
-            if constexpr (FIRST) {
-                const T half_m = T(0.5) * mm[H0][r];  // exact
-                vv[r] = taylor_first(c, lap, half_m);
-                if constexpr (TAPER) vv[r] = (gxi * gyz[r]) * vv[r];
-            } else if constexpr (kBrn) {
-                const T pr = aa[H0][r] * qq[H0][r];  // dm q, rounded before the add
-                if constexpr (TAPER) {
-                    const T g = gxi * gyz[r];
-                    vv[r] = g * (leapfrog(c, g * u2[H0][r], lap, mm[H0][r]) + pr);
-                } else {
-                    vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]) + pr;
-                }
-            } else if constexpr (TAPER) {
-                const T g = gxi * gyz[r];
-                vv[r] = g * leapfrog(c, g * u2[H0][r], lap, mm[H0][r]);
-            } else {
-                vv[r] = leapfrog(c, u2[H0][r], lap, mm[H0][r]);
-            }
+            const T lap = sum_div<T>(tx, ty, tz, p);
+            const T a = aux.av(Ph<H0>{}, r), q = aux.qv(Ph<H0>{}, r);
+            xv[r] = side_value<T, MODE>(c, lap, a, q);
+            vv[r] = medium_update<T, FIRST, TAPER, MODE>(c, u2[H0][r], lap, mm[H0][r], gxi, sponge.yz(r), a, q);
         }
-        // stores: own plane + fused periodic wrap (buffer stores, masked lanes dropped)
-        {
-            const auto rs = prs(p.u, i);
-#pragma unroll
-            for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rs, os[r]);
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-                if (i >= p.w_lo[g] && i <= p.w_hi[g]) {
-                    const auto rw = prs(p.u, i + p.w_sh[g]);
-#pragma unroll
-                    for (int r = 0; r < R; ++r) bst<kStAux>(vv[r], rw, os[r]);
-                }
-            if constexpr (MODE == kSave || kImg) {
-                const auto rx = prs(MODE == kSave ? p.lap_out : p.acc, i);
-#pragma unroll
-                for (int r = 0; r < R; ++r) bst<kStAux>(xv[r], rx, os[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (!valid[r]) continue;
-            chk += vv[r];
-            if (erow) ma = max_abs(ma, vv[r]);
-        }
+        store_plane<MODE>(t, p, i, vv, xv, os);
+        plane_stats(p, i, vv, valid, chk, ma);
     };
-
-    for (int i = ib;;) {
-        plane(Ph<0>{}, i);
-        if (++i > ie) break;
-        plane(Ph<1>{}, i);
-        if (++i > ie) break;
-        plane(Ph<2>{}, i);
-        if (++i > ie) break;
-        plane(Ph<3>{}, i);
-        if (++i > ie) break;
-    }
+    march_planes<4>(ib, t.ie, plane);
     commit_errors(ma, T(kErrInit), chk, p.err);
 }
 
-// the k_march_mb instantiations: 4 rows per lane (`make resources`: no scratch in any of them)
-template <class T>
-void (*march_mb_kernel(bool first, bool taper, int mode))(const MediumParamsB<T>) {
-    if (mode == kSave) return taper ? k_march_mb<T, false, 4, true, kSave> : k_march_mb<T, false, 4, false, kSave>;
-    if (mode == kImage) return taper ? k_march_mb<T, false, 4, true, kImage> : k_march_mb<T, false, 4, false, kImage>;
-    if (mode == kBorn) return taper ? k_march_mb<T, false, 4, true, kBorn> : k_march_mb<T, false, 4, false, kBorn>;
-    if (first) return taper ? k_march_mb<T, true, 4, true> : k_march_mb<T, true, 4, false>;
-    return taper ? k_march_mb<T, false, 4, true> : k_march_mb<T, false, 4, false>;
+// The runtime (first, taper, mode) of a launch as template arguments: pick(FIRST, TAPER, MODE),
+// three integral constants, returns the kernel of one family for them. The modes exist for the
+// leapfrog step only. Every instantiation has 4 rows per lane unless a variant asks for 2
+// (`make resources`: no scratch in any of them).
+template <class F>
+auto select_march(bool first, bool taper, int mode, F pick) {
+    auto with_taper = [&](auto fi, auto mo) {
+        return taper ? pick(fi, std::true_type{}, mo) : pick(fi, std::false_type{}, mo);
+    };
+    switch (mode) {
+        case kSave: return with_taper(std::false_type{}, Ph<kSave>{});
+        case kImage: return with_taper(std::false_type{}, Ph<kImage>{});
+        case kBorn: return with_taper(std::false_type{}, Ph<kBorn>{});
+        default: break;
+    }
+    return first ? with_taper(std::true_type{}, Ph<kPlain>{}) : with_taper(std::false_type{}, Ph<kPlain>{});
 }
 
 struct NodeGrid {
@@ -1005,15 +711,35 @@ NodeGrid node_grid(const GridView& gv) {
     return NodeGrid{gv.si, gv.sj, gv.X + 2, gv.Y + 2, gv.Z + 2};
 }
 
-template <class T, bool FIRST, bool TAPER>
-void (*march_m_kernel(int variant))(const MediumParams<T>) {
-    constexpr int RD = 4;  // march_rows_per_thread()
-    switch (variant & 3) {
-        case 1: return k_march_m<T, FIRST, RD, true, TAPER>;
-        case 2: return k_march_m<T, FIRST, 2, false, TAPER>;
-        case 3: return k_march_m<T, FIRST, 2, true, TAPER>;
-        default: return k_march_m<T, FIRST, RD, false, TAPER>;
-    }
+// k_march_m: the plain step exists in four variants (R, NTM); the modes for the default one only
+template <class T>
+void (*march_m_kernel(bool first, bool taper, int mode, int variant))(const MediumParams<T>) {
+    return select_march(first, taper, mode, [&](auto fi, auto ta, auto mo) -> void (*)(const MediumParams<T>) {
+        constexpr bool FIRST = decltype(fi)::value, TAPER = decltype(ta)::value;
+        constexpr int MODE = decltype(mo)::value;
+        constexpr int RD = 4;  // march_rows_per_thread()
+        if constexpr (MODE != kPlain) return k_march_m<T, FIRST, RD, true, TAPER, MODE>;
+        else switch (variant & 3) {
+                case 1: return k_march_m<T, FIRST, RD, true, TAPER>;
+                case 2: return k_march_m<T, FIRST, 2, false, TAPER>;
+                case 3: return k_march_m<T, FIRST, 2, true, TAPER>;
+                default: return k_march_m<T, FIRST, RD, false, TAPER>;
+            }
+    });
+}
+
+template <class T, int M>
+void (*march_mh_kernel(bool first, bool taper, int mode))(const MediumParamsH<T>) {
+    return select_march(first, taper, mode, [](auto fi, auto ta, auto mo) -> void (*)(const MediumParamsH<T>) {
+        return k_march_mh<T, M, decltype(fi)::value, 4, decltype(ta)::value, decltype(mo)::value>;
+    });
+}
+
+template <class T>
+void (*march_mb_kernel(bool first, bool taper, int mode))(const MediumParamsB<T>) {
+    return select_march(first, taper, mode, [](auto fi, auto ta, auto mo) -> void (*)(const MediumParamsB<T>) {
+        return k_march_mb<T, decltype(fi)::value, 4, decltype(ta)::value, decltype(mo)::value>;
+    });
 }
 
 }  // namespace
@@ -1069,11 +795,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     if (born) {
         // q and dm are read while u is written (own plane and wrap planes): no shared memory
         const i64 span = i64(gv.X + 2 * gv.G - 1) * gv.si + i64(gv.Y + 2 * gv.G - 1) * gv.sj + gv.Z + 2 * gv.G;
-        auto overlaps = [&](const T* x) {
-            const std::uintptr_t u0 = std::uintptr_t(u), x0 = std::uintptr_t(x), n = std::uintptr_t(span) * sizeof(T);
-            return u0 < x0 + n && x0 < u0 + n;
-        };
-        W3D_REQUIRE(!overlaps(q) && !overlaps(dm), "Born mode: q or dm shares memory with u");
+        W3D_REQUIRE(!overlaps<T>(u, q, span) && !overlaps<T>(u, dm, span), "Born mode: q or dm shares memory with u");
     }
     const int mode = save ? kSave : image ? kImage : born ? kBorn : kPlain;
     // reflecting faces of k_march_mh: (j_lo, j_hi, k_lo, k_hi), +-2^29 where there is none
@@ -1096,28 +818,17 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                         "mirror faces nearer than the stencil's half-width");
     }
     MediumParams<T> p{};
-    p.xcd = xcd_swizzle_enabled();
+    fill_tile_params(p, gv, h2);
     p.u1 = u1;
     p.u2 = u2;
     p.m = m;
     p.u = u;
-    p.si = gv.si;
-    p.sj = gv.sj;
-    p.poff = gv.poff;
-    p.jmax = gv.jmax();
-    p.kmax = gv.kmax();
     p.ei0 = ei0;
     p.ei1 = ei1;
     for (int q = 0; q < kMaxWrap; ++q)
         W3D_REQUIRE(wrap.src[q] < 1 || (wrap.src[q] <= gv.X && wrap.dst[q] >= 1 - gv.G && wrap.dst[q] <= gv.X + gv.G),
                     "wrap plane outside the grid");
     wrap_ranges(wrap, p.w_lo, p.w_hi, p.w_sh);
-    p.hx2 = T(h2[0]);
-    p.hy2 = T(h2[1]);
-    p.hz2 = T(h2[2]);
-    p.yx2 = T(1) / T(h2[0]);
-    p.yy2 = T(1) / T(h2[1]);
-    p.yz2 = T(1) / T(h2[2]);
     p.err = err;
     p.gx = gx;
     p.gy = gy;
@@ -1126,20 +837,6 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     p.q = q;
     p.acc = acc;
     p.dm = dm;
-    const int tj_rows = kWaves * (M == 2   ? march_mh_rows<T, 2>(mode)
-                                  : M == 4 ? march_mh_rows<T, 4>(mode)
-                                  : (variant & 2) ? 2
-                                                  : 4);
-    int btiles[kMaxBoxes], bplanes[kMaxBoxes], nbt = 0;
-    for (int q = 0; q < nbox; ++q) {
-        const Box& bx = boxes[q];
-        if (bx.empty()) continue;
-        btiles[nbt] = ((bx.k1 - 1) / kTK - (bx.k0 - 1) / kTK + 1) * cdiv(bx.j1 - bx.j0 + 1, tj_rows);
-        bplanes[nbt++] = bx.i1 - bx.i0 + 1;
-    }
-    // launch_step's march path: 32-plane work items, shorter on small grids
-    const int achunk = auto_chunk_boxes(32, btiles, bplanes, nbt);
-    int nb = 0, total = 0;
     for (int q = 0; q < nbox; ++q) {
         const Box& bx = boxes[q];
         if (bx.empty()) continue;
@@ -1157,22 +854,11 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                                            : "step box nearer than order / 2 to an unmirrored storage edge");
             }
         }
-        BoxLaunch& L = p.box[nb];
-        L.i0 = bx.i0, L.i1 = bx.i1, L.j0 = bx.j0, L.j1 = bx.j1, L.k0 = bx.k0, L.k1 = bx.k1;
-        const int t0 = (bx.k0 - 1) / kTK, t1 = (bx.k1 - 1) / kTK;
-        L.kbase = 1 + t0 * kTK;
-        L.tiles_k = t1 - t0 + 1;
-        L.tiles_j = cdiv(bx.j1 - bx.j0 + 1, tj_rows);
-        const int planes = bx.i1 - bx.i0 + 1;
-        int ch = std::min(chunk > 0 ? chunk : achunk, planes);
-        ch = cdiv(planes, cdiv(planes, ch));  // equal work items (no short tail chunk)
-        L.chunk = ch;
-        L.block_begin = total;
-        total += L.tiles_k * L.tiles_j * cdiv(planes, ch);
-        ++nb;
     }
-    p.nbox = nb;
-    if (nb == 0) return;
+    // 4 rows per lane in every kernel but k_march_m's two-row variants
+    const int tj_rows = kWaves * (M == 1 && (variant & 2) ? 2 : 4);
+    const int total = plan_boxes(p, boxes, nbox, tj_rows, chunk);
+    if (p.nbox == 0) return;
     if (M > 1) {
         MediumParamsH<T> ph{};
         static_cast<MediumParams<T>&>(ph) = p;
@@ -1190,13 +876,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
         HIP_OK(hipGetLastError());
         return;
     }
-    void (*kern)(const MediumParams<T>) =
-        taper ? (first ? march_m_kernel<T, true, true>(variant) : march_m_kernel<T, false, true>(variant))
-              : (first ? march_m_kernel<T, true, false>(variant) : march_m_kernel<T, false, false>(variant));
-    if (save) kern = taper ? k_march_m<T, false, 4, true, true, kSave> : k_march_m<T, false, 4, true, false, kSave>;
-    if (image) kern = taper ? k_march_m<T, false, 4, true, true, kImage> : k_march_m<T, false, 4, true, false, kImage>;
-    if (born) kern = taper ? k_march_m<T, false, 4, true, true, kBorn> : k_march_m<T, false, 4, true, false, kBorn>;
-    hipLaunchKernelGGL(kern, dim3(total), dim3(kThreads), 0, s, p);
+    hipLaunchKernelGGL(march_m_kernel<T>(first, taper, mode, variant), dim3(total), dim3(kThreads), 0, s, p);
     HIP_OK(hipGetLastError());
 }
 

@@ -323,31 +323,16 @@ class MediumSolver:
 
         p = self.problem
         N, K, dt = p.N, p.timesteps, p.torch_dtype
-        if not torch.cuda.is_available():
-            raise RuntimeError("the hip backend needs a HIP device")
-        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else self.device)
-        c = reference.tables(N, K, (p.Lx, p.Ly, p.Lz), p.T, p.pi)[4]
-        h2 = (c["hx2"], c["hy2"], c["hz2"])
-        M, box, wrap, step_kw = self._layout()
+        s = _HipSetup(self)
+        dev, M, box, wrap, h2 = s.dev, s.M, s.box, s.wrap, s.h2
         with torch.cuda.device(dev):
-            lv = [kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev) for _ in range(3)]
-            m = kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev)
-            m.copy_(reference.medium_coefficient(p.speed2, c["tau"], N, dt, M, p.density))
-            if p.density is not None:
-                bu = kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev)
-                bu.copy_(reference.buoyancy_field(p.density, N, dt, M))
-                step_kw = dict(step_kw, buoyancy=bu)
-            taper = None
-            if self.taper is not None:
-                taper = tuple(t.to(dev) for t in reference.taper_tables(self.taper, N, dt, M))
+            lv = [s.level() for _ in range(3)]
+            m = s.level()
+            s.medium(m, lv[0])
+            step_kw, taper, g, src, rec = s.step_kw, s.taper, s.g, s.src, s.rec
             if self.u0 is not None:
                 lv[0][M:N + 1 + M] = self.u0.to(dt).to(dev)
                 reference._wrap_x(lv[0], N, M)
-            ent = reference.source_entries(self.sources, N, M)
-            g = reference.source_table(self.wavelet, K, len(self.sources), c["hx"], c["hy"], c["hz"], dt)
-            g = g[:, [s for _, s in ent]].contiguous().to(dev)  # one column per storage node
-            src = kernels.source_nodes([nd for nd, _ in ent], lv[0])
-            rec = kernels.receiver_nodes([(i + M, j, k) for i, j, k in self.receivers], lv[0])
             traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
             mx0 = reference.max_abs_field(lv[0][M:N + 1 + M, 1:N, 1:N])
@@ -368,10 +353,9 @@ class MediumSolver:
                 kernels.inject(u, m, src, g[n - 1], wrap)
                 kernels.record(u, rec, traces[n])
                 if self.check_every > 0 and n % self.check_every == 0:
-                    flags = stat[2:3 * n + 3:3].cpu()  # one read-back: the flags of layers 0..n
-                    if bool((flags != 0).any()):
-                        abort = dict(aborted=True, abort_layer=int((flags != 0).nonzero()[0]),
-                                     abort_reason="non-finite values")
+                    bad = _nonfinite_layer(stat, n)  # one read-back: the flags of layers 0..n
+                    if bad is not None:
+                        abort = dict(aborted=True, abort_layer=bad, abort_reason="non-finite values")
                         done = n
                         break
             ev1.record()
@@ -457,15 +441,9 @@ class MediumSolver:
 
         p = self.problem
         N, K, dt = p.N, p.timesteps, p.torch_dtype
-        if not torch.cuda.is_available():
-            raise RuntimeError("the hip backend needs a HIP device")
-        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else self.device)
-        c = reference.tables(N, K, (p.Lx, p.Ly, p.Lz), p.T, p.pi)[4]
-        h2 = (c["hx2"], c["hy2"], c["hz2"])
-        M, box, wrap, step_kw = self._layout()
+        s = _HipSetup(self)
+        dev, c, M, box, wrap, h2, level = s.dev, s.c, s.M, s.box, s.wrap, s.h2, s.level
         with torch.cuda.device(dev):
-            level_bytes = kernels.level_bytes(N + 1 + 2 * M, N + 1, N + 1, dt)
-            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
             if segment is None:
                 segment = best_gradient_segment(K, wrt_density=wrt_density)
                 what = "the smallest schedule"
@@ -473,17 +451,11 @@ class MediumSolver:
                 segment = int(segment)
                 what = f"the schedule of segment = {segment}"
             nlev = gradient_levels(K, segment, density=p.density is not None, wrt_density=wrt_density)
-            if nlev * level_bytes > free:
-                raise RuntimeError(f"gradient(): {what} holds {nlev} levels = {nlev * level_bytes} bytes, but only "
-                                   f"{free} bytes of device memory are free")
+            s.require_levels(nlev, f"gradient(): {what}")
             # forward steps 2..K in segments [a, b]; the last one keeps its q, the others a checkpoint
             segs = [(a, min(a + segment - 1, K)) for a in range(2, K + 1, segment)]
             qlen = min(segment, K - 1)
             t0 = time.perf_counter()
-
-            def level():
-                return kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev)
-
             lv = [level() for _ in range(3)]
             ad = [level() for _ in range(3)] if len(segs) > 1 else lv  # the adjoint's ring
             m, acc = level(), level()
@@ -493,19 +465,8 @@ class MediumSolver:
             ub = [level() for _ in range(qlen)] if wrt_density else None
             accb = level() if wrt_density else None
             ck = [(level(), level()) for _ in segs[:-1]]
-            mc = reference.medium_coefficient(p.speed2, c["tau"], N, dt, M, p.density)
-            m.copy_(mc)
-            if p.density is not None:
-                bu = level()
-                bu.copy_(reference.buoyancy_field(p.density, N, dt, M))
-                step_kw = dict(step_kw, buoyancy=bu)
-            tt = None if self.taper is None else reference.taper_tables(self.taper, N, dt, M)
-            taper = None if tt is None else tuple(t.to(dev) for t in tt)
-            ent = reference.source_entries(self.sources, N, M)
-            gsrc = reference.source_table(self.wavelet, K, len(self.sources), c["hx"], c["hy"], c["hz"], dt)
-            g = gsrc[:, [s for _, s in ent]].contiguous().to(dev)
-            src = kernels.source_nodes([nd for nd, _ in ent], lv[0])
-            rec = kernels.receiver_nodes([(i + M, j, k) for i, j, k in self.receivers], lv[0])
+            mc = s.medium(m, lv[0])
+            step_kw, tt, taper, gsrc, g, src, rec = s.step_kw, s.tt, s.taper, s.gsrc, s.g, s.src, s.rec
             traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
             scratch = kernels.new_err(1, device=dev)  # statistics of the recomputed steps (those of `stat` again)
@@ -520,12 +481,6 @@ class MediumSolver:
                                     variant=None if save is not None else self.variant, taper=taper, lap_out=save,
                                     **step_kw)
                 kernels.inject(u, m, src, g[n - 1], wrap)
-
-            def check(st, name):
-                flags = st[2::3].cpu()  # the one read-back of this pass
-                if bool((flags != 0).any()):
-                    raise RuntimeError(f"gradient(): non-finite values in the {name} pass at layer "
-                                       f"{int((flags != 0).nonzero()[0])}")
 
             # forward pass: run()'s steps; checkpoints before the segments, q of the last segment
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
@@ -546,7 +501,7 @@ class MediumSolver:
                     if last and n < b:
                         keep_level(n, a)
             ev[1].record()
-            check(stat, "forward")
+            _require_finite(stat, "gradient()", "forward pass")
             tr = traces.cpu()
             J, res = reference.misfit_medium(tr, obs)
             anodes, atab = reference.adjoint_source_table(res, self.receivers, N, tt, M)
@@ -584,7 +539,7 @@ class MediumSolver:
                     if wrt_density:  # u1 = mu^{n+1}, injected and wrapped; its level is reused two steps on
                         kernels.face_correlation(u1, ub[n - (a - 1)], accb, box, h2=h2)
             ev[3].record()
-            check(astat, "adjoint")
+            _require_finite(astat, "gradient()", "adjoint pass")
             acc_c, a_c = acc.cpu(), a_dev.cpu()
             gs, gw = reference.finish_gradient_medium(acc_c, a_c, gsrc, mc, tt, self.sources, N, c["tau"],
                                                       c["hx"], c["hy"], c["hz"], M, p.density)
@@ -663,46 +618,19 @@ class MediumSolver:
 
         p = self.problem
         N, K, dt = p.N, p.timesteps, p.torch_dtype
-        if not torch.cuda.is_available():
-            raise RuntimeError("the hip backend needs a HIP device")
-        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else self.device)
-        c = reference.tables(N, K, (p.Lx, p.Ly, p.Lz), p.T, p.pi)[4]
-        h2 = (c["hx2"], c["hy2"], c["hz2"])
-        M, box, wrap, step_kw = self._layout()
+        s = _HipSetup(self)
+        dev, c, M, box, wrap, h2, level = s.dev, s.c, s.M, s.box, s.wrap, s.h2, s.level
         with torch.cuda.device(dev):
-            level_bytes = kernels.level_bytes(N + 1 + 2 * M, N + 1, N + 1, dt)
-            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
             nlev = born_levels(density=p.density is not None)
-            if nlev * level_bytes > free:
-                raise RuntimeError(f"born(): the schedule holds {nlev} levels = {nlev * level_bytes} bytes, but only "
-                                   f"{free} bytes of device memory are free")
+            s.require_levels(nlev, "born(): the schedule")
             t0 = time.perf_counter()
-
-            def level():
-                return kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev)
-
             lv = [level() for _ in range(3)]
             dl = [level() for _ in range(3)]
             m, dm, q = level(), level(), level()
-            m.copy_(reference.medium_coefficient(p.speed2, c["tau"], N, dt, M, p.density))
+            s.medium(m, lv[0], dwavelet=dw)
+            step_kw, taper, g, dg, src, rec = s.step_kw, s.taper, s.g, s.dg, s.src, s.rec
             if ds is not None:  # None: dm = 0, the scattering term adds zeros
                 dm.copy_(reference.medium_coefficient(ds, c["tau"], N, dt, M, p.density))
-            if p.density is not None:
-                bu = level()
-                bu.copy_(reference.buoyancy_field(p.density, N, dt, M))
-                step_kw = dict(step_kw, buoyancy=bu)
-            taper = None
-            if self.taper is not None:
-                taper = tuple(t.to(dev) for t in reference.taper_tables(self.taper, N, dt, M))
-            ent = reference.source_entries(self.sources, N, M)
-            S = len(self.sources)
-            cols = [s for _, s in ent]
-            g = reference.source_table(self.wavelet, K, S, c["hx"], c["hy"], c["hz"], dt)[:, cols].contiguous().to(dev)
-            dg = None
-            if dw is not None:
-                dg = reference.source_table(dw, K, S, c["hx"], c["hy"], c["hz"], dt)[:, cols].contiguous().to(dev)
-            src = kernels.source_nodes([nd for nd, _ in ent], lv[0])
-            rec = kernels.receiver_nodes([(i + M, j, k) for i, j, k in self.receivers], lv[0])
             traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
             dtraces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
@@ -728,11 +656,8 @@ class MediumSolver:
                 kernels.record(d, rec, dtraces[n])
             ev1.record()
             ev1.synchronize()
-            for st, name in ((stat, "background"), (dstat, "perturbation")):  # the one read-back of the flags
-                flags = st[2::3].cpu()
-                if bool((flags != 0).any()):
-                    raise RuntimeError(f"born(): non-finite values in the {name} field at layer "
-                                       f"{int((flags != 0).nonzero()[0])}")
+            _require_finite(stat, "born()", "background field")
+            _require_finite(dstat, "born()", "perturbation field")
             dec = kernels.decode_err(dstat)
             mx = [0.0] + [dec[n][0] for n in range(1, K + 1)]  # du^0 = 0
             duf = dl[K % 3][M:N + 1 + M].cpu()
@@ -753,6 +678,89 @@ class MediumSolver:
         r.extra["dtraces"] = b.dtraces
         r.extra["born_ms"] = b.total_ms
         return r
+
+
+class _HipSetup:
+    """What run(), gradient() and born() share on the "hip" backend: the device, the grid constants
+    ``c`` / ``h2``, the storage layout of :meth:`MediumSolver._layout`, the level allocator, and
+    (:meth:`medium`) the model and source data on the device. The drivers allocate their levels
+    themselves, in their own order."""
+
+    def __init__(self, solver: MediumSolver):
+        from ..ops import reference
+
+        p = solver.problem
+        if not torch.cuda.is_available():
+            raise RuntimeError("the hip backend needs a HIP device")
+        self.solver = solver
+        self.dev = torch.device("cuda", torch.cuda.current_device() if solver.device is None else solver.device)
+        self.c = reference.tables(p.N, p.timesteps, (p.Lx, p.Ly, p.Lz), p.T, p.pi)[4]
+        self.h2 = (self.c["hx2"], self.c["hy2"], self.c["hz2"])
+        self.M, self.box, self.wrap, self.step_kw = solver._layout()
+        self.shape = (p.N + 1 + 2 * self.M, p.N + 1, p.N + 1)
+
+    def level(self):
+        from ..ops import kernels
+
+        return kernels.alloc_level(*self.shape, self.solver.problem.torch_dtype, self.dev)
+
+    def require_levels(self, nlev: int, what: str) -> None:
+        """Raises unless ``nlev`` levels fit into the free device memory; ``what`` names the schedule."""
+        from ..ops import kernels
+
+        dev = self.dev
+        level_bytes = kernels.level_bytes(*self.shape, self.solver.problem.torch_dtype)
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        if nlev * level_bytes > free:
+            raise RuntimeError(f"{what} holds {nlev} levels = {nlev * level_bytes} bytes, but only "
+                               f"{free} bytes of device memory are free")
+
+    def medium(self, m, lv0, dwavelet=None):
+        """Fills the level ``m`` with the coefficient field and returns its host copy; allocates the
+        buoyancy level of a density model into ``step_kw``; then the taper tables (``tt`` on the host,
+        ``taper`` on the device, None without a sponge), the source entries, the source table of the
+        wavelet (``gsrc`` on the host, ``g`` its columns on the device, one per storage node; ``dg``
+        those of ``dwavelet``) and the source and receiver nodes ``src`` / ``rec`` in the strides of
+        the level ``lv0``."""
+        from ..ops import kernels, reference
+
+        sv, c, M, dev = self.solver, self.c, self.M, self.dev
+        p = sv.problem
+        N, K, dt = p.N, p.timesteps, p.torch_dtype
+        mc = reference.medium_coefficient(p.speed2, c["tau"], N, dt, M, p.density)
+        m.copy_(mc)
+        if p.density is not None:
+            bu = self.level()
+            bu.copy_(reference.buoyancy_field(p.density, N, dt, M))
+            self.step_kw = dict(self.step_kw, buoyancy=bu)
+        self.tt = None if sv.taper is None else reference.taper_tables(sv.taper, N, dt, M)
+        self.taper = None if self.tt is None else tuple(t.to(dev) for t in self.tt)
+        ent = reference.source_entries(sv.sources, N, M)
+        cols = [s for _, s in ent]  # one column per storage node
+
+        def table(w):
+            return reference.source_table(w, K, len(sv.sources), c["hx"], c["hy"], c["hz"], dt)
+
+        self.gsrc = table(sv.wavelet)
+        self.g = self.gsrc[:, cols].contiguous().to(dev)
+        self.dg = None if dwavelet is None else table(dwavelet)[:, cols].contiguous().to(dev)
+        self.src = kernels.source_nodes([nd for nd, _ in ent], lv0)
+        self.rec = kernels.receiver_nodes([(i + M, j, k) for i, j, k in sv.receivers], lv0)
+        return mc
+
+
+def _nonfinite_layer(stat, upto: int | None = None):
+    """The first layer whose non-finite flag is set in the statistics ``stat`` (of the layers
+    0..``upto``; None: all), or None: one read-back of the flags."""
+    flags = (stat[2::3] if upto is None else stat[2:3 * upto + 3:3]).cpu()
+    bad = (flags != 0).nonzero()
+    return int(bad[0]) if len(bad) else None
+
+
+def _require_finite(stat, who: str, what: str) -> None:
+    n = _nonfinite_layer(stat)
+    if n is not None:
+        raise RuntimeError(f"{who}: non-finite values in the {what} at layer {n}")
 
 
 @dataclass
