@@ -17,6 +17,7 @@
 #include <pybind11/stl.h>
 
 #include "checkpoint.hpp"
+#include "deep_halo.hpp"
 #include "hip_kernels.hpp"
 #include "hip_medium.hpp"
 #include "problem.hpp"
@@ -509,6 +510,56 @@ PYBIND11_MODULE(_wave3d_C, m) {
         r["self_x"] = hp.self_x;
         return r;
     });
+    // the deep-halo plan of one rank as plain lists (deep_halo.hpp): planes are (peer, tag, level,
+    // plane, nplanes), boxes (peer, tag, level, [i0,i1,j0,j1,k0,k1], dx, buf, off), bufs (peer, tag,
+    // count); a round's sbufs / rbufs index `bufs`
+    m.def("deep_halo_plan", [](int N, int nprocs, int rank, std::vector<int> dims, int depth, bool direct,
+                               bool x_self, int tile_rows, int slabs) {
+        int d[3] = {0, 0, 0};
+        for (size_t q = 0; q < dims.size() && q < 3; ++q) d[q] = dims[q];
+        const Topology t = Topology::make(N, nprocs, rank, d);
+        const HaloPlan hp = make_halo_plan(t, i64(t.ext[1] + 2) * (t.ext[2] + 2), t.ext[2] + 2, x_self);
+        const DeepHaloPlan P = plan_deep_halo(t, hp.self_x, depth, depth, direct, tile_rows, slabs);
+        auto bx = [](const Box& b) { return std::vector<int>{b.i0, b.i1, b.j0, b.j1, b.k0, b.k1}; };
+        auto boxes = [&](const std::vector<Box>& v) {
+            py::list l;
+            for (auto& b : v) l.append(bx(b));
+            return l;
+        };
+        auto round = [&](const HaloRound& r) {
+            auto planes = [](const std::vector<PlaneMsg>& v) {
+                py::list l;
+                for (auto& m : v) l.append(py::make_tuple(m.peer, m.tag, m.level, m.plane, m.nplanes));
+                return l;
+            };
+            auto bmsgs = [&](const std::vector<BoxMsg>& v) {
+                py::list l;
+                for (auto& m : v) l.append(py::make_tuple(m.peer, m.tag, m.level, bx(m.box), m.dx, m.buf, m.off));
+                return l;
+            };
+            py::dict o;
+            o["sends"] = planes(r.sends), o["recvs"] = planes(r.recvs);
+            o["bsends"] = bmsgs(r.bsends), o["brecvs"] = bmsgs(r.brecvs);
+            o["sbufs"] = r.sbufs, o["rbufs"] = r.rbufs;
+            return o;
+        };
+        py::dict r;
+        py::list rounds, pipe, bufs;
+        for (auto& q : P.rounds) rounds.append(round(q));
+        for (auto& q : P.pipe) pipe.append(round(q));
+        for (auto& b : P.bufs) bufs.append(py::make_tuple(b.peer, b.tag, b.count));
+        r["rounds"] = rounds, r["pipe"] = pipe, r["bufs"] = bufs;
+        r["slabs"] = boxes(P.slabs), r["shell"] = boxes(P.shell);
+        r["interior"] = bx(P.interior), r["compute_box"] = bx(t.compute_box());
+        r["alias"] = std::vector<bool>{P.alias[0], P.alias[1]};
+        r["ext"] = std::vector<int>{t.ext[0], t.ext[1], t.ext[2]};
+        r["nbr"] = std::vector<std::vector<int>>{{t.nbr[0][0], t.nbr[0][1]}, {t.nbr[1][0], t.nbr[1][1]},
+                                                 {t.nbr[2][0], t.nbr[2][1]}};
+        r["self_x"] = hp.self_x, r["alias_plane"] = kAliasPlane, r["peer_tag"] = kPeerTag;
+        return r;
+    }, py::arg("N"), py::arg("nprocs"), py::arg("rank"), py::arg("dims"), py::arg("depth"), py::arg("direct"),
+       py::arg("x_self"), py::arg("tile_rows"), py::arg("slabs"),
+       "Deep-halo plan of one rank (temporal-blocking sweeps), host only.");
     m.def("dims_create", [](int n, std::vector<int> dims) {
         int d[3] = {0, 0, 0};
         for (size_t q = 0; q < dims.size() && q < 3; ++q) d[q] = dims[q];

@@ -22,6 +22,7 @@
 #include <thread>
 
 #include "checkpoint.hpp"
+#include "deep_halo.hpp"
 #include "device_common.hpp"
 #include "hip_kernels.hpp"
 #include "hip_selftest.hpp"
@@ -95,46 +96,10 @@ struct DevRank {
     Wrap wrap4;                  // depth-4 self-wrap (four-layer blocking: IC and the last layer)
     Box cdom;                    // temporal blocking: where C is a stencil value
     FusedPack<T> pack;           // pointers into sbuf
-    // temporal blocking across ranks (x slabs): plane messages, seam alias plane, boxes
-    struct PlaneMsg {
-        int peer, tag;
-        int level;      // 0 = A level (D of the sweep), 1 = B level (C of the sweep)
-        int plane;      // first logical plane; kAliasPlane = the alias buffer
-        int nplanes;
-    };
-    std::vector<PlaneMsg> tb_sends, tb_recvs;
-    // y/z splits: rows / columns of depth 2 (D) and 1 (C), staged through buffers; round 0
-    // (y) and round 1 (z) run after the x planes, each over the full extent of the previous
-    // axes (ghosts included), so edges arrive without diagonal messages
-    struct BoxMsg {
-        int peer, tag;
-        int level;      // 0 = next A level, 1 = next B level, 2 = seam alias plane (A)
-        Box box;
-        T* buf;
-    };
-    std::vector<BoxMsg> tb_bsends[2], tb_brecvs[2];
-    // --halo direct: one round — every face, edge and corner ghost region of the A / B levels
-    // and of the seam alias planes straight from the rank that owns it (level 0 = A, 1 = B,
-    // 2 = alias A, 3 = alias B; box = source region on sends, ghost region on receives)
-    std::vector<BoxMsg> tb_dsends, tb_drecvs;
-    // ... packed back to back per peer: one message per peer and direction of travel (2x2x2:
-    // 7 peers, one xGMI link each); BoxMsg::buf points into these
-    struct PeerBuf {
-        int peer;
-        T* buf;
-        size_t count;
-    };
-    std::vector<PeerBuf> tb_psends, tb_precvs;
-    // --overlap pipe: the direct plan cut into one group per x slab of the deep sweep (a message
-    // belongs to the slab that computes its source region: x faces and dx != 0 boxes to the end
-    // slabs, dx == 0 boxes cut along x), each group packed per peer like the whole plan
-    struct PipeGroup {
-        std::vector<PlaneMsg> sends, recvs;
-        std::vector<BoxMsg> dsends, drecvs;
-        std::vector<PeerBuf> psends, precvs;
-    };
-    std::vector<PipeGroup> pipe;
-    std::vector<Box> slabs;      // the compute box cut into the sweep's x slabs
+    // temporal blocking across ranks: the deep-halo plan (deep_halo.hpp) and one device buffer
+    // per entry of its `bufs`
+    DeepHaloPlan halo;
+    std::vector<T*> hbuf;
     // the seam alias planes: x=N (first x-rank) or x=0 (last x-rank) of the A and the B level,
     // one pair per parity of the exchange that filled them (alias_plane(): with --overlap pipe a
     // sweep's first halo groups arrive while its later slabs still read the previous pair)
@@ -142,11 +107,9 @@ struct DevRank {
     T* seamc_buf = nullptr;      // earlier layers on the seam partner planes (tb3: 2 planes, tb4: 8)
     T* seamc_in = nullptr;       // the interior's copy (overlapped self-wrap runs)
     T* pinned = nullptr;         // checkpoint staging (2 levels, pinned host memory)
-    Box tb_interior;
-    std::vector<Box> tb_shell;
 };
 
-constexpr int kAliasPlane = -1000;
+static_assert(kShellTileK == kTileK, "the deep-halo plan's k shells are whole tiles of the sweeps");
 
 template <class T>
 class HipSolver {
@@ -260,9 +223,9 @@ public:
                         overlap_ ? "on" : "off", " transport ",
                         ext_ ? ext_->name() : (world_ > 1 ? "loopback" : "self"));
                 log_msg(LogLevel::Debug, "rank ", R.topo.rank, ": ", R.plan.sends.size(),
-                        " face sends, ", R.tb_sends.size(), " deep-halo sends, interior ",
-                        R.interior.empty() ? 0 : 1, " shell boxes ", R.shell.size(), "/",
-                        R.tb_shell.size());
+                        " face sends, ", R.halo.rounds.empty() ? 0 : R.halo.rounds[0].sends.size(),
+                        " deep-halo sends, interior ", R.interior.empty() ? 0 : 1, " shell boxes ", R.shell.size(),
+                        "/", R.halo.shell.size());
             }
             log_msg(LogLevel::Info, "setup ", init_ms_, " ms");
         }
@@ -306,7 +269,7 @@ public:
         if (ext_ || world_ > 1) {
             res.overlap_interior = -1;
             for (auto& R : ranks_) {
-                const i64 c = (tb_ ? R.tb_interior : R.interior).count();
+                const i64 c = (tb_ ? R.halo.interior : R.interior).count();
                 res.overlap_interior = res.overlap_interior < 0 ? c : std::min<long long>(res.overlap_interior, c);
             }
         }
@@ -526,8 +489,9 @@ private:
             if (t.nbr[2][0] >= 0) in.k0 = std::max(in.k0, TKm > 1 ? 1 + TKm : 2);
             if (t.nbr[2][1] >= 0) in.k1 = std::min(in.k1, TKm > 1 ? TKm * ((Z - 1) / TKm) : Z - 1);
             R.interior = in;
-            build_tb_plan(R);
-            if (pipe_c_) build_pipe(R);
+            R.halo.interior = R.compute;
+            if (tb_) R.halo = plan_deep_halo(t, R.plan.self_x, tbd_, G_, direct_, tb_rows_ * tb_waves_, pipe_c_);
+            alloc_deep_halo(R);
             if (tbd_ >= 3 && (R.plan.self_x || t.first(0) || t.last(0))) {
                 // earlier layers on the seam partner planes (three- / four-layer sweeps);
                 // allocated here, never inside a hipGraph capture
@@ -539,22 +503,9 @@ private:
                     HIP_CHECK(hipMemset(R.seamc_in, 0, np * R.gv.si * sizeof(T)));
                 }
             }
-            R.shell.clear();
-            auto add = [&](Box b) {
-                if (!b.empty()) R.shell.push_back(b);
-            };
-            if (in.empty()) {
-                add(c);
-                R.shell_x = int(R.shell.size());
-            } else {
-                add({c.i0, in.i0 - 1, c.j0, c.j1, c.k0, c.k1});
-                add({in.i1 + 1, c.i1, c.j0, c.j1, c.k0, c.k1});
-                R.shell_x = int(R.shell.size());
-                add({in.i0, in.i1, c.j0, in.j0 - 1, c.k0, c.k1});
-                add({in.i0, in.i1, in.j1 + 1, c.j1, c.k0, c.k1});
-                add({in.i0, in.i1, in.j0, in.j1, c.k0, in.k0 - 1});
-                add({in.i0, in.i1, in.j0, in.j1, in.k1 + 1, c.k1});
-            }
+            ShellSplit sp = split_shells(c, in);
+            R.shell = std::move(sp.shell);
+            R.shell_x = sp.nx;
         }
         host_err_.assign(size_t(prob_.K + 1) * kSlotsPerLayer, 0);
     }
@@ -580,16 +531,7 @@ private:
             (void)hipFree(R.seamc_buf);
             (void)hipFree(R.seamc_in);
             if (R.pinned) (void)hipHostFree(R.pinned);
-            for (int q = 0; q < 2; ++q) {
-                for (auto& m : R.tb_bsends[q]) (void)hipFree(m.buf);
-                for (auto& m : R.tb_brecvs[q]) (void)hipFree(m.buf);
-            }
-            for (auto* v : {&R.tb_psends, &R.tb_precvs}) {
-                for (auto& m : *v) (void)hipFree(m.buf);
-            }
-            for (auto& g : R.pipe)
-                for (auto* v : {&g.psends, &g.precvs})
-                    for (auto& m : *v) (void)hipFree(m.buf);
+            for (auto* p : R.hbuf) (void)hipFree(p);
         }
         ranks_.clear();
         if (mirror_buf_) (void)hipFree(mirror_buf_);
@@ -736,319 +678,22 @@ private:
                        R.err + size_t(n) * kSlotsPerLayer, cfg_.chunk, s, cfg_.delta ? u2 : nullptr);
     }
 
-    // Halo plan of the temporal-blocking paths (depth dA = layers per sweep):
-    //  x up:   newest level planes ending at X (last x-rank: at X-1) -> peer ghosts 1-dA..0,
-    //          the level before at depth dA-1, [last: plane X -> peer alias plane(s)]
-    //  x down: mirrored -> peer ghosts X+1..X+dA, [first: plane 1 -> peer alias]
-    //  y, z:   rows / columns staged through buffers, after the x planes, over the full extent
-    //          of the axes exchanged before (edges without diagonal messages)
-    // Sends are listed up then down, receives from-down then from-up: per-peer FIFO order
-    // matches on both ends also when up == down (dims[0] == 2).
-    void build_tb_plan(DevRank<T>& R) {
-        R.tb_sends.clear();
-        R.tb_recvs.clear();
-        const auto& t = R.topo;
-        const int X = t.X(), Y = t.Y(), Z = t.Z();
-        R.tb_interior = R.compute;
-        R.tb_shell.clear();
-        const bool ysplit = t.dims[1] > 1, zsplit = t.dims[2] > 1;
-        if (!tb_ || (R.plan.self_x && !ysplit && !zsplit)) return;
-        using M = typename DevRank<T>::PlaneMsg;
-        using BM = typename DevRank<T>::BoxMsg;
-        // ---- x: whole planes (contiguous, sent in place) ----------------------------------
-        // depth dA of the newest level (next A), dB = dA - 1 of the one before (next B); the
-        // periodic duplicate plane x = N is skipped (mpi_new.cpp:186-187) and shipped to the
-        // other end of the ring as the seam alias plane instead (tags 12/14, 22/24)
-        const int dA = tbd_, dB = tbd_ - 1;
-        if (!R.plan.self_x) {
-            W3D_REQUIRE(X >= 2 * dA, "temporal blocking needs >= 2 x depth planes per rank");
-            // one x rank messaging itself (--x-self-transport): the seam partner planes are
-            // its own planes X and 1 (see sweep), no alias messages
-            const bool first = t.first(0) && t.dims[0] > 1, last = t.last(0) && t.dims[0] > 1;
-            const bool lastx = t.last(0), firstx = t.first(0);
-            const int up = t.nbr[0][1], dn = t.nbr[0][0];
-            const bool aliasB = tbd_ >= 3;
-            R.tb_sends.push_back(M{up, 11, 0, lastx ? X - dA : X - dA + 1, dA});
-            if (last) R.tb_sends.push_back(M{up, 12, 0, X, 1});
-            R.tb_sends.push_back(M{up, 13, 1, lastx ? X - dB : X - dB + 1, dB});
-            if (last && aliasB) R.tb_sends.push_back(M{up, 14, 1, X, 1});
-            R.tb_sends.push_back(M{dn, 21, 0, firstx ? 2 : 1, dA});
-            if (first) R.tb_sends.push_back(M{dn, 22, 0, 1, 1});
-            R.tb_sends.push_back(M{dn, 23, 1, firstx ? 2 : 1, dB});
-            if (first && aliasB) R.tb_sends.push_back(M{dn, 24, 1, 1, 1});
-            R.tb_recvs.push_back(M{dn, 11, 0, 1 - dA, dA});
-            if (first) R.tb_recvs.push_back(M{dn, 12, 0, kAliasPlane, 1});
-            R.tb_recvs.push_back(M{dn, 13, 1, 1 - dB, dB});
-            if (first && aliasB) R.tb_recvs.push_back(M{dn, 14, 1, kAliasPlane, 1});
-            R.tb_recvs.push_back(M{up, 21, 0, X + 1, dA});
-            if (last) R.tb_recvs.push_back(M{up, 22, 0, kAliasPlane, 1});
-            R.tb_recvs.push_back(M{up, 23, 1, X + 1, dB});
-            if (last && aliasB) R.tb_recvs.push_back(M{up, 24, 1, kAliasPlane, 1});
-            if (first || last) {
-                for (int q = 0; q < 2; ++q) {
-                    HIP_CHECK(hipMalloc(&R.alias[q][0], R.gv.si * sizeof(T)));
-                    HIP_CHECK(hipMemset(R.alias[q][0], 0, R.gv.si * sizeof(T)));
-                }
-                if (aliasB) {
-                    for (int q = 0; q < 2; ++q) {
-                        HIP_CHECK(hipMalloc(&R.alias[q][1], R.gv.si * sizeof(T)));
-                        HIP_CHECK(hipMemset(R.alias[q][1], 0, R.gv.si * sizeof(T)));
-                    }
-                }
+    // Device side of the deep-halo plan: the seam alias planes (zeroed: the first sweeps read them
+    // before any exchange fills them) and one staging buffer per entry of the plan's `bufs`
+    void alloc_deep_halo(DevRank<T>& R) {
+        for (int ab = 0; ab < 2; ++ab)
+            for (int q = 0; q < 2 && R.halo.alias[ab]; ++q) {
+                HIP_CHECK(hipMalloc(&R.alias[q][ab], R.gv.si * sizeof(T)));
+                HIP_CHECK(hipMemset(R.alias[q][ab], 0, R.gv.si * sizeof(T)));
             }
-        }
-        // ---- y (round 0) and z (round 1): next A depth dA, next B depth dB ---------------
-        const int G = G_;
-        if (direct_) build_tb_direct(R);
-        for (int ax = 1; ax <= 2 && !direct_; ++ax) {
-            if (t.dims[ax] == 1) continue;
-            const int n = ax == 1 ? Y : Z;
-            auto box = [&](int lo, int hi) {
-                // full extent (ghosts included) on the axes exchanged before this one
-                Box b{1 - G, X + G, 1, Y, 1, Z};
-                if (ax == 1) b.j0 = lo, b.j1 = hi;
-                else b.j0 = 1 - G, b.j1 = Y + G, b.k0 = lo, b.k1 = hi;
-                return b;
-            };
-            auto add = [&](std::vector<BM>& v, int peer, int tag, int level, Box b) {
-                const size_t cnt = size_t(b.i1 - b.i0 + 1) * (b.j1 - b.j0 + 1) * (b.k1 - b.k0 + 1);
-                T* buf = nullptr;
-                HIP_CHECK(hipMalloc(&buf, cnt * sizeof(T)));
-                v.push_back(BM{peer, tag, level, b, buf});
-            };
-            const int base = ax == 1 ? 30 : 50;
-            const int dn = t.nbr[ax][0], up = t.nbr[ax][1];
-            auto& S = R.tb_bsends[ax - 1];
-            auto& V = R.tb_brecvs[ax - 1];
-            // sends: down (to dn) then up; receives: from down then from up — the same
-            // per-peer order on both sides (tag-less RCCL matching)
-            W3D_REQUIRE(n >= 2 * dA, "temporal blocking needs >= 2 x depth nodes per rank on split axes");
-            if (dn >= 0) add(S, dn, base + 1, 0, box(1, dA)), add(S, dn, base + 2, 1, box(1, dB));
-            if (up >= 0)
-                add(S, up, base + 11, 0, box(n - dA + 1, n)), add(S, up, base + 12, 1, box(n - dB + 1, n));
-            if (dn >= 0) add(V, dn, base + 11, 0, box(1 - dA, 0)), add(V, dn, base + 12, 1, box(1 - dB, 0));
-            if (up >= 0)
-                add(V, up, base + 1, 0, box(n + 1, n + dA)), add(V, up, base + 2, 1, box(n + 1, n + dB));
-            // three-layer sweeps also evaluate C on the seam alias plane (k_seam_c), whose
-            // j/k neighbours at the subdomain edge are ghosts: the alias planes of the y/z
-            // neighbours (same x coordinate, so they hold the same global plane) supply them
-            if (tbd_ >= 3 && R.alias[0][0]) {
-                auto abox = [&](int lo, int hi) {
-                    Box b = box(lo, hi);
-                    b.i0 = b.i1 = 0;
-                    return b;
-                };
-                if (dn >= 0) add(S, dn, base + 3, 2, abox(1, dA));
-                if (up >= 0) add(S, up, base + 13, 2, abox(n - dA + 1, n));
-                if (dn >= 0) add(V, dn, base + 13, 2, abox(1 - dA, 0));
-                if (up >= 0) add(V, up, base + 3, 2, abox(n + 1, n + dA));
-                // ... and the B alias plane (level 3, depth dB): the seam stages read B there on
-                // their rings, whose y/z ghosts the x round delivered stale (round 6: tb4 on 2x2x2
-                // with --halo rounds was wrong from the third sweep on; --halo direct sends them)
-                if (R.alias[0][1]) {
-                    if (dn >= 0) add(S, dn, base + 4, 3, abox(1, dB));
-                    if (up >= 0) add(S, up, base + 14, 3, abox(n - dB + 1, n));
-                    if (dn >= 0) add(V, dn, base + 14, 3, abox(1 - dB, 0));
-                    if (up >= 0) add(V, up, base + 4, 3, abox(n + 1, n + dB));
-                }
-            }
-        }
-        // the last layer within dA nodes of a received ghost depends on it (through the rings).
-        // The j/k shells are widened to whole tiles — TJ rows from the compute box's edge, k on
-        // the global 64-column tile grid — so the shell launch runs no partially filled tiles
-        // (a 2-column z shell used 2 of 64 lanes per tile and cost ~20 % of a sweep); the
-        // interior shrinks by the same nodes, so the total work is that of one full sweep. x
-        // shells stay dA planes thin: the march along i handles thin boxes at a small prologue.
-        // The shells also contain every plane / row / column the next exchange sends (the first
-        // and last x-ranks send one plane deeper, skipping the periodic duplicate plane), so the
-        // exchange can start as soon as the shells are done, while the interior still runs.
-        Box c = R.compute, in = c;
-        const int TJ = tb_rows_ * tb_waves_, TKs = kTileK;
-        if (!R.plan.self_x) {
-            const int xs = t.dims[0] > 1 ? 1 : 0;  // one x rank messaging itself: both ends
-            in.i0 = std::max(in.i0, 1 + dA + ((t.first(0) || !xs) ? 1 : 0));
-            in.i1 = std::min(in.i1, X - dA - ((t.last(0) || !xs) ? 1 : 0));
-        }
-        if (t.nbr[1][0] >= 0) in.j0 = std::max(in.j0, std::max(1 + dA, c.j0 + TJ));
-        if (t.nbr[1][1] >= 0) in.j1 = std::min(in.j1, std::min(Y - dA, c.j1 - TJ));
-        if (t.nbr[2][0] >= 0) in.k0 = std::max(in.k0, 1 + TKs * ((dA + TKs - 1) / TKs));
-        if (t.nbr[2][1] >= 0) in.k1 = std::min(in.k1, TKs * ((Z - dA) / TKs));
-        R.tb_interior = in;
-        auto add = [&](Box b) {
-            if (!b.empty()) R.tb_shell.push_back(b);
-        };
-        if (in.empty()) {
-            add(c);
-        } else {
-            add({c.i0, in.i0 - 1, c.j0, c.j1, c.k0, c.k1});
-            add({in.i1 + 1, c.i1, c.j0, c.j1, c.k0, c.k1});
-            add({in.i0, in.i1, c.j0, in.j0 - 1, c.k0, c.k1});
-            add({in.i0, in.i1, in.j1 + 1, c.j1, c.k0, c.k1});
-            add({in.i0, in.i1, in.j0, in.j1, c.k0, in.k0 - 1});
-            add({in.i0, in.i1, in.j0, in.j1, in.k1 + 1, c.k1});
-        }
-    }
-
-    // Single-round deep-halo plan (--halo direct, the default). The round plan above needs three
-    // dependent rounds (x planes, then y boxes over the received x ghosts, then z boxes over both)
-    // so that edges and corners arrive without diagonal messages. On a fully connected xGMI node
-    // every diagonal neighbour has its own link, so here every ghost region — faces, edges,
-    // corners, of A (depth dA) and B (depth dB), and of the seam alias planes — comes straight
-    // from the rank that owns it, all in one transport group: one latency instead of three, all
-    // links busy at once (2x2x2: 7 peers, one link each). Region rules per axis a, receiver R,
-    // sender S = R + d: d_a = -1 -> R's ghosts 1-D..0 from S's top D owned nodes, +1 -> R's
-    // ghosts E+1..E+D from S's bottom D, 0 -> the owned range (and the x ghosts as well when x
-    // wraps inside the rank: the fused wrap fills them). Across the periodic seam the duplicate
-    // plane is skipped (mpi_new.cpp:186-187): the last x-rank sends X-D..X-1, the first 2..D+1,
-    // and the planes x = N / x = 0 themselves travel as the alias planes. Messages are listed
-    // by (level, direction) on both ends, so per-peer FIFO order matches for tag-less RCCL.
-    void build_tb_direct(DevRank<T>& R) {
-        using BM = typename DevRank<T>::BoxMsg;
-        const auto& t = R.topo;
-        const int E[3] = {t.X(), t.Y(), t.Z()};
-        const int dA = tbd_, dB = tbd_ - 1;
-        const bool selfx = R.plan.self_x;  // dims[0] == 1, wrap fused into the kernels
-        const bool seam = t.dims[0] > 1;   // alias planes exist (first / last x-rank)
-        auto peer = [&](const int d[3]) -> int {  // rank at coords + d, -1 outside y/z
-            int c[3];
-            for (int a = 0; a < 3; ++a) {
-                c[a] = t.coords[a] + d[a];
-                if (a == 0) c[a] = ((c[a] % t.dims[0]) + t.dims[0]) % t.dims[0];
-                else if (c[a] < 0 || c[a] >= t.dims[a]) return -1;
-            }
-            return t.rank_of(c[0], c[1], c[2]);
-        };
-        auto add = [&](std::vector<BM>& v, int pr, int tag, int level, Box b) {
-            v.push_back(BM{pr, tag, level, b, nullptr});  // buffer: the peer's packed message
-        };
-        // receive box of R for direction d (ghost region), depth D
-        auto rbox = [&](const int d[3], int D, bool alias) {
-            int lo[3], hi[3];
-            for (int a = 0; a < 3; ++a) {
-                if (d[a] < 0) lo[a] = 1 - D, hi[a] = 0;
-                else if (d[a] > 0) lo[a] = E[a] + 1, hi[a] = E[a] + D;
-                else if (a == 0 && selfx) lo[a] = 1 - D, hi[a] = E[a] + D;
-                else lo[a] = 1, hi[a] = E[a];
-            }
-            if (alias) lo[0] = hi[0] = 0;  // the alias buffer's one plane (logical i = 0)
-            return Box{lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]};
-        };
-        // source box of R for a receiver Q = R - d (R fills Q's ghosts in direction d)
-        auto sbox = [&](const int d[3], int D, bool alias) {
-            int lo[3], hi[3];
-            for (int a = 0; a < 3; ++a) {
-                // crossing the periodic seam from Q to R: Q first and R last x-rank (d = -1),
-                // or Q last and R first (d = +1); with one x rank messaging itself both hold
-                const int tw = a == 0 && ((d[a] < 0 && t.last(0)) || (d[a] > 0 && t.first(0))) ? 1 : 0;
-                if (d[a] < 0) lo[a] = E[a] - D + 1 - tw, hi[a] = E[a] - tw;
-                else if (d[a] > 0) lo[a] = 1 + tw, hi[a] = D + tw;
-                else if (a == 0 && selfx) lo[a] = 1 - D, hi[a] = E[a] + D;
-                else lo[a] = 1, hi[a] = E[a];
-            }
-            if (alias) lo[0] = hi[0] = d[0] < 0 ? E[0] : 1;  // plane x = N (last) / x = 0 (first)
-            return Box{lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]};
-        };
-        for (int level = 0; level < (tbd_ >= 3 ? 4 : 3); ++level) {
-            const bool alias = level >= 2;
-            if (alias && !seam) continue;
-            const int D = (level == 0 || level == 2) ? dA : dB;
-            int q = 0;
-            for (int dx = -1; dx <= 1; ++dx)
-                for (int dy = -1; dy <= 1; ++dy)
-                    for (int dz = -1; dz <= 1; ++dz, ++q) {
-                        if (!dx && !dy && !dz) continue;
-                        if (selfx && dx) continue;  // x ghosts: fused wrap
-                        if (alias && !dx) continue;  // alias planes cross the x seam only
-                        if (!dy && !dz) continue;    // x faces: whole planes in place (x list)
-                        const int tag = 200 + q * 4 + level;
-                        const int d[3] = {dx, dy, dz}, md[3] = {-dx, -dy, -dz};
-                        // receive: from S = R + d into R's ghosts (alias: R first x-rank <- last
-                        // for d_x = -1, R last <- first for d_x = +1)
-                        const int S = peer(d);
-                        const bool ra = !alias || (dx < 0 ? t.first(0) : t.last(0));
-                        if (S >= 0 && ra) add(R.tb_drecvs, S, tag, level, rbox(d, D, alias));
-                        // send: to Q = R - d from R's own nodes (alias: R last x-rank -> first
-                        // for d_x = -1, R first -> last for d_x = +1)
-                        const int Q = peer(md);
-                        const bool sa = !alias || (dx < 0 ? t.last(0) : t.first(0));
-                        if (Q >= 0 && sa) add(R.tb_dsends, Q, tag, level, sbox(d, D, alias));
-                    }
-        }
-        aggregate(R.tb_dsends, R.tb_psends);
-        aggregate(R.tb_drecvs, R.tb_precvs);
-    }
-    // one buffer per peer: its boxes back to back in (level, direction) order — the order in which
-    // both ends list them, so the packed messages have the same layout
-    void aggregate(std::vector<typename DevRank<T>::BoxMsg>& v, std::vector<typename DevRank<T>::PeerBuf>& agg) {
-        std::vector<int> peers;
-        for (auto& m : v)
-            if (std::find(peers.begin(), peers.end(), m.peer) == peers.end()) peers.push_back(m.peer);
-        std::sort(peers.begin(), peers.end());
-        for (int pr : peers) {
-            size_t n = 0;
-            for (auto& m : v)
-                if (m.peer == pr) n += size_t(m.box.count());
-            T* buf = nullptr;
-            HIP_CHECK(hipMalloc(&buf, n * sizeof(T)));
-            size_t off = 0;
-            for (auto& m : v)
-                if (m.peer == pr) m.buf = buf + off, off += size_t(m.box.count());
-            agg.push_back({pr, buf, n});
-        }
-    }
-
-    // --overlap pipe: slab j of a deep sweep covers planes xs(j) .. xs(j+1)-1 of 1..X (the same cut
-    // on every rank of an x coordinate, so y/z neighbours cut their messages alike). Group j holds
-    // what slab j computes: the x faces and the dx != 0 boxes of the direct plan go with the end
-    // slab that holds their source planes (dx < 0 / the x+ faces: slab C-1; dx > 0 / the x- faces:
-    // slab 0; each slab is >= depth + 1 planes thick, pipe_slabs()), the dx == 0 boxes are cut
-    // along x. Both ends derive the groups from plans that already match message for message, and
-    // cut them the same way, so every group's packed per-peer messages match too.
-    void build_pipe(DevRank<T>& R) {
-        using BM = typename DevRank<T>::BoxMsg;
-        using PG = typename DevRank<T>::PipeGroup;
-        const int C = pipe_c_, X = R.topo.X();
-        auto xs = [&](int j) { return 1 + int(i64(j) * X / C); };
-        R.slabs.clear();
-        for (int j = 0; j < C; ++j) {
-            Box b = R.compute;
-            if (j > 0) b.i0 = std::max(b.i0, xs(j));
-            if (j < C - 1) b.i1 = std::min(b.i1, xs(j + 1) - 1);
-            R.slabs.push_back(b);
-        }
-        R.pipe.assign(size_t(C), PG{});
-        // x faces: tags 11-14 travel up from the top planes, 21-24 down from the bottom ones
-        for (auto& m : R.tb_sends) R.pipe[m.tag < 20 ? C - 1 : 0].sends.push_back(m);
-        for (auto& m : R.tb_recvs) R.pipe[m.tag < 20 ? C - 1 : 0].recvs.push_back(m);
-        // direct boxes: tag = 200 + 4 q + level, q = 9 (dx+1) + 3 (dy+1) + (dz+1)
-        auto split = [&](const std::vector<BM>& v, std::vector<BM> PG::*dst) {
-            for (const auto& m : v) {
-                const int dx = (m.tag - 200) / 4 / 9 - 1;
-                if (dx) {
-                    (R.pipe[dx < 0 ? C - 1 : 0].*dst).push_back(m);
-                    continue;
-                }
-                for (int j = 0; j < C; ++j) {
-                    BM p = m;
-                    if (j > 0) p.box.i0 = std::max(p.box.i0, xs(j));
-                    if (j < C - 1) p.box.i1 = std::min(p.box.i1, xs(j + 1) - 1);
-                    if (p.box.i0 <= p.box.i1) (R.pipe[j].*dst).push_back(p);
-                }
-            }
-        };
-        split(R.tb_dsends, &PG::dsends);
-        split(R.tb_drecvs, &PG::drecvs);
-        for (auto& g : R.pipe) aggregate(g.dsends, g.psends), aggregate(g.drecvs, g.precvs);
+        R.hbuf.assign(R.halo.bufs.size(), nullptr);
+        for (size_t q = 0; q < R.hbuf.size(); ++q) HIP_CHECK(hipMalloc(&R.hbuf[q], R.halo.bufs[q].count * sizeof(T)));
     }
 
     // single-step overlap: y/z shells as whole tiles of the march kernel (else flat shells)
     bool shells_tiled() const { return kind_.march && !kind_.flat; }
 
-    bool tb_halo(const DevRank<T>& R) const {
-        return !R.tb_sends.empty() || !R.tb_bsends[0].empty() || !R.tb_bsends[1].empty() ||
-               !R.tb_brecvs[0].empty() || !R.tb_brecvs[1].empty() || !R.tb_dsends.empty() ||
-               !R.tb_drecvs.empty();
-    }
+    bool tb_halo(const DevRank<T>& R) const { return R.halo.any(); }
 
     // logical plane 0 of the seam alias plane (ab: 0 = A, 1 = B level) holding layer `layer`'s
     // plane: the pair of that layer's exchange (layers one sweep apart alternate), nullptr on
@@ -1057,201 +702,100 @@ private:
         T* p = R.alias[(std::max(layer, 0) / std::max(tbd_, 1)) & 1][ab];
         return p ? p + R.plane_off : nullptr;
     }
-    void* tb_ptr(DevRank<T>& R, const typename DevRank<T>::PlaneMsg& m, int mD) {
+    void* tb_ptr(DevRank<T>& R, const PlaneMsg& m, int mD) {
         if (m.plane == kAliasPlane) return alias_plane(R, mD, m.level) - R.plane_off;
         return plane(R, lvl(m.level == 0 ? mD : mD - 1), m.plane);
     }
 
-    // exchange after a sweep whose D layer is mD (A level = mD, B level = mD-1)
-    // --halo direct: pack every message, one transport group (or loopback copies), unpack.
-    // Grid of a message's box: levels 0 / 1 are the A / B levels; the seam alias levels 2 / 3 are
-    // sent from the sender's own A / B planes (x = N or x = 0) and received into the alias
-    // buffers (one plane, logical i = 0).
-    T* direct_grid(DevRank<T>& R, int level, int mD, bool send) {
-        if (level >= 2 && !send) return alias_plane(R, mD, level - 2);
+    // Grid of a box of the exchange after a sweep whose D layer is mD (A level = mD, B level =
+    // mD-1): levels 0 / 1 are the A / B levels; the seam alias levels 2 / 3 are the alias buffers
+    // (one plane, logical i = 0) — except on the sends of the direct plan, which take them from
+    // the sender's own A / B planes (x = N or x = 0).
+    T* box_grid(DevRank<T>& R, int level, int mD, bool send) {
+        if (level >= 2 && !(direct_ && send)) return alias_plane(R, mD, level - 2);
         return R.g[lvl(level % 2 == 0 ? mD : mD - 1)];
     }
-    void box_copies(DevRank<T>& R, std::vector<typename DevRank<T>::BoxMsg>& v, int mD, bool to_buf, hipStream_t s) {
+    void box_copies(DevRank<T>& R, const std::vector<BoxMsg>& v, int mD, bool to_buf, hipStream_t s) {
         for (size_t q0 = 0; q0 < v.size(); q0 += kMaxBoxCopy) {
             BoxCopy<T> o[kMaxBoxCopy];
             int n = 0;
             for (size_t q = q0; q < v.size() && n < kMaxBoxCopy; ++q, ++n) {
                 // an alias buffer holds one plane: never let a box index another (host check)
-                W3D_REQUIRE(v[q].level < 2 || to_buf || (v[q].box.i0 == 0 && v[q].box.i1 == 0),
-                            "direct halo: alias box outside its one-plane buffer");
-                o[n].grid = direct_grid(R, v[q].level, mD, to_buf), o[n].buf = v[q].buf, o[n].b = v[q].box;
+                W3D_REQUIRE(v[q].level < 2 || (direct_ && to_buf) || (v[q].box.i0 == 0 && v[q].box.i1 == 0),
+                            "deep halo: alias box outside its one-plane buffer");
+                o[n].grid = box_grid(R, v[q].level, mD, to_buf), o[n].buf = R.hbuf[size_t(v[q].buf)] + v[q].off;
+                o[n].b = v[q].box;
             }
             launch_box_copy<T>(o, n, R.gv, to_buf, s);
         }
     }
-    // the message lists of one direct exchange: the whole plan, or one x-slab group (--overlap pipe)
-    struct HaloLists {
-        std::vector<typename DevRank<T>::PlaneMsg>*sends, *recvs;
-        std::vector<typename DevRank<T>::BoxMsg>*dsends, *drecvs;
-        std::vector<typename DevRank<T>::PeerBuf>*psends, *precvs;
-    };
-    static HaloLists whole_plan(DevRank<T>& R) {
-        return {&R.tb_sends, &R.tb_recvs, &R.tb_dsends, &R.tb_drecvs, &R.tb_psends, &R.tb_precvs};
-    }
-    static HaloLists pipe_group(DevRank<T>& R, int g) {
-        auto& G = R.pipe[size_t(g)];
-        return {&G.sends, &G.recvs, &G.dsends, &G.drecvs, &G.psends, &G.precvs};
-    }
-    void exchange_direct(int mD, hipStream_t s) {
-        exchange_lists(mD, s, [](DevRank<T>& R) { return whole_plan(R); });
-    }
-    template <class Sel>
-    void exchange_lists(int mD, hipStream_t s, Sel sel, bool inject = true) {
-        for (auto& R : ranks_) box_copies(R, *sel(R).dsends, mD, true, s);
+
+    // One transport round: snd[q] / rcv[q] are what local rank q sends / receives. External
+    // transport: the link model of this rank's sends, then one group. Simulated ranks: the link
+    // model of the busiest (sender, receiver) pair, then every send copied to the receive of the
+    // same (peer, tag) on its destination rank. Timer slots 6 / 7 bracket the transport — always
+    // on loopback, with an external transport only when this rank has a message in the round.
+    using Messages = std::vector<std::vector<Message>>;
+    void deliver(const char* kind, const Messages& snd, const Messages& rcv, hipStream_t s) {
+        if (ext_ && snd[0].empty() && rcv[0].empty()) return;
         mark(s, 6);
-        constexpr int kPeerTag = 199;  // one packed message per peer and direction of travel
-        if (ext_) {
-            // x faces as whole planes sent and received in place (their y/z ghost rows are
-            // overwritten by the edge boxes unpacked after the group), then one packed message
-            // per peer — the same order on both ends
-            auto& R = ranks_[0];
-            const HaloLists L = sel(R);
-            std::vector<Message> snd, rcv;
-            for (auto& m : *L.sends)
-                snd.push_back({m.peer, m.tag, tb_ptr(R, m, mD), size_t(m.nplanes) * R.gv.si * sizeof(T)});
-            for (auto& m : *L.recvs)
-                rcv.push_back({m.peer, m.tag, tb_ptr(R, m, mD), size_t(m.nplanes) * R.gv.si * sizeof(T)});
-            for (auto& m : *L.psends) snd.push_back({m.peer, kPeerTag, m.buf, m.count * sizeof(T)});
-            for (auto& m : *L.precvs) rcv.push_back({m.peer, kPeerTag, m.buf, m.count * sizeof(T)});
-            model_link_ext(snd, s);
-            if (!snd.empty() || !rcv.empty()) ext_->exchange(snd, rcv, s);
-        } else {
-            std::map<std::pair<int, int>, size_t> link;
-            for (auto& S : ranks_) {
-                for (auto& m : *sel(S).sends) link[{S.topo.rank, m.peer}] += size_t(m.nplanes) * S.gv.si * sizeof(T);
-                for (auto& m : *sel(S).psends) link[{S.topo.rank, m.peer}] += m.count * sizeof(T);
+        std::map<std::pair<int, int>, size_t> link;
+        for (size_t q = 0; q < snd.size(); ++q)
+            for (const auto& m : snd[q]) link[{ranks_[q].topo.rank, m.peer}] += m.bytes;
+        if (!ext_ || !link.empty()) model_link(link, s);
+        if (ext_) ext_->exchange(snd[0], rcv[0], s);
+        for (size_t q = 0; q < snd.size() && !ext_; ++q)  // simulated ranks: local index = rank
+            for (const auto& m : snd[q]) {
+                auto who = [&] {
+                    return std::string(kind) + " message tag " + std::to_string(m.tag) + " from rank " +
+                           std::to_string(q) + " to rank " + std::to_string(m.peer);
+                };
+                const Message* to = nullptr;
+                for (const auto& g : rcv[size_t(m.peer)])
+                    if (g.peer == int(q) && g.tag == m.tag) {
+                        to = &g;
+                        break;
+                    }
+                W3D_REQUIRE(to, "unmatched " + who());
+                W3D_REQUIRE(to->bytes == m.bytes, "size mismatch of " + who());
+                loop_copy(to->ptr, m.ptr, m.bytes, int(q), m.peer, m.tag, s);
             }
-            model_link(link, s);
-            for (auto& S : ranks_)
-                for (auto& m : *sel(S).sends) {
-                    auto& D = ranks_[m.peer];
-                    bool done = false;
-                    for (auto& g : *sel(D).recvs)
-                        if (g.peer == S.topo.rank && g.tag == m.tag) {
-                            W3D_REQUIRE(g.nplanes == m.nplanes, "tb halo size mismatch");
-                            loop_copy(tb_ptr(D, g, mD), tb_ptr(S, m, mD), size_t(m.nplanes) * S.gv.si * sizeof(T),
-                                      S.topo.rank, D.topo.rank, m.tag, s);
-                            done = true;
-                            break;
-                        }
-                    W3D_REQUIRE(done, "unmatched tb halo message");
-                }
-            for (auto& S : ranks_)
-                for (auto& m : *sel(S).psends) {
-                    bool done = false;
-                    for (auto& g : *sel(ranks_[m.peer]).precvs)
-                        if (g.peer == S.topo.rank) {
-                            W3D_REQUIRE(g.count == m.count, "direct halo size mismatch between ranks " +
-                                                                std::to_string(S.topo.rank) + " and " +
-                                                                std::to_string(m.peer));
-                            loop_copy(g.buf, m.buf, m.count * sizeof(T), S.topo.rank, m.peer, kPeerTag, s);
-                            done = true;
-                            break;
-                        }
-                    W3D_REQUIRE(done, "unmatched direct halo message to rank " + std::to_string(m.peer));
-                }
-        }
         mark(s, 7);
-        for (auto& R : ranks_) box_copies(R, *sel(R).drecvs, mD, false, s);
-        if (inject)
-            for (auto& R : ranks_) inject_after_exchange(R, mD, s);
     }
 
+    // the transport messages of one round of the deep-halo plan: x planes in place, then the
+    // staging buffers (the same order on both ends)
+    std::vector<Message> round_messages(DevRank<T>& R, const HaloRound& r, int mD, bool send) {
+        std::vector<Message> v;
+        for (const auto& m : send ? r.sends : r.recvs)
+            v.push_back({m.peer, m.tag, tb_ptr(R, m, mD), size_t(m.nplanes) * R.gv.si * sizeof(T)});
+        for (int id : send ? r.sbufs : r.rbufs) {
+            const HaloBuf& b = R.halo.bufs[size_t(id)];
+            v.push_back({b.peer, b.tag, R.hbuf[size_t(id)], b.count * sizeof(T)});
+        }
+        return v;
+    }
+    // pack, deliver, unpack the round sel(R) of every local rank (x-face planes travel in place;
+    // their y/z ghost rows are overwritten by the edge boxes unpacked after the transport)
+    template <class Sel>
+    void exchange_round(int mD, hipStream_t s, Sel sel) {
+        Messages snd, rcv;
+        for (auto& R : ranks_) {
+            box_copies(R, sel(R).bsends, mD, true, s);
+            snd.push_back(round_messages(R, sel(R), mD, true));
+            rcv.push_back(round_messages(R, sel(R), mD, false));
+        }
+        deliver("deep halo", snd, rcv, s);
+        for (auto& R : ranks_) box_copies(R, sel(R).brecvs, mD, false, s);
+    }
+
+    // exchange after a sweep whose D layer is mD: the plan's rounds in order (--halo direct: one;
+    // rounds: x, then y and z strictly after it — a y / z round no rank takes part in is skipped)
     void exchange_tb(int mD, hipStream_t s) {
-        if (direct_) {
-            exchange_direct(mD, s);
-            return;
-        }
-        if (ext_) {
-            auto& R = ranks_[0];
-            std::vector<Message> snd, rcv;
-            for (auto& m : R.tb_sends)
-                snd.push_back({m.peer, m.tag, tb_ptr(R, m, mD), size_t(m.nplanes) * R.gv.si * sizeof(T)});
-            for (auto& m : R.tb_recvs)
-                rcv.push_back({m.peer, m.tag, tb_ptr(R, m, mD), size_t(m.nplanes) * R.gv.si * sizeof(T)});
-            if (!snd.empty() || !rcv.empty()) {
-                mark(s, 6);
-                model_link_ext(snd, s);
-                ext_->exchange(snd, rcv, s);
-                mark(s, 7);
-            }
-        } else {
-            mark(s, 6);
-            for (auto& S : ranks_)
-                for (auto& m : S.tb_sends) {
-                    auto& D = ranks_[m.peer];
-                    bool done = false;
-                    for (auto& g : D.tb_recvs)
-                        if (g.peer == S.topo.rank && g.tag == m.tag) {
-                            W3D_REQUIRE(g.nplanes == m.nplanes, "tb halo size mismatch");
-                            loop_copy(tb_ptr(D, g, mD), tb_ptr(S, m, mD), size_t(m.nplanes) * S.gv.si * sizeof(T),
-                                      S.topo.rank, D.topo.rank, m.tag, s);
-                            done = true;
-                            break;
-                        }
-                    W3D_REQUIRE(done, "unmatched tb halo message");
-                }
-            mark(s, 7);
-        }
-        // y then z rounds: pack -> transport / D2D -> unpack, strictly after the x planes
-        for (int rd = 0; rd < 2; ++rd) {
-            bool any = false;
-            for (auto& R : ranks_) any |= !R.tb_bsends[rd].empty() || !R.tb_brecvs[rd].empty();
-            if (!any) continue;
-            auto ops = [&](DevRank<T>& R, std::vector<typename DevRank<T>::BoxMsg>& v) {
-                std::vector<BoxCopy<T>> o;
-                for (auto& m : v) {
-                    BoxCopy<T> b;
-                    // levels 2 / 3 = the seam alias planes of A / B (one-plane buffers at logical i = 0)
-                    b.grid = m.level >= 2 ? alias_plane(R, mD, m.level - 2) : R.g[lvl(m.level == 0 ? mD : mD - 1)];
-                    b.buf = m.buf;
-                    b.b = m.box;
-                    o.push_back(b);
-                }
-                return o;
-            };
-            for (auto& R : ranks_) {
-                auto o = ops(R, R.tb_bsends[rd]);
-                launch_box_copy<T>(o.data(), int(o.size()), R.gv, true, s);
-            }
-            auto bytes = [](const typename DevRank<T>::BoxMsg& m) {
-                const Box& b = m.box;
-                return size_t(b.i1 - b.i0 + 1) * (b.j1 - b.j0 + 1) * (b.k1 - b.k0 + 1) * sizeof(T);
-            };
-            if (ext_) {
-                auto& R = ranks_[0];
-                std::vector<Message> snd, rcv;
-                for (auto& m : R.tb_bsends[rd]) snd.push_back({m.peer, m.tag, m.buf, bytes(m)});
-                for (auto& m : R.tb_brecvs[rd]) rcv.push_back({m.peer, m.tag, m.buf, bytes(m)});
-                mark(s, 6);
-                model_link_ext(snd, s);
-                ext_->exchange(snd, rcv, s);
-                mark(s, 7);
-            } else {
-                mark(s, 6);
-                for (auto& S : ranks_)
-                    for (auto& m : S.tb_bsends[rd]) {
-                        bool done = false;
-                        for (auto& g : ranks_[m.peer].tb_brecvs[rd])
-                            if (g.peer == S.topo.rank && g.tag == m.tag) {
-                                W3D_REQUIRE(bytes(g) == bytes(m), "tb box halo size mismatch");
-                                loop_copy(g.buf, m.buf, bytes(m), S.topo.rank, m.peer, m.tag, s);
-                                done = true;
-                                break;
-                            }
-                        W3D_REQUIRE(done, "unmatched tb box halo message");
-                    }
-                mark(s, 7);
-            }
-            for (auto& R : ranks_) {
-                auto o = ops(R, R.tb_brecvs[rd]);
-                launch_box_copy<T>(o.data(), int(o.size()), R.gv, false, s);
-            }
+        for (size_t rd = 0; rd < ranks_[0].halo.rounds.size(); ++rd) {
+            bool any = rd == 0;
+            for (auto& R : ranks_) any |= !R.halo.rounds[rd].empty();
+            if (any) exchange_round(mD, s, [rd](DevRank<T>& R) -> const HaloRound& { return R.halo.rounds[rd]; });
         }
         for (auto& R : ranks_) inject_after_exchange(R, mD, s);
     }
@@ -1297,7 +841,7 @@ private:
     }
 
     // x-slab pipelined deep sweep (--overlap pipe, the x-pipelined exchange): the sweep runs as
-    // pipe_c_ launches over x slabs (build_pipe), and after each slab its halo group goes out on
+    // pipe_c_ launches over x slabs (deep_halo.cpp), and after each slab its halo group goes out on
     // the comm stream while the next slab computes; no interior/shell split, every launch a full
     // j/k extent of whole tiles. A slab waits only for the groups of the previous exchange it
     // reads: its own and both neighbours' (its rings reach `depth` planes past the slab; slab 0's
@@ -1318,13 +862,15 @@ private:
             }
             for (auto& R : ranks_) {
                 if ((sl == 0 && R.topo.first(0)) || (sl == C - 1 && R.topo.last(0))) seam_pre(R, n, span, s_comp_);
-                sweep_deep(R, n, span, s_comp_, &R.slabs[size_t(sl)], 1);
+                sweep_deep(R, n, span, s_comp_, &R.halo.slabs[size_t(sl)], 1);
             }
             if (!send) continue;
             HIP_CHECK(hipEventRecord(ev_slab_, s_comp_));
             HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_slab_, 0));
             mark(s_comm_, 2);
-            exchange_lists(mD, s_comm_, [sl](DevRank<T>& R) { return pipe_group(R, sl); }, p == C - 1);
+            exchange_round(mD, s_comm_, [sl](DevRank<T>& R) -> const HaloRound& { return R.halo.pipe[size_t(sl)]; });
+            if (p == C - 1)
+                for (auto& R : ranks_) inject_after_exchange(R, mD, s_comm_);
             mark(s_comm_, 3);
             HIP_CHECK(hipEventRecord(ev_grp_[cur][sl], s_comm_));
         }
@@ -1491,52 +1037,20 @@ private:
         }
     }
 
-    // Exchange of layer n, issued on stream s (loopback: all ranks; transport: this rank).
+    // Exchange of layer n, issued on stream s (loopback: all ranks; transport: this rank); the
+    // y/z faces were packed by the step kernels (or pack_faces)
     void exchange(int n, hipStream_t s) {
-        if (ext_) {
-            auto& R = ranks_[0];
-            std::vector<Message> snd, rcv;
+        Messages snd, rcv;
+        for (auto& R : ranks_) {
+            snd.emplace_back(), rcv.emplace_back();
             for (size_t m = 0; m < R.plan.sends.size(); ++m)
-                snd.push_back({R.plan.sends[m].peer, R.plan.sends[m].tag, send_ptr(R, m, n),
-                               size_t(R.plan.sends[m].count) * sizeof(T)});
+                snd.back().push_back({R.plan.sends[m].peer, R.plan.sends[m].tag, send_ptr(R, m, n),
+                                      size_t(R.plan.sends[m].count) * sizeof(T)});
             for (size_t m = 0; m < R.plan.recvs.size(); ++m)
-                rcv.push_back({R.plan.recvs[m].peer, R.plan.recvs[m].tag, recv_ptr(R, m, n),
-                               size_t(R.plan.recvs[m].count) * sizeof(T)});
-            if (!snd.empty() || !rcv.empty()) {
-                mark(s, 6);
-                model_link_ext(snd, s);
-                ext_->exchange(snd, rcv, s);
-                mark(s, 7);
-            }
-            pack_faces(R, n, s, false);
-            inject_after_exchange(R, n, s);
-            return;
+                rcv.back().push_back({R.plan.recvs[m].peer, R.plan.recvs[m].tag, recv_ptr(R, m, n),
+                                      size_t(R.plan.recvs[m].count) * sizeof(T)});
         }
-        mark(s, 6);
-        {
-            std::map<std::pair<int, int>, size_t> link;
-            for (auto& S : ranks_)
-                for (auto& f : S.plan.sends) link[{S.topo.rank, f.peer}] += size_t(f.count) * sizeof(T);
-            model_link(link, s);
-        }
-        for (auto& S : ranks_)
-            for (size_t m = 0; m < S.plan.sends.size(); ++m) {
-                const auto& f = S.plan.sends[m];
-                auto& D = ranks_[f.peer];
-                bool done = false;
-                for (size_t q = 0; q < D.plan.recvs.size(); ++q) {
-                    const auto& g = D.plan.recvs[q];
-                    if (g.peer == S.topo.rank && g.tag == f.tag) {
-                        W3D_REQUIRE(g.count == f.count, "halo size mismatch");
-                        loop_copy(recv_ptr(D, q, n), send_ptr(S, m, n), f.count * sizeof(T), S.topo.rank,
-                                  D.topo.rank, f.tag, s);
-                        done = true;
-                        break;
-                    }
-                }
-                W3D_REQUIRE(done, "unmatched halo message");
-            }
-        mark(s, 7);
+        deliver("face halo", snd, rcv, s);
         for (auto& R : ranks_) {
             pack_faces(R, n, s, false);
             inject_after_exchange(R, n, s);
@@ -1553,12 +1067,6 @@ private:
     // through the staged transport): its own busiest outgoing link — every rank sends at once, so
     // the exchange lasts about that long on every rank (bench.py --model-link rehearses the
     // 8-GPU decompositions on one GPU with a link cost)
-    void model_link_ext(const std::vector<Message>& snd, hipStream_t s) {
-        if (cfg_.model_link_gbps <= 0 || snd.empty()) return;
-        std::map<std::pair<int, int>, size_t> link;
-        for (const auto& m : snd) link[{ranks_[0].topo.rank, m.peer}] += m.bytes;
-        model_link(link, s);
-    }
     void model_link(const std::map<std::pair<int, int>, size_t>& link_bytes, hipStream_t s) {
         if (cfg_.model_link_gbps <= 0) return;
         size_t most = 0;
@@ -1608,10 +1116,9 @@ private:
         size_t most = 8 * (size_t(prob_.K) + 1) * kSlotsPerLayer;  // the error-key allreduce
         for (auto& R : ranks_) {
             for (auto& f : R.plan.sends) most = std::max(most, size_t(f.count) * sizeof(T));
-            for (auto& m : R.tb_sends) most = std::max(most, size_t(m.nplanes) * size_t(R.gv.si) * sizeof(T));
-            for (int rd = 0; rd < 2; ++rd)
-                for (auto& m : R.tb_bsends[rd]) most = std::max(most, size_t(m.box.count()) * sizeof(T));
-            for (auto& m : R.tb_psends) most = std::max(most, m.count * sizeof(T));
+            for (auto& r : R.halo.rounds)
+                for (auto& m : r.sends) most = std::max(most, size_t(m.nplanes) * size_t(R.gv.si) * sizeof(T));
+            for (auto& b : R.halo.bufs) most = std::max(most, b.count * sizeof(T));
         }
         int dev = 0;
         HIP_CHECK(hipGetDevice(&dev));
@@ -1690,44 +1197,42 @@ private:
             return out;
         }
         const i64 alias_gi = t.first(0) ? prob_.N : 0;  // first x-rank holds x=N, last x=0
-        for (const auto& m : R.tb_recvs) {
-            const unsigned salt = m.level == 0 ? sA : sB;
-            if (m.plane == kAliasPlane) {
-                const T* o = alias_plane(R, mD, m.level);
-                region(m.peer, m.tag, o, Box{0, 0, 1, Y, 1, Z}, salt, alias_gi, "seam alias plane");
-            } else {
-                region(m.peer, m.tag, R.g[m.level == 0 ? lA : lB],
-                       Box{m.plane, m.plane + m.nplanes - 1, 1, Y, 1, Z}, salt, -1, "x planes");
-            }
-        }
-        for (const auto& m : R.tb_drecvs) {  // --halo direct: every message is one box
-            Box b = m.box;
-            if (R.plan.self_x && m.level < 2) b.i0 = std::max(b.i0, 1), b.i1 = std::min(b.i1, X);
-            const unsigned salt = (m.level == 0 || m.level == 2) ? sA : sB;
-            const bool al = m.level >= 2;
-            region(m.peer, m.tag, direct_grid(R, m.level, 2, false), b, salt, al ? alias_gi : -1,
-                   al ? "direct alias box" : "direct box");
-        }
         const int dA = tbd_, dB = tbd_ - 1;
-        for (int rd = 0; rd < 2; ++rd)
-            for (const auto& m : R.tb_brecvs[rd]) {
-                // only what the sender itself held valid: ghosts of depth dA (A) / dB (B) on
-                // the axes exchanged before; a fused local x wrap is not part of the exchange
-                const int d = m.level == 1 || m.level == 3 ? dB : dA;
-                Box b = m.box;
-                if (m.level < 2) {
-                    b.i0 = std::max(b.i0, R.plan.self_x ? 1 : 1 - d);
-                    b.i1 = std::min(b.i1, R.plan.self_x ? X : X + d);
+        for (size_t rd = 0; rd < R.halo.rounds.size(); ++rd) {
+            for (const auto& m : R.halo.rounds[rd].recvs) {
+                const unsigned salt = m.level == 0 ? sA : sB;
+                if (m.plane == kAliasPlane) {
+                    const T* o = alias_plane(R, mD, m.level);
+                    region(m.peer, m.tag, o, Box{0, 0, 1, Y, 1, Z}, salt, alias_gi, "seam alias plane");
+                } else {
+                    region(m.peer, m.tag, R.g[m.level == 0 ? lA : lB],
+                           Box{m.plane, m.plane + m.nplanes - 1, 1, Y, 1, Z}, salt, -1, "x planes");
                 }
-                b.j0 = std::max(b.j0, 1 - d), b.j1 = std::min(b.j1, Y + d);
-                b.k0 = std::max(b.k0, 1 - d), b.k1 = std::min(b.k1, Z + d);
-                if (m.level >= 2)
-                    region(m.peer, m.tag, alias_plane(R, mD, m.level - 2), b,
-                           m.level == 2 ? sA : sB, alias_gi, "alias plane box");
-                else
-                    region(m.peer, m.tag, R.g[m.level == 0 ? lA : lB], b, m.level == 0 ? sA : sB, -1,
-                           rd == 0 ? "y box" : "z box");
             }
+            for (const auto& m : R.halo.rounds[rd].brecvs) {
+                const bool al = m.level >= 2, lvA = m.level % 2 == 0;
+                Box b = m.box;
+                const char* what;
+                if (direct_) {
+                    // every message is one box; a fused local x wrap is not part of the exchange
+                    if (!al && R.plan.self_x) b.i0 = std::max(b.i0, 1), b.i1 = std::min(b.i1, X);
+                    what = al ? "direct alias box" : "direct box";
+                } else {
+                    // only what the sender itself held valid: ghosts of depth dA (A) / dB (B) on
+                    // the axes exchanged before
+                    const int d = lvA ? dA : dB;
+                    if (!al) {
+                        b.i0 = std::max(b.i0, R.plan.self_x ? 1 : 1 - d);
+                        b.i1 = std::min(b.i1, R.plan.self_x ? X : X + d);
+                    }
+                    b.j0 = std::max(b.j0, 1 - d), b.j1 = std::min(b.j1, Y + d);
+                    b.k0 = std::max(b.k0, 1 - d), b.k1 = std::min(b.k1, Z + d);
+                    what = al ? "alias plane box" : (rd == 1 ? "y box" : "z box");
+                }
+                region(m.peer, m.tag, al ? alias_plane(R, mD, m.level - 2) : R.g[lvA ? lA : lB], b, lvA ? sA : sB,
+                       al ? alias_gi : -1, what);
+            }
+        }
         return out;
     }
 
@@ -1999,8 +1504,8 @@ private:
                 HIP_CHECK(hipStreamWaitEvent(s_comp_, ev_halo_, 0));
                 for (auto& R : ranks_) {
                     seam_pre(R, n, span, s_comp_);
-                    if (!R.tb_shell.empty())
-                        sweep_deep(R, n, span, s_comp_, R.tb_shell.data(), int(R.tb_shell.size()));
+                    if (!R.halo.shell.empty())
+                        sweep_deep(R, n, span, s_comp_, R.halo.shell.data(), int(R.halo.shell.size()));
                 }
                 const int last = n + span - 1;
                 if (last < K) {
@@ -2010,7 +1515,7 @@ private:
                     exchanged = true;
                 }
                 for (auto& R : ranks_)
-                    if (!R.tb_interior.empty()) sweep_deep(R, n, span, s_comp_, &R.tb_interior, 1);
+                    if (!R.halo.interior.empty()) sweep_deep(R, n, span, s_comp_, &R.halo.interior, 1);
             } else if (span >= 3 && overlap_) {
                 // Shells on the (high-priority) comm stream right behind the previous halo,
                 // concurrently with the interior on the compute stream, as the two-layer path:
@@ -2023,16 +1528,16 @@ private:
                 HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_layer_, 0));
                 for (auto& R : ranks_) {
                     seam_pre(R, n, span, s_comm_);
-                    if (!R.tb_shell.empty())
-                        sweep_deep(R, n, span, s_comm_, R.tb_shell.data(), int(R.tb_shell.size()));
+                    if (!R.halo.shell.empty())
+                        sweep_deep(R, n, span, s_comm_, R.halo.shell.data(), int(R.halo.shell.size()));
                 }
                 HIP_CHECK(hipEventRecord(ev_shell_, s_comm_));
                 for (auto& R : ranks_) {
                     // periodic self-wrap: the interior spans every x plane, so it reads the seam
                     // partner planes too (at positions that need no remote halo) — from its own
                     // copy, the shells' copy is rewritten concurrently on the comm stream
-                    if (R.plan.self_x && !R.tb_interior.empty()) seam_pre(R, n, span, s_comp_, true);
-                    if (!R.tb_interior.empty()) sweep_deep(R, n, span, s_comp_, &R.tb_interior, 1, true);
+                    if (R.plan.self_x && !R.halo.interior.empty()) seam_pre(R, n, span, s_comp_, true);
+                    if (!R.halo.interior.empty()) sweep_deep(R, n, span, s_comp_, &R.halo.interior, 1, true);
                 }
                 HIP_CHECK(hipStreamWaitEvent(s_comp_, ev_shell_, 0));
                 comm_follows = true;
@@ -2404,7 +1909,7 @@ private:
         return b;
     }
     bool xself_ = false;  // --x-self-transport
-    bool direct_ = true;  // --halo direct: single-round deep-halo plan (build_tb_direct)
+    bool direct_ = true;  // --halo direct: single-round deep-halo plan (deep_halo.cpp)
     static constexpr size_t kMirrorSlots = 2048;
     std::unique_ptr<RcclTransport> mirror_;  // --rccl-mirror: 1-rank communicator
     void* mirror_buf_ = nullptr;
