@@ -16,7 +16,8 @@
 //    Dirichlet faces (described at the kernel).
 //  * k_march_mb: k_march_m with a variable density: the operator div(b grad u) with the buoyancy
 //    b = 1 / rho as a fifth stream that rolls through registers and LDS like u^{n-1} (described at
-//    the kernel).
+//    the kernel). It alone has the scatter and Born-add modes of Born modelling with a density
+//    perturbation.
 //  * all three march kernels have the save, image and Born modes of the adjoint-state gradient and
 //    of Born modelling (MarchMode below; hip_medium.hpp has the contract), and are built from the
 //    tile skeleton of march_tile.hpp and the per-mode pieces below, each written once.
@@ -51,9 +52,11 @@ struct MediumParams : TileParams<T> {
     u64* err;
     const T *gx, *gy, *gz;  // TAPER: sponge factors per axis, storage indexing (X+2, Y+2, Z+2 values)
     T* lap_out;             // kSave: receives lap(u1) at the box nodes (strides of u)
-    const T* q;             // kImage: the grid multiplied with the centre value of u1 ...
+    const T* q;             // kImage: the grid multiplied with the centre value of u1 ... (kScatter: db, below)
     T* acc;                 // ... and the grid the product is added to, at the box nodes
     const T* dm;            // kBorn: the coefficient perturbation; u receives + dm * q (q as above)
+                            // kScatter (k_march_mb): lap_out receives dm * lap + m * r, r = D_db u1 with the
+                            // buoyancy perturbation db, a level like b, in q; kBornAdd: u receives + q
 };
 
 // Modes of the march kernels: the plain step; kSave also stores the Laplacian that entered the
@@ -64,23 +67,30 @@ struct MediumParams : TileParams<T> {
 // (kSave: lap_out), or a read-once stream (q) and a read-modify-write one (kImage: acc), or two
 // read-once streams (kBorn: q and dm, no store beside u's); all at the lane's own nodes, masked
 // like the stores of u and without the periodic wrap.
-enum MarchMode { kPlain = 0, kSave = 1, kImage = 2, kBorn = 3 };
+// Born modelling with a density perturbation (k_march_mb only) splits Born mode's work differently:
+// kScatter is the background step that also stores the whole scattering term s = dm lap + m r,
+// r = D_db u1 with the buoyancy perturbation db in b's place (a read-once stream dm, a write-once
+// stream lap_out = s, and db handled like b: described at the kernel); kBornAdd is the step of the
+// perturbation field that adds it, u = G (((2 u1 - G u2) + m lap) + s) (one read-once stream, q = s).
+enum MarchMode { kPlain = 0, kSave = 1, kImage = 2, kBorn = 3, kScatter = 4, kBornAdd = 5 };
 
 constexpr int kNt = 2;  // cache policy of the read-once and write-once streams: non-temporal
 
-// The two extra streams of image mode (q and acc) and Born mode (q and dm), at the lane's own
-// nodes: two-slot register rings prefetched one plane ahead like m; plane x in slot (x - ib) & 1.
+// The extra read streams of image mode (q and acc), Born mode (q and dm), scatter mode (dm alone) and
+// Born-add mode (q = s alone), at the lane's own nodes: two-slot register rings prefetched one plane
+// ahead like m; plane x in slot (x - ib) & 1.
 template <class T, int R, int MODE>
 struct AuxRings {
-    static constexpr bool kOn = MODE == kImage || MODE == kBorn;
-    T q[kOn ? 2 : 1][kOn ? R : 1], a[kOn ? 2 : 1][kOn ? R : 1];
+    static constexpr bool kQ = MODE == kImage || MODE == kBorn || MODE == kBornAdd;
+    static constexpr bool kA = MODE == kImage || MODE == kBorn || MODE == kScatter;
+    T q[kQ ? 2 : 1][kQ ? R : 1], a[kA ? 2 : 1][kA ? R : 1];
 
     static __device__ __forceinline__ const T* second(const MediumParams<T>& p) {
-        return MODE == kBorn ? p.dm : p.acc;
+        return MODE == kImage ? p.acc : p.dm;
     }
     // plane ib into slot 0
     __device__ __forceinline__ void prime(const Tile<T, R>& t, const MediumParams<T>& p, const unsigned (&os)[R]) {
-        if constexpr (kOn) {
+        if constexpr (kQ && kA) {
             const auto rQ = t.prs(p.q, t.ib), rA = t.prs(second(p), t.ib);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -88,30 +98,52 @@ struct AuxRings {
                 a[0][r] = bld<T, kNt>(rA, os[r]);
                 q[1][r] = a[1][r] = T(0);
             }
+        } else if constexpr (kQ) {
+            const auto rQ = t.prs(p.q, t.ib);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                q[0][r] = bld<T, kNt>(rQ, os[r]);
+                q[1][r] = T(0);
+            }
+        } else if constexpr (kA) {
+            const auto rA = t.prs(second(p), t.ib);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                a[0][r] = bld<T, kNt>(rA, os[r]);
+                a[1][r] = T(0);
+            }
         }
     }
     // plane i + 1 into slot H1
     template <int H1>
     __device__ __forceinline__ void prefetch(Ph<H1>, const Tile<T, R>& t, const MediumParams<T>& p, int i,
                                              bool more, const unsigned (&os)[R]) {
-        if constexpr (kOn) {
+        if constexpr (kQ && kA) {
             const auto rQ = t.next_rsrc(p.q, i, 1, more), rA = t.next_rsrc(second(p), i, 1, more);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 q[H1][r] = bld<T, kNt>(rQ, os[r]);
                 a[H1][r] = bld<T, kNt>(rA, os[r]);
             }
+        } else if constexpr (kQ) {
+            const auto rQ = t.next_rsrc(p.q, i, 1, more);
+#pragma unroll
+            for (int r = 0; r < R; ++r) q[H1][r] = bld<T, kNt>(rQ, os[r]);
+        } else if constexpr (kA) {
+            const auto rA = t.next_rsrc(second(p), i, 1, more);
+#pragma unroll
+            for (int r = 0; r < R; ++r) a[H1][r] = bld<T, kNt>(rA, os[r]);
         }
     }
     // the values of the current plane (slot H0) at row r; 0, and unused, in the other modes
     template <int H0>
     __device__ __forceinline__ T qv(Ph<H0>, int r) const {
-        if constexpr (kOn) return q[H0][r];
+        if constexpr (kQ) return q[H0][r];
         else return T(0);
     }
     template <int H0>
     __device__ __forceinline__ T av(Ph<H0>, int r) const {
-        if constexpr (kOn) return a[H0][r];
+        if constexpr (kA) return a[H0][r];
         else return T(0);
     }
 };
@@ -147,7 +179,7 @@ struct Sponge {
 };
 
 // The new value of a node: centre c = u1, u2, the (density-weighted) Laplacian, m; sponge factors
-// gxi, gyz (TAPER); Born mode's a = dm and q.
+// gxi, gyz (TAPER); Born mode's a = dm and q; Born-add mode's q = s, the scattering term as stored.
 template <class T, bool FIRST, bool TAPER, int MODE>
 __device__ __forceinline__ T medium_update(T c, T u2, T lap, T m, T gxi, T gyz, T a, T q) {
 #pragma clang fp contract(off)
@@ -157,8 +189,8 @@ __device__ __forceinline__ T medium_update(T c, T u2, T lap, T m, T gxi, T gyz, 
         const T v = taylor_first(c, lap, half_m);
         if constexpr (TAPER) return (gxi * gyz) * v;
         else return v;
-    } else if constexpr (MODE == kBorn) {
-        const T pr = a * q;  // dm q, rounded before the add
+    } else if constexpr (MODE == kBorn || MODE == kBornAdd) {
+        const T pr = MODE == kBorn ? a * q : q;  // dm q, rounded before the add; or s itself
         if constexpr (TAPER) {
             const T g = gxi * gyz;
             return g * (leapfrog(c, g * u2, lap, m) + pr);
@@ -173,15 +205,19 @@ __device__ __forceinline__ T medium_update(T c, T u2, T lap, T m, T gxi, T gyz, 
     }
 }
 
-// What a mode stores beside u: kSave the Laplacian, kImage the new acc = a + c q (a = acc)
+// What a mode stores beside u: kSave the Laplacian, kImage the new acc = a + c q (a = acc), kScatter
+// the scattering term a lap + m q (a = dm, q = r = D_db u1), both products rounded before the add
 template <class T, int MODE>
-__device__ __forceinline__ T side_value(T c, T lap, T a, T q) {
+__device__ __forceinline__ T side_value(T c, T lap, T a, T q, T m = T(0)) {
 #pragma clang fp contract(off)
     if constexpr (MODE == kSave) {
         return lap;
     } else if constexpr (MODE == kImage) {
         const T pr = c * q;
         return a + pr;
+    } else if constexpr (MODE == kScatter) {
+        const T p1 = a * lap, p2 = m * q;
+        return p1 + p2;
     } else {
         return T(0);
     }
@@ -202,8 +238,8 @@ __device__ __forceinline__ void store_plane(const Tile<T, R>& t, const MediumPar
 #pragma unroll
             for (int r = 0; r < R; ++r) bst<kNt>(vv[r], rw, os[r]);
         }
-    if constexpr (MODE == kSave || MODE == kImage) {
-        const auto rx = t.prs(MODE == kSave ? p.lap_out : p.acc, i);
+    if constexpr (MODE == kSave || MODE == kImage || MODE == kScatter) {
+        const auto rx = t.prs(MODE == kImage ? p.acc : p.lap_out, i);
 #pragma unroll
         for (int r = 0; r < R; ++r) bst<kNt>(xv[r], rx, os[r]);
     }
@@ -536,11 +572,20 @@ __device__ __forceinline__ T flux_diff(T c, T um, T up, T bc, T bm, T bp) {
 // rows come from registers for b as for u1. The loads of b are ordinary temporal loads (the halo
 // lines are reused across tiles through L2); m stays non-temporal. A masked b reads 0: it only
 // enters nodes whose stores are masked too. 40 B per node in fp64 (20 B in fp32).
+// Scatter mode (kScatter) also evaluates r = D_db u1 with the same operations, db's values in b's
+// place, and stores s = dm D_b u1 + m r where save mode stores D_b u1. db needs its six neighbours
+// too, so it is a third copy of b's machinery: a 4-slot register ring, a third LDS tile of the same
+// shape under the same barrier, one more halo cell per lane and plane with b's offset and masking,
+// temporal loads. dm is a read-once stream (AuxRings). u and the statistic are the plain step's.
+// 64 B per node in fp64: u1, u2, m, b, db, dm read, u and s written. Born-add mode (kBornAdd) reads
+// the stored s back: 48 B.
 template <class T, bool FIRST, int R, bool TAPER, int MODE = kPlain>
 __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p) {
     constexpr int kTJ = kWaves * R;
+    constexpr bool SC = MODE == kScatter;
     __shared__ T lds[2][kTJ + 2][kLW];
     __shared__ T ldb[2][kTJ + 2][kLW];
+    __shared__ T ldd[SC ? 2 : 1][SC ? kTJ + 2 : 1][SC ? kLW : 1];  // db's tile, scatter mode only
     const Tile<T, R> t(p);
     const int lane = t.lane, w = t.w, ib = t.ib;
 
@@ -558,8 +603,21 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
 
     T u1[4][R], bb[4][R], u2[2][R], mm[2][R];
     T hv[2], hb[2];
+    T dd[SC ? 4 : 1][SC ? R : 1], hd[2];  // db's ring and halo cell
     AuxRings<T, R, MODE> aux;
     aux.prime(t, p, os);
+    if constexpr (SC) {  // db travels in p.q (MediumParams)
+        const auto d0 = t.prs(p.q, ib - 1), d1 = t.prs(p.q, ib), d2 = t.prs(p.q, ib + 1);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            dd[0][r] = bld<T>(d0, oa[r]);
+            dd[1][r] = bld<T>(d1, oa[r]);
+            dd[2][r] = bld<T>(d2, oa[r]);
+            dd[3][r] = T(0);
+        }
+        hd[0] = bld<T>(d1, h.hoff);
+        hd[1] = T(0);
+    }
     {
         const auto r0 = t.prs(p.u1, ib - 1), r1 = t.prs(p.u1, ib), r2 = t.prs(p.u1, ib + 1);
         const auto b0 = t.prs(p.b, ib - 1), b1 = t.prs(p.b, ib), b2 = t.prs(p.b, ib + 1);
@@ -605,18 +663,26 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
             }
             hv[H1] = bld<T>(rH, h.hoff);
             hb[H1] = bld<T>(bH, h.hoff);
+            if constexpr (SC) {
+                const auto dN = t.next_rsrc(p.q, i, 2, more), dH = t.next_rsrc(p.q, i, 1, more);
+#pragma unroll
+                for (int r = 0; r < R; ++r) dd[S3][r] = bld<T>(dN, oa[r]);
+                hd[H1] = bld<T>(dH, h.hoff);
+            }
             aux.prefetch(Ph<H1>{}, t, p, i, more, os);
         }
 
-        // stage plane i of u1 and b: one barrier for both tiles
+        // stage plane i of u1 and b (and db): one barrier for all tiles
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             lds[H0][1 + w * R + r][1 + lane] = u1[S1][r];
             ldb[H0][1 + w * R + r][1 + lane] = bb[S1][r];
+            if constexpr (SC) ldd[H0][1 + w * R + r][1 + lane] = dd[S1][r];
         }
         if (h.hon) {
             lds[H0][h.hrow][h.hcol] = hv[H0];
             ldb[H0][h.hrow][h.hcol] = hb[H0];
+            if constexpr (SC) ldd[H0][h.hrow][h.hcol] = hd[H0];
         }
         __syncthreads();
 
@@ -635,8 +701,19 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
             const T tz = flux_diff(c, lds[H0][lr][lane], lds[H0][lr][lane + 2], bc, ldb[H0][lr][lane],
                                    ldb[H0][lr][lane + 2]);
             const T lap = sum_div<T>(tx, ty, tz, p);
-            const T a = aux.av(Ph<H0>{}, r), q = aux.qv(Ph<H0>{}, r);
-            xv[r] = side_value<T, MODE>(c, lap, a, q);
+            const T a = aux.av(Ph<H0>{}, r);
+            T q = aux.qv(Ph<H0>{}, r);
+            if constexpr (SC) {  // q = r = D_db u1
+                const T dc = dd[S1][r];
+                const T djm = r == 0 ? ldd[H0][lr - 1][1 + lane] : dd[S1][r - 1];
+                const T djp = r == R - 1 ? ldd[H0][lr + 1][1 + lane] : dd[S1][r + 1];
+                const T rx = flux_diff(c, u1[S0][r], u1[S2][r], dc, dd[S0][r], dd[S2][r]);
+                const T ry = flux_diff(c, jm, jp, dc, djm, djp);
+                const T rz = flux_diff(c, lds[H0][lr][lane], lds[H0][lr][lane + 2], dc, ldd[H0][lr][lane],
+                                       ldd[H0][lr][lane + 2]);
+                q = sum_div<T>(rx, ry, rz, p);
+            }
+            xv[r] = side_value<T, MODE>(c, lap, a, q, mm[H0][r]);
             vv[r] = medium_update<T, FIRST, TAPER, MODE>(c, u2[H0][r], lap, mm[H0][r], gxi, sponge.yz(r), a, q);
         }
         store_plane<MODE>(t, p, i, vv, xv, os);
@@ -659,6 +736,8 @@ auto select_march(bool first, bool taper, int mode, F pick) {
         case kSave: return with_taper(std::false_type{}, Ph<kSave>{});
         case kImage: return with_taper(std::false_type{}, Ph<kImage>{});
         case kBorn: return with_taper(std::false_type{}, Ph<kBorn>{});
+        case kScatter: return with_taper(std::false_type{}, Ph<kScatter>{});
+        case kBornAdd: return with_taper(std::false_type{}, Ph<kBornAdd>{});
         default: break;
     }
     return first ? with_taper(std::true_type{}, Ph<kPlain>{}) : with_taper(std::false_type{}, Ph<kPlain>{});
@@ -718,7 +797,8 @@ void (*march_m_kernel(bool first, bool taper, int mode, int variant))(const Medi
         constexpr bool FIRST = decltype(fi)::value, TAPER = decltype(ta)::value;
         constexpr int MODE = decltype(mo)::value;
         constexpr int RD = 4;  // march_rows_per_thread()
-        if constexpr (MODE != kPlain) return k_march_m<T, FIRST, RD, true, TAPER, MODE>;
+        if constexpr (MODE == kScatter || MODE == kBornAdd) return nullptr;  // k_march_mb only (the launcher checks)
+        else if constexpr (MODE != kPlain) return k_march_m<T, FIRST, RD, true, TAPER, MODE>;
         else switch (variant & 3) {
                 case 1: return k_march_m<T, FIRST, RD, true, TAPER>;
                 case 2: return k_march_m<T, FIRST, 2, false, TAPER>;
@@ -731,7 +811,9 @@ void (*march_m_kernel(bool first, bool taper, int mode, int variant))(const Medi
 template <class T, int M>
 void (*march_mh_kernel(bool first, bool taper, int mode))(const MediumParamsH<T>) {
     return select_march(first, taper, mode, [](auto fi, auto ta, auto mo) -> void (*)(const MediumParamsH<T>) {
-        return k_march_mh<T, M, decltype(fi)::value, 4, decltype(ta)::value, decltype(mo)::value>;
+        constexpr int MODE = decltype(mo)::value;
+        if constexpr (MODE == kScatter || MODE == kBornAdd) return nullptr;  // k_march_mb only (the launcher checks)
+        else return k_march_mh<T, M, decltype(fi)::value, 4, decltype(ta)::value, MODE>;
     });
 }
 
@@ -769,7 +851,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant, const T* gx,
                         const T* gy, const T* gz, T* lap_out, const T* q, T* acc, int order, const int* mirror,
-                        const T* b, const T* dm) {
+                        const T* b, const T* dm, const T* db, const T* sadd) {
     W3D_REQUIRE(order == 2 || order == 4 || order == 8, "space order must be 2, 4 or 8, not " + std::to_string(order));
     W3D_REQUIRE(!b || order == 2, "variable density (b) exists for space order 2 only");
     const int M = order / 2;
@@ -782,11 +864,28 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     W3D_REQUIRE(gv.sj >= gv.Z + 2 * gv.G && gv.si >= i64(gv.Y + 2 * gv.G) * gv.sj, "strides smaller than the grid");
     if (variant < 0) variant = medium_variant();
     W3D_REQUIRE(!b || variant == 1, "variable density (b) is instantiated for the default variant only (nt, 4 rows per lane)");
+    // Scatter mode (db, with lap_out = s_out and dm) and Born-add mode (sadd = s): k_march_mb only
+    const bool scatter = db != nullptr, born_add = sadd != nullptr;
+    const i64 span = i64(gv.X + 2 * gv.G - 1) * gv.si + i64(gv.Y + 2 * gv.G - 1) * gv.sj + gv.Z + 2 * gv.G;
+    if (scatter || born_add) {
+        W3D_REQUIRE(!(scatter && born_add), "scatter mode (db) and Born-add mode (s) cannot be combined");
+        W3D_REQUIRE(b, "scatter / Born-add modes need the buoyancy b (variable density, order 2, default variant)");
+        W3D_REQUIRE(!first, "scatter / Born-add modes: not on the Taylor start (first)");
+        W3D_REQUIRE(!q && !acc, "scatter / Born-add modes cannot be combined with image or Born mode");
+        if (scatter) {
+            W3D_REQUIRE(lap_out && dm, "scatter mode needs s_out (lap_out) and dm beside db");
+            for (const T* o : {(const T*)u, u1, u2, m, b, dm, db})
+                W3D_REQUIRE(!overlaps<T>(lap_out, o, span), "scatter mode: s_out shares memory with another grid");
+        } else {
+            W3D_REQUIRE(!lap_out && !dm, "Born-add mode cannot be combined with save or Born mode");
+            W3D_REQUIRE(!overlaps<T>(u, sadd, span), "Born-add mode: s shares memory with u");
+        }
+    }
     // Born mode: q and dm without acc; q with neither acc nor dm stays an incomplete image mode
-    const bool born = dm != nullptr;
+    const bool born = dm != nullptr && !scatter;
     W3D_REQUIRE(!born || q, "Born mode needs q beside dm");
     W3D_REQUIRE(!born || (!lap_out && !acc), "Born mode (q, dm) cannot be combined with save or image mode");
-    const bool save = lap_out != nullptr, image = !born && (q || acc);
+    const bool save = lap_out != nullptr && !scatter, image = !born && (q || acc);
     W3D_REQUIRE(!image || (q && acc), "image mode needs both q and acc");
     W3D_REQUIRE(!(save && image), "save mode (lap_out) and image mode (q, acc) cannot be combined");
     W3D_REQUIRE(!(save || image || born) || !first, "save / image / Born modes: not on the Taylor start (first)");
@@ -794,10 +893,9 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                 "save / image / Born modes are instantiated for the default variant only (nt, 4 rows per lane)");
     if (born) {
         // q and dm are read while u is written (own plane and wrap planes): no shared memory
-        const i64 span = i64(gv.X + 2 * gv.G - 1) * gv.si + i64(gv.Y + 2 * gv.G - 1) * gv.sj + gv.Z + 2 * gv.G;
         W3D_REQUIRE(!overlaps<T>(u, q, span) && !overlaps<T>(u, dm, span), "Born mode: q or dm shares memory with u");
     }
-    const int mode = save ? kSave : image ? kImage : born ? kBorn : kPlain;
+    const int mode = scatter ? kScatter : born_add ? kBornAdd : save ? kSave : image ? kImage : born ? kBorn : kPlain;
     // reflecting faces of k_march_mh: (j_lo, j_hi, k_lo, k_hi), +-2^29 where there is none
     int mir[4] = {kNoMirror, -kNoMirror, kNoMirror, -kNoMirror};
     bool has[4] = {false, false, false, false};
@@ -834,7 +932,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     p.gy = gy;
     p.gz = gz;
     p.lap_out = lap_out;
-    p.q = q;
+    p.q = born_add ? sadd : scatter ? db : q;
     p.acc = acc;
     p.dm = dm;
     for (int q = 0; q < nbox; ++q) {
@@ -899,7 +997,8 @@ void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int
     template void launch_step_medium<T>(bool, const T*, const T*, const T*, T*, const GridView&,       \
                                         const Box*, int, int, int, const Wrap&, const double[3], u64*, \
                                         int, hipStream_t, int, const T*, const T*, const T*, T*,       \
-                                        const T*, T*, int, const int*, const T*, const T*);            \
+                                        const T*, T*, int, const int*, const T*, const T*, const T*,   \
+                                        const T*);                                                      \
     template void launch_inject<T>(T*, const T*, const GridView&, const int*, const T*, int,           \
                                    const Wrap&, hipStream_t);                                          \
     template void launch_record<T>(const T*, const GridView&, const int*, T*, int, hipStream_t);

@@ -59,6 +59,20 @@ namespace wave3d {
 // D_b u1 = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2, every operation rounded on its own, the
 // divisions correctly rounded (ops/reference.py laplace_density). Save mode stores D_b u1. b is read
 // at the box nodes and their six neighbours, never written. Per node in fp64: 40 B (20 B in fp32).
+//
+// Born modelling with a density perturbation: two more modes of k_march_mb (b non-null, so order 2 and
+// variant 1; leapfrog steps only; every other combination is rejected before the launch).
+// Scatter mode (db non-null, with lap_out = s_out and dm; q and acc null): the background step that
+// also stores the whole scattering term. db is the buoyancy perturbation, a level like b (x ghost
+// planes filled), read at the box nodes and their six neighbours; r = D_db u1 is formed by D_b's
+// operations with db's values in b's place, and s_out = dm D_b u1 + m r at the box nodes, both products
+// rounded, then the add. u and err are those of the plain step bit for bit; s_out must not share
+// memory with u, u1, u2, m, b, dm or db. Per node in fp64: 64 B.
+// Born-add mode (sadd non-null; lap_out, q, acc, dm and db null): the step of the perturbation field
+// with the scattering term read back, u = ((2 u1 - u2) + m D_b u1) + s, with the sponge
+// u = G (((2 u1 - G u2) + m D_b u1) + s); s is read once at the box nodes with the strides of u and
+// must not share memory with it. The wrap, err[0] and the non-finite flag are those of the updated
+// values, as in Born mode. Per node in fp64: 48 B.
 constexpr int kNoMirror = -(1 << 29);
 template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
@@ -66,7 +80,8 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant = -1,
                         const T* gx = nullptr, const T* gy = nullptr, const T* gz = nullptr,
                         T* lap_out = nullptr, const T* q = nullptr, T* acc = nullptr, int order = 2,
-                        const int* mirror = nullptr, const T* b = nullptr, const T* dm = nullptr);
+                        const int* mirror = nullptr, const T* b = nullptr, const T* dm = nullptr,
+                        const T* db = nullptr, const T* sadd = nullptr);
 
 // Central second-derivative weight c_d of the star stencil of `order` (2, 4, 8), d = 0 .. order / 2:
 // the double quotient of its two integers (order 4: -5/2, 4/3, -1/12; order 8: -205/72, 8/5, -1/5,

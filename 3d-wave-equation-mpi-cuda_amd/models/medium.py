@@ -558,21 +558,29 @@ class MediumSolver:
 
     # ---- Born (linearised) modelling and Gauss-Newton products -------------------------------
 
-    def born(self, dspeed2=None, dwavelet=None) -> "MediumBorn":
+    def born(self, dspeed2=None, dwavelet=None, ddensity=None) -> "MediumBorn":
         """Born (linearised) modelling, the Jacobian that :meth:`gradient` transposes: the change of the
         traces, to first order, for a perturbation ``dspeed2`` of ``speed2`` (a scalar or ``(N+1)^3``,
-        finite, periodic in x, of any sign; the density stays fixed) and ``dwavelet``
-        ``[timesteps, len(sources)]`` of the wavelet. At least one of the two.
+        finite, periodic in x, of any sign; the density stays fixed), ``dwavelet``
+        ``[timesteps, len(sources)]`` of the wavelet and ``ddensity`` of the density (like ``dspeed2``, at
+        fixed ``speed2``; needs ``problem.density``, a scalar is fine). At least one of the three.
 
         The background field and the perturbation field ``du`` run in lock step from rest
         (``ops.reference.born_medium`` has the recurrence): ``dtraces[n, r] = du^n[x_r]``, row 0 is 0.
         For any ``r`` of the traces' shape, ``(dtraces[1:] * r[1:]).sum()`` equals
         ``(grad_speed2[:N] * dspeed2[:N]).sum() + (grad_wavelet * dwavelet).sum()`` of
-        ``gradient(traces - r)`` up to rounding.
+        ``gradient(traces - r)`` up to rounding. ``ddensity`` is honoured on the Dirichlet wall nodes too
+        (their buoyancy enters the adjacent half-face averages), so ``dtraces`` is the true directional
+        derivative; ``grad_density`` holds the wall densities fixed, so for a ``ddensity`` that vanishes
+        on the y/z faces the identity gains ``(grad_density[:N] * ddensity[:N]).sum()`` of
+        ``gradient(traces - r, wrt_density=True)``.
 
         "hip": nine levels (the rings of u and du, m, dm and one q level; ten with a density), checked
         against the free device memory. Per step the background step runs in save mode into q and
-        the step of du reads it back in Born mode (``ops.kernels.step_medium``)."""
+        the step of du reads it back in Born mode (``ops.kernels.step_medium``). With ``ddensity``:
+        eleven levels (one more, the buoyancy perturbation), the background step runs in scatter mode
+        and stores the whole scattering term ``s = dm q + m D_db u`` where q went, and the step of du
+        adds it in Born-add mode. Without ``ddensity`` nothing changes: the same kernels, levels and bits."""
         from ..ops import reference
 
         p = self.problem
@@ -581,9 +589,13 @@ class MediumSolver:
             raise ValueError("born() starts from rest: u0 is not supported")
         if not self.receivers:
             raise ValueError("born() needs at least one receiver")
-        if dspeed2 is None and dwavelet is None:
-            raise ValueError("born() needs a perturbation: dspeed2, dwavelet or both")
+        if dspeed2 is None and dwavelet is None and ddensity is None:
+            raise ValueError("born() needs a perturbation: dspeed2, dwavelet, ddensity or any of them together")
+        if ddensity is not None and p.density is None:
+            raise ValueError("born(ddensity=...) needs a density model: build the MediumProblem with "
+                             "density=... (a scalar such as 1.0 is fine)")
         ds = None if dspeed2 is None else reference.perturbation_field(dspeed2, N, "dspeed2")
+        dr = None if ddensity is None else reference.perturbation_field(ddensity, N, "ddensity")
         dw = None
         if dwavelet is not None:
             if not self.sources:
@@ -594,9 +606,9 @@ class MediumSolver:
                                  f"not {tuple(dw.shape)}")
             if not bool(torch.isfinite(dw).all()):
                 raise ValueError("dwavelet must be finite")
-        return self._born_cpu(ds, dw) if self.backend == "cpu" else self._born_hip(ds, dw)
+        return self._born_cpu(ds, dw, dr) if self.backend == "cpu" else self._born_hip(ds, dw, dr)
 
-    def _born_cpu(self, ds, dw) -> "MediumBorn":
+    def _born_cpu(self, ds, dw, dr=None) -> "MediumBorn":
         import time
 
         from ..ops import reference
@@ -606,12 +618,13 @@ class MediumSolver:
         tr, dtr, duf, mx = reference.born_medium(p.N, p.timesteps, p.speed2, ds, dw, sources=self.sources,
                                                  wavelet=self.wavelet, receivers=self.receivers, taper=self.taper,
                                                  L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
-                                                 order=p.space_order, density=p.density)
+                                                 order=p.space_order, density=p.density, ddensity=dr)
         return MediumBorn(traces=tr, dtraces=dtr, du_final=duf, max_abs_du=mx,
                           total_ms=(time.perf_counter() - t0) * 1e3,
-                          extra=dict(levels=None, space_order=p.space_order, density=p.density is not None))
+                          extra=dict(levels=None, space_order=p.space_order, density=p.density is not None,
+                                     ddensity=dr is not None))
 
-    def _born_hip(self, ds, dw) -> "MediumBorn":
+    def _born_hip(self, ds, dw, dr=None) -> "MediumBorn":
         import time
 
         from ..ops import kernels, reference
@@ -621,16 +634,23 @@ class MediumSolver:
         s = _HipSetup(self)
         dev, c, M, box, wrap, h2, level = s.dev, s.c, s.M, s.box, s.wrap, s.h2, s.level
         with torch.cuda.device(dev):
-            nlev = born_levels(density=p.density is not None)
+            nlev = born_levels(density=p.density is not None, ddensity=dr is not None)
             s.require_levels(nlev, "born(): the schedule")
             t0 = time.perf_counter()
             lv = [level() for _ in range(3)]
             dl = [level() for _ in range(3)]
-            m, dm, q = level(), level(), level()
+            m, dm, q = level(), level(), level()  # with ddensity, q holds s = dm q + m D_db u instead
+            db = None if dr is None else level()
             s.medium(m, lv[0], dwavelet=dw)
             step_kw, taper, g, dg, src, rec = s.step_kw, s.taper, s.g, s.dg, s.src, s.rec
             if ds is not None:  # None: dm = 0, the scattering term adds zeros
                 dm.copy_(reference.medium_coefficient(ds, c["tau"], N, dt, M, p.density))
+            if dr is not None:  # born_medium's dm and db
+                dmr = reference.medium_coefficient(p.speed2, c["tau"], N, dt, M, dr)
+                if ds is not None:
+                    dmr = reference.medium_coefficient(ds, c["tau"], N, dt, M, p.density) + dmr
+                dm.copy_(dmr)
+                db.copy_(reference.dbuoyancy_field(dr, p.density, N, dt, M))
             traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
             dtraces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
@@ -642,13 +662,20 @@ class MediumSolver:
                 u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
                 d1, d2, d = dl[(n + 2) % 3], dl[(n + 1) % 3], dl[n % 3]
                 first = n == 1
-                # the background step, saving q = lap u^{n-1} (save mode: the default variant)
+                # the background step, saving q = lap u^{n-1} (save mode: the default variant), or with
+                # ddensity the scattering term s (scatter mode); the step of du reads it back
+                if first:
+                    save, read = {}, {}
+                elif db is None:
+                    save, read = dict(lap_out=q), dict(born=(q, dm))
+                else:
+                    save, read = dict(scatter=(q, dm, db)), dict(born_add=q)
                 kernels.step_medium(u1, u2, m, u, box, first=first, stat=stat[3 * n:3 * n + 3],
-                                    variant=self.variant if first else None, lap_out=None if first else q, **common)
+                                    variant=self.variant if first else None, **save, **common)
                 kernels.inject(u, m, src, g[n - 1], wrap)
-                # the step of du with the scattering term dm q, then the perturbed source terms
+                # the step of du with the scattering term, then the perturbed source terms
                 kernels.step_medium(d1, d2, m, d, box, first=first, stat=dstat[3 * n:3 * n + 3],
-                                    variant=self.variant if first else None, born=None if first else (q, dm), **common)
+                                    variant=self.variant if first else None, **read, **common)
                 kernels.inject(d, dm, src, g[n - 1], wrap)
                 if dg is not None:
                     kernels.inject(d, m, src, dg[n - 1], wrap)
@@ -665,16 +692,23 @@ class MediumSolver:
             return MediumBorn(traces=tr, dtraces=dtr, du_final=duf, max_abs_du=mx,
                               total_ms=(time.perf_counter() - t0) * 1e3,
                               extra=dict(levels=nlev, space_order=p.space_order, density=p.density is not None,
-                                         loop_ms=ev0.elapsed_time(ev1)))
+                                         ddensity=dr is not None, loop_ms=ev0.elapsed_time(ev1)))
 
-    def gauss_newton(self, dspeed2=None, dwavelet=None, *, segment: int | None = None) -> "MediumGradient":
+    def gauss_newton(self, dspeed2=None, dwavelet=None, ddensity=None, *, segment: int | None = None,
+                     wrt_density: bool | None = None) -> "MediumGradient":
         """The Gauss-Newton Hessian applied to a perturbation: one :meth:`born` run, then
         :meth:`gradient` with ``observed = traces - dtraces``, so that the residuals are ``dtraces`` and
         ``grad_speed2``, ``grad_wavelet`` are ``J^T J [dspeed2; dwavelet]`` (``misfit`` is
         ``1/2 |dtraces[1:]|^2``). ``segment``: the checkpoint schedule of :meth:`gradient`. ``extra``
-        also carries the Born run's ``dtraces``. Both backends form ``observed`` on the host alike."""
-        b = self.born(dspeed2, dwavelet)
-        r = self.gradient(b.traces - b.dtraces, segment=segment)
+        also carries the Born run's ``dtraces``. Both backends form ``observed`` on the host alike.
+
+        ``ddensity``: the density block of the perturbation (:meth:`born`). ``wrt_density`` (default:
+        whether ``ddensity`` is given) also returns ``grad_density``, the density row of
+        ``J^T J [dspeed2; dwavelet; ddensity]``, with the wall convention of :meth:`gradient`."""
+        b = self.born(dspeed2, dwavelet, ddensity)
+        if wrt_density is None:
+            wrt_density = ddensity is not None
+        r = self.gradient(b.traces - b.dtraces, segment=segment, wrt_density=wrt_density)
         r.extra["dtraces"] = b.dtraces
         r.extra["born_ms"] = b.total_ms
         return r
@@ -773,11 +807,12 @@ class MediumBorn:
     extra: dict = field(default_factory=dict)  # levels; "hip" also loop_ms, the device time of the time loop
 
 
-def born_levels(density: bool = False) -> int:
+def born_levels(density: bool = False, ddensity: bool = False) -> int:
     """Number of grid levels the "hip" schedule of :meth:`MediumSolver.born` holds: the rings of the
     background and the perturbation field (3 each), m, dm and one q level; ``density``: one more, the
-    buoyancy."""
-    return 9 + bool(density)
+    buoyancy; ``ddensity`` (a density perturbation, which needs a density model): 11, the buoyancy and
+    its perturbation, the scattering term taking q's place."""
+    return 11 if ddensity else 9 + bool(density)
 
 
 @dataclass

@@ -355,7 +355,7 @@ def _check_taper(taper, u) -> list[int]:
 
 def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None, chunk: int = 0,
                 variant: str | None = None, taper=None, lap_out=None, image=None, order: int = 2,
-                mirror=None, buoyancy=None, born=None) -> None:
+                mirror=None, buoyancy=None, born=None, scatter=None, born_add=None) -> None:
     """One layer of ``u_tt = c^2 (lap u + f)`` over ``boxes``: ``u = (2 u1 - u2) + m lap(u1)``, on
     the Taylor start (``first``) ``u = u1 + (0.5 m) lap(u1)``, with ``m = c^2 tau^2`` per node.
 
@@ -404,6 +404,19 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     matches ``u`` in shape, dtype, device and strides, its ghost planes filled like those of ``u1``;
     it is read at the box nodes and their six neighbours and never written. For ``order`` 2 and the
     default variant only (``ValueError`` before any launch otherwise).
+
+    Two more modes of the density step serve Born modelling with a density perturbation; both need
+    ``buoyancy`` (so order 2 and the default variant), exist for leapfrog steps only and cannot be
+    combined with each other or with ``lap_out``, ``image`` or ``born``. ``scatter = (s_out, dm,
+    dbuoyancy)``: the background step, ``u`` and ``stat`` those of the plain step bit for bit, that also
+    stores the scattering term ``s_out = dm D_b u1 + m D_db u1`` at the box nodes (both products rounded,
+    then the add), ``D_db`` being ``D_b``'s operations with the buoyancy perturbation ``dbuoyancy`` in
+    b's place: a grid like ``buoyancy``, read at the box nodes and their six neighbours. ``s_out`` must
+    not share memory with any other grid of the call. ``born_add = s``: the step of the perturbation
+    field that adds it, ``u = ((2 u1 - u2) + m D_b u1) + s``, with the sponge
+    ``u = G (((2 u1 - G u2) + m D_b u1) + s)``; ``s`` is read at the box nodes and must not share memory
+    with ``u``; the wrap and ``stat`` are those of the updated values. All these grids match ``u`` in
+    shape, dtype, device and strides.
     """
     if order not in (2, 4, 8):
         raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
@@ -418,6 +431,24 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
         if not isinstance(buoyancy, torch.Tensor):
             raise ValueError("buoyancy must be a tensor")
         variant = "nt"
+    if scatter is not None or born_add is not None:
+        if scatter is not None and born_add is not None:
+            raise ValueError("scatter mode (scatter) and Born-add mode (born_add) cannot be combined")
+        if lap_out is not None or image is not None or born is not None:
+            raise ValueError("scatter / Born-add modes cannot be combined with save mode (lap_out), image mode "
+                             "(image) or Born mode (born)")
+        if buoyancy is None:
+            raise ValueError("scatter / Born-add modes need a buoyancy (variable density)")
+        if first:
+            raise ValueError("scatter / Born-add modes: not on the Taylor start (first=True)")
+        if scatter is not None:
+            if len(scatter) != 3:
+                raise ValueError("scatter = (s_out, dm, dbuoyancy)")
+            extra = list(scatter)
+        else:
+            extra = [born_add]
+        if not all(isinstance(t, torch.Tensor) for t in extra):
+            raise ValueError("s_out, dm, dbuoyancy and s must be tensors")
     if born is not None:
         if lap_out is not None or image is not None:
             raise ValueError("Born mode (born) cannot be combined with save mode (lap_out) or image mode (image)")
@@ -458,6 +489,18 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
             t0, t1 = _grid_span(t)
             if u_0 < t1 and t0 < u_1:
                 raise ValueError(f"Born mode: {name} shares memory with u")
+    if scatter is not None:
+        s_0, s_1 = _grid_span(scatter[0])
+        for t, name in zip((u, u1, u2, m, buoyancy, scatter[1], scatter[2]),
+                           ("u", "u1", "u2", "m", "buoyancy", "dm", "dbuoyancy")):
+            t0, t1 = _grid_span(t)
+            if s_0 < t1 and t0 < s_1:
+                raise ValueError(f"scatter mode: s_out shares memory with {name}")
+    if born_add is not None:
+        u_0, u_1 = _grid_span(u)
+        t0, t1 = _grid_span(born_add)
+        if u_0 < t1 and t0 < u_1:
+            raise ValueError("Born-add mode: s shares memory with u")
     if isinstance(boxes[0], int):
         boxes = [boxes]
     if not 1 <= len(boxes) <= 7:
@@ -481,11 +524,14 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     fn = getattr(_C(), "k_step_medium_" + _sfx(u))
     fn(bool(first), u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, bl, int(stat_i[0]),
        int(stat_i[1]), w, [float(v) for v in h2], stat.data_ptr(), int(chunk), _stream(),
-       _MEDIUM_VARIANTS[variant], *gp, lap_out.data_ptr() if lap_out is not None else 0,
+       _MEDIUM_VARIANTS[variant], *gp,
+       lap_out.data_ptr() if lap_out is not None else scatter[0].data_ptr() if scatter is not None else 0,
        *((image[0].data_ptr(), image[1].data_ptr()) if image is not None
          else (born[0].data_ptr(), 0) if born is not None else (0, 0)), int(order), mir,
        buoyancy.data_ptr() if buoyancy is not None else 0,
-       born[1].data_ptr() if born is not None else 0)
+       born[1].data_ptr() if born is not None else scatter[1].data_ptr() if scatter is not None else 0,
+       scatter[2].data_ptr() if scatter is not None else 0,
+       born_add.data_ptr() if born_add is not None else 0)
 
 
 def _grid_span(t: torch.Tensor) -> tuple[int, int]:

@@ -341,7 +341,7 @@ def _lap_box(u1, box, hx2, hy2, hz2, order: int, mirror, buoyancy=None):
 
 
 def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None, order: int = 2,
-                mirror=None, buoyancy=None, born=None) -> torch.Tensor:
+                mirror=None, buoyancy=None, born=None, born_add=None) -> torch.Tensor:
     """Layer update on ``box`` with the per-node coefficient ``m = c^2 tau^2``: the Taylor start
     ``c + (0.5 m) lap`` or ``(2c - u2) + m lap``; returns the updated box values.
 
@@ -358,11 +358,24 @@ def step_medium(u1, u2, m, box, *, first: bool, hx2, hy2, hz2, taper=None, order
     born = (q_box, dm): the step of Born (linearised) modelling on a perturbation field, leapfrog
     steps only: ``((2c - u2) + m lap) + dm q`` or ``G (((2c - G u2) + m lap) + dm q)``, the product
     rounded before its add. ``q_box`` = the Laplacian of the background field on the box, as
-    ``_lap_box`` returns it; ``dm`` = the perturbation of m, a grid like m."""
+    ``_lap_box`` returns it; ``dm`` = the perturbation of m, a grid like m.
+
+    born_add = s_box: the same step with the scattering term already formed, on the box (leapfrog steps
+    only, not together with ``born``): ``((2c - u2) + m lap) + s`` or ``G (((2c - G u2) + m lap) + s)``.
+    Born modelling with a density perturbation uses it (``born_medium``): there s has two terms."""
     if order not in STAR_WEIGHTS:
         raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
     i0, i1, j0, j1, k0, k1 = box
     sc = None
+    if born_add is not None:
+        if born is not None:
+            raise ValueError("born_add cannot be combined with born")
+        if first:
+            raise ValueError("Born-add mode: not on the Taylor start (first=True)")
+        want = (i1 - i0 + 1, j1 - j0 + 1, k1 - k0 + 1)
+        if tuple(born_add.shape) != want:
+            raise ValueError(f"born_add must have the box's shape {want}, not {tuple(born_add.shape)}")
+        sc = born_add
     if born is not None:
         if first:
             raise ValueError("Born mode: not on the Taylor start (first=True)")
@@ -436,6 +449,18 @@ def buoyancy_field(density, N: int, dtype, ghost: int = 1) -> torch.Tensor:
     b[ghost:N + 1 + ghost] = (1.0 / r).to(dtype)
     _wrap_x(b, N, ghost)
     return b
+
+
+def dbuoyancy_field(ddensity, density, N: int, dtype, ghost: int = 1) -> torch.Tensor:
+    """The first-order change of the buoyancy for a perturbation ``ddensity`` of ``density`` (each a
+    scalar or ``(N+1)^3``): db = -(drho / (rho rho)) in float64, then cast; stored like
+    ``buoyancy_field`` with the x ghost planes filled periodically."""
+    r = _node_field(density, N, "density")
+    d = _node_field(ddensity, N, "ddensity")
+    db = torch.zeros(N + 1 + 2 * ghost, N + 1, N + 1, dtype=dtype)
+    db[ghost:N + 1 + ghost] = (-(d / (r * r))).to(dtype)
+    _wrap_x(db, N, ghost)
+    return db
 
 
 def _buoyancy(density, N: int, dtype, order: int, ghost: int):
@@ -864,6 +889,18 @@ def gradient_medium_density(N: int, K: int, speed2, observed, *, sources=(), wav
 # du^n[x_r] is the directional derivative of the traces, and for any r [K+1, R]
 #   (dtraces[1:] * r[1:]).sum() == (grad_speed2[:N] * ds[:N]).sum() + (grad_wavelet * dw).sum()
 # with the gradients of gradient_medium(observed = traces - r), in exact arithmetic.
+#
+# A perturbation drho of the density at fixed speed2 changes the step in two places: m = rho c^2 tau^2 by
+# dm_rho = medium_coefficient(speed2, density=drho) (added to the dm above in the working dtype; one
+# term alone is used as it is), and the buoyancy b = 1 / rho by db = -drho / rho^2 (dbuoyancy_field).
+# D_b is linear in b, so with r^{n-1} = D_db u^{n-1} (laplace_density with db in b's place) the
+# scattering term becomes s^{n-1} = dm q^{n-1} + m r^{n-1}, both products rounded, then the add, and
+#   du^n = G (((2 du^{n-1} - G du^{n-2}) + m D_b du^{n-1}) + s^{n-1}) + dm g[n-1] e_s + m dg[n-1] e_s
+# (step_medium's ``born_add``); du^1 has no db term, u^0 being 0. The wall nodes' db enters the
+# adjacent half-face averages exactly as their b does, so dtraces is the true directional derivative
+# for any drho. gradient_medium_density holds the wall densities fixed and reports 0 there, so the
+# adjoint identity gains the term (grad_density[:N] * drho[:N]).sum() for drho that vanishes on the
+# y/z faces.
 
 def perturbation_field(v, N: int, name: str) -> torch.Tensor:
     """A model perturbation as a float64 CPU tensor: a scalar or ``(N+1)^3``, finite, of any sign,
@@ -885,19 +922,24 @@ def perturbation_field(v, N: int, name: str) -> torch.Tensor:
 
 def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=(), wavelet=None, receivers=(),
                 taper=None, L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
-                order: int = 2, density=None):
+                order: int = 2, density=None, ddensity=None):
     """Born modelling from rest: ``solve_medium``'s run and, in lock step, the first-order change of
     its field for the perturbations ``dspeed2`` of speed2 (a scalar or ``(N+1)^3``, finite, periodic
-    in x, of any sign; the density stays fixed) and ``dwavelet`` ``[K, S]`` of the wavelet; at least
-    one of the two. Returns (traces ``[K+1, R]``, those of ``solve_medium`` bit for bit; dtraces
+    in x, of any sign; the density stays fixed), ``dwavelet`` ``[K, S]`` of the wavelet and ``ddensity``
+    of the density (like ``dspeed2``, at fixed speed2, wall nodes included; needs ``density``); at
+    least one of the three. Returns (traces ``[K+1, R]``, those of ``solve_medium`` bit for bit; dtraces
     ``[K+1, R]``, row 0 zero; du^K ``(N+1)^3``; max |du| per layer ``[K+1]`` like ``solve_medium``'s).
 
     Per step: the background step, the Born step ``step_medium(born=(q, dm))`` with q the Laplacian
     of the background level it started from, then per source node ``du += dm g[n-1, s]`` and
     ``du += m dg[n-1, s]`` (each a rounded product, then the add), the wrap, the sample. Step 1 has
-    no Born term."""
-    if dspeed2 is None and dwavelet is None:
-        raise ValueError("born_medium needs a perturbation: dspeed2, dwavelet or both")
+    no Born term. With ``ddensity`` the Born step is ``step_medium(born_add=s)`` with
+    ``s = dm q + m r``, r = ``laplace_density`` of the same background level with the buoyancy
+    perturbation in b's place; without it every operation is the one above."""
+    if dspeed2 is None and dwavelet is None and ddensity is None:
+        raise ValueError("born_medium needs a perturbation: dspeed2, dwavelet, ddensity or any of them together")
+    if ddensity is not None and density is None:
+        raise ValueError("ddensity needs a density model: density=... (a scalar such as 1.0 is fine)")
     c = tables(N, K, L, T, pi)[4]
     M, box, mirror = _medium_layout(N, order)
     tt = None if taper is None else taper_tables(taper, N, dtype, M)
@@ -907,6 +949,12 @@ def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=
     else:
         dm = medium_coefficient(perturbation_field(dspeed2, N, "dspeed2"), c["tau"], N, dtype, M, density)
     bu = _buoyancy(density, N, dtype, order, M)
+    db = None
+    if ddensity is not None:
+        dr = perturbation_field(ddensity, N, "ddensity")
+        dmr = medium_coefficient(speed2, c["tau"], N, dtype, M, dr)
+        dm = dmr if dspeed2 is None else dm + dmr
+        db = dbuoyancy_field(dr, density, N, dtype, M)
     ent = source_entries(sources, N, M)
     S = len(sources)
     g = source_table(wavelet, K, S, c["hx"], c["hy"], c["hz"], dtype)
@@ -934,7 +982,11 @@ def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=
         for nd, s in ent:
             u[nd] = u[nd] + m[nd] * g[n - 1, s]
         _wrap_x(u, N, M)
-        dvals = step_medium(d1, d2, m, box, first=n == 1, born=None if n == 1 else (q, dm), **kw)
+        if db is None or n == 1:
+            dvals = step_medium(d1, d2, m, box, first=n == 1, born=None if n == 1 else (q, dm), **kw)
+        else:  # q and r of the level u1 the background step above started from
+            r = _lap_box(u1, box, c["hx2"], c["hy2"], c["hz2"], order, mirror, db)
+            dvals = step_medium(d1, d2, m, box, first=False, born_add=dm[own] * q + m[own] * r, **kw)
         mx.append(max_abs_field(dvals))
         d.zero_()
         d[own] = dvals

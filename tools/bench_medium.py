@@ -9,6 +9,7 @@
     python tools/bench_medium.py --gradient --density --wrt-density [--N 512] [--steps 100] [--segment 10]
     python tools/bench_medium.py --born [--N 512] [--steps 100] [--dtypes fp64,fp32] [--order 2,4,8]
                                  [--kernels-only] [--density]
+    python tools/bench_medium.py --born --density --ddensity [--N 512] [--steps 100] [--kernels-only]
 
 For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
 and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
@@ -57,6 +58,14 @@ gradient() of the two-layer density problem with and without `wrt_density`, with
 (segment = steps) and with `--segment`, the four alternating inside each repeat: the device time of
 the two passes, the wall time, the levels held and their size. A schedule that does not fit the free
 device memory is reported as such.
+
+`--born --density --ddensity` measures Born modelling with a density perturbation (order 2), per dtype in
+one process, three arms alternating inside each round: the scatter step (u1, u2, m, b, db, dm read, u and
+s written: 64 B per node in fp64) and the Born-add step (u1, u2, m, b, s read, u written: 48 B); the save
+step (48 B) and the Born step (56 B) of the same density problem; the plain density step k_march_mb
+(40 B), the yardstick, with and without the sponge. Then, alternating as well, the time loops of
+born(ddensity=...), born(dspeed2=...) and run() of the two-layer density problem. `--kernels-only` skips
+the loops.
 """
 import argparse
 import json
@@ -197,6 +206,111 @@ def density_gradient_bench(a) -> int:
             if wd and base and base[0]["fits"]:
                 row["passes_vs_without"] = round(row["passes_ms"] / base[0]["passes_ms"], 3)
             out["gradient"].append(row)
+        del sol
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+    return 0
+
+
+def born_density_bench(a) -> int:
+    import math
+
+    import torch
+
+    import wave3d
+    from wave3d.ops import kernels, reference
+
+    N, K = a.N, a.steps
+    h = 3.1415926535 / N
+    hi = (0.9 * wave3d.cfl_limit(2) * h * K) ** 2 / 1.5
+    speed2 = smooth_speed2(N, 0.5 * hi, hi)
+    rho = two_layer_density(N)
+    drho = 0.01 * smooth_speed2(N, -1.0, 1.0, seed=11)
+    nodes = float(N + 1) ** 3
+    out = {"N": N, "steps": K, "device": torch.cuda.get_device_name(0), "density": "two layers: 1, 2",
+           "kernels": [], "born": []}
+    dev = torch.device("cuda", 0)
+    for dtype in a.dtypes.split(","):
+        es = 8 if dtype == "fp64" else 4
+        prob = wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype, density=rho)
+        dt = prob.torch_dtype
+        c = reference.tables(N, K)[4]
+        h2 = (c["hx2"], c["hy2"], c["hz2"])
+        box, wrap = (1, N + 1, 1, N - 1, 1, N - 1), [N, 0, 2, N + 2]
+        sponge = wave3d.sponge_taper(prob, 16)
+        taper = tuple(t.to(dev) for t in reference.taper_tables(sponge, N, dt))
+
+        # the kernels on one set of levels (smooth values, nothing denormal)
+        g = torch.Generator().manual_seed(1)
+        seed = torch.rand(N + 1, N + 1, generator=g, dtype=torch.float64).to(dt).to(dev)
+        u1, u2, m, u, x, q, dm, bu, db = (kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(9))
+        m.copy_(reference.medium_coefficient(speed2, c["tau"], N, dt, 1, rho))
+        dm.copy_(reference.medium_coefficient(speed2, c["tau"], N, dt, 1, drho))
+        bu.copy_(reference.buoyancy_field(rho, N, dt))
+        db.copy_(reference.dbuoyancy_field(drho, rho, N, dt))
+        for t in (u1, u2, q):
+            t[:, 1:N, 1:N] = seed[1:N, 1:N]
+        stat = kernels.new_err(1, device=dev)
+        # (bytes per node / element size, keywords); the three arms in the order they alternate
+        arms = {"scatter": (8, dict(scatter=(x, dm, db))), "born_add": (6, dict(born_add=q)),
+                "save": (6, dict(lap_out=x)), "born": (7, dict(born=(q, dm))), "plain": (5, {})}
+        reps = 20
+        for tp_name in ("", "sponge"):
+            ms = {k: [] for k in arms}
+            for rnd in range(a.repeat + 1):  # round 0 warms up
+                for name, (_, kw) in arms.items():  # the arms alternate inside each round
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(reps):
+                        kernels.step_medium(u1, u2, m, u, box, first=False, h2=h2, stat=stat, stat_i=(1, N + 1),
+                                            wrap=wrap, buoyancy=bu, taper=taper if tp_name else None, **kw)
+                    e1.record()
+                    e1.synchronize()
+                    if rnd:
+                        ms[name].append(e0.elapsed_time(e1) / reps)
+            for name, (bpn, _) in arms.items():
+                best = min(ms[name])
+                out["kernels"].append({"dtype": dtype, "mode": name, "sponge": bool(tp_name),
+                                       "ms_per_step": round(best, 4), "all_ms": [round(v, 4) for v in ms[name]],
+                                       "bytes_per_node": bpn * es, "expected_ratio": bpn / 5,
+                                       "ratio_to_plain": round(best / min(ms["plain"]), 4),
+                                       "eff_tb_per_s": round(bpn * es * nodes / (best * 1e-3) / 1e12, 3)})
+                print(f"bench_medium: {dtype} {name} {tp_name}: {best:.4f} ms/step", file=sys.stderr, flush=True)
+        del u1, u2, m, u, x, q, dm, bu, db, arms, taper
+        torch.cuda.empty_cache()
+        if a.kernels_only:
+            continue
+
+        w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
+        mid = N // 2
+        sol = wave3d.MediumSolver(prob, "hip", sources=[(mid, mid, mid)], wavelet=w,
+                                  receivers=[(mid - K // 5, mid, mid), (mid, mid - K // 4, mid + 3)], taper=sponge)
+        ds = 0.01 * speed2
+        loops = {"born_ddensity": lambda: sol.born(ddensity=drho), "born": lambda: sol.born(ds),
+                 "run": lambda: sol.run()}
+        rows = {n: [] for n in loops}
+        for rnd in range(a.repeat + 1):  # round 0 warms up
+            for name, fn in loops.items():
+                r = fn()
+                if name == "run":
+                    ms_loop = r.total_ms
+                else:
+                    assert math.isfinite(float(r.dtraces.abs().max())) and float(r.dtraces.abs().max()) > 0
+                    ms_loop = r.extra["loop_ms"]
+                del r
+                if rnd:
+                    rows[name].append(round(ms_loop, 2))
+                print(f"bench_medium: {dtype} {name}: {ms_loop:.2f} ms", file=sys.stderr, flush=True)
+                torch.cuda.empty_cache()
+        best = {n: min(v) for n, v in rows.items()}
+        out["born"].append({"dtype": dtype, "run_loop_ms": best["run"], "born_loop_ms": best["born"],
+                            "born_ddensity_loop_ms": best["born_ddensity"],
+                            "born_vs_run": round(best["born"] / best["run"], 3),
+                            "born_ddensity_vs_run": round(best["born_ddensity"] / best["run"], 3),
+                            "born_ddensity_vs_born": round(best["born_ddensity"] / best["born"], 3),
+                            "levels": wave3d.born_levels(density=True),
+                            "levels_ddensity": wave3d.born_levels(density=True, ddensity=True),
+                            "born_ddensity_loop_ms_all": rows["born_ddensity"], "born_loop_ms_all": rows["born"]})
         del sol
         torch.cuda.empty_cache()
     print(json.dumps(out))
@@ -391,6 +505,8 @@ def main(argv=None) -> int:
                     help="also time the variable-density step (two-layer rho), alternating with the constant-density one")
     ap.add_argument("--wrt-density", action="store_true",
                     help="--gradient --density: time k_face_corr and gradient(wrt_density=True) instead")
+    ap.add_argument("--ddensity", action="store_true",
+                    help="--born --density: time the scatter and Born-add steps and born(ddensity=...) instead")
     a = ap.parse_args(argv)
 
     import math
@@ -414,6 +530,10 @@ def main(argv=None) -> int:
         return density_gradient_bench(a)
     if a.born and a.gradient:
         ap.error("--born and --gradient are separate measurements")
+    if a.ddensity:
+        if not (a.born and a.density) or orders != [2]:
+            ap.error("--ddensity goes with --born --density at order 2")
+        return born_density_bench(a)
     if a.gradient or a.born:
         return gradient_bench(a)
     variants = a.variants.split(",")
