@@ -25,7 +25,8 @@ def __getattr__(name):
 
         return getattr(wave, name)
     if name in ("MediumProblem", "MediumSolver", "MediumResult", "MediumGradient", "MediumBorn", "ricker",
-                "sponge_taper", "gradient_levels", "best_gradient_segment", "born_levels", "cfl_limit"):
+                "sponge_taper", "gradient_levels", "best_gradient_segment", "born_levels", "cfl_limit",
+                "precondition"):
         from .models import medium
 
         return getattr(medium, name)

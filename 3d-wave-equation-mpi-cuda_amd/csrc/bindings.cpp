@@ -334,12 +334,14 @@ void k_zero_faces(uintptr_t u, const std::vector<i64>& g, int mask, uintptr_t st
 // dm: the coefficient perturbation of the Born step (with q; lap_out and acc 0), 0 otherwise.
 // db: the buoyancy perturbation of the scatter step (with lap_out = s_out, dm and b); sadd: the
 // scattering term of the Born-add step (with b alone); 0 otherwise.
+// illum: the illumination grid of the illum / save+illum steps (alone or with lap_out), 0 otherwise.
 template <class T>
 void k_step_medium(bool first, uintptr_t u1, uintptr_t u2, uintptr_t m, uintptr_t u, const std::vector<i64>& g,
                    const std::vector<std::vector<int>>& boxes, int ei0, int ei1, const std::vector<int>& wrap,
                    const std::vector<double>& h2, uintptr_t err, int chunk, uintptr_t stream, int variant,
                    uintptr_t gx, uintptr_t gy, uintptr_t gz, uintptr_t lap_out, uintptr_t q, uintptr_t acc, int order,
-                   const std::vector<int>& mirror, uintptr_t b, uintptr_t dm, uintptr_t db, uintptr_t sadd) {
+                   const std::vector<int>& mirror, uintptr_t b, uintptr_t dm, uintptr_t db, uintptr_t sadd,
+                   uintptr_t illum) {
     std::vector<Box> bx;
     for (auto& e : boxes) bx.push_back(tobox(e));
     W3D_REQUIRE(h2.size() == 3, "h2 = (hx2, hy2, hz2)");
@@ -349,7 +351,7 @@ void k_step_medium(bool first, uintptr_t u1, uintptr_t u2, uintptr_t m, uintptr_
     launch_step_medium<T>(first, P<T>(u1), P<T>(u2), P<T>(m), P<T>(u), gview(g), bx.data(), int(bx.size()), ei0,
                           ei1, towrap(wrap), h, P<u64>(err), chunk, (hipStream_t)stream, variant, P<T>(gx), P<T>(gy),
                           P<T>(gz), P<T>(lap_out), P<T>(q), P<T>(acc), order, mirror.empty() ? nullptr : mirror.data(),
-                          P<T>(b), P<T>(dm), P<T>(db), P<T>(sadd));
+                          P<T>(b), P<T>(dm), P<T>(db), P<T>(sadd), P<T>(illum));
 }
 
 // Face correlation (k_face_corr): acc = acc + C(a, v) at the box nodes; grid view as above
@@ -637,7 +639,7 @@ PYBIND11_MODULE(_wave3d_C, m) {
         py::arg("ei0"), py::arg("ei1"), py::arg("wrap"), py::arg("h2"), py::arg("err"), py::arg("chunk"),          \
         py::arg("stream"), py::arg("variant"), py::arg("gx"), py::arg("gy"), py::arg("gz"), py::arg("lap_out"),    \
         py::arg("q"), py::arg("acc"), py::arg("order") = 2, py::arg("mirror") = std::vector<int>{},         \
-        py::arg("b") = 0, py::arg("dm") = 0, py::arg("db") = 0, py::arg("sadd") = 0
+        py::arg("b") = 0, py::arg("dm") = 0, py::arg("db") = 0, py::arg("sadd") = 0, py::arg("illum") = 0
     m.def("k_step_medium_f64", &k_step_medium<double>, W3D_STEP_MEDIUM_ARGS);
     m.def("k_step_medium_f32", &k_step_medium<float>, W3D_STEP_MEDIUM_ARGS);
 #undef W3D_STEP_MEDIUM_ARGS

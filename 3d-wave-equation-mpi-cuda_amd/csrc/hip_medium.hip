@@ -19,7 +19,8 @@
 //    the kernel). It alone has the scatter and Born-add modes of Born modelling with a density
 //    perturbation.
 //  * all three march kernels have the save, image and Born modes of the adjoint-state gradient and
-//    of Born modelling (MarchMode below; hip_medium.hpp has the contract), and are built from the
+//    of Born modelling and the two illumination modes (MarchMode below; hip_medium.hpp has the
+//    contract), and are built from the
 //    tile skeleton of march_tile.hpp and the per-mode pieces below, each written once.
 //  * k_inject / k_record: one thread per source entry / receiver.
 //
@@ -57,6 +58,7 @@ struct MediumParams : TileParams<T> {
     const T* dm;            // kBorn: the coefficient perturbation; u receives + dm * q (q as above)
                             // kScatter (k_march_mb): lap_out receives dm * lap + m * r, r = D_db u1 with the
                             // buoyancy perturbation db, a level like b, in q; kBornAdd: u receives + q
+    T* illum;               // kIllum, kSaveIllum: h = h + lap * lap at the box nodes (strides of u)
 };
 
 // Modes of the march kernels: the plain step; kSave also stores the Laplacian that entered the
@@ -72,21 +74,35 @@ struct MediumParams : TileParams<T> {
 // r = D_db u1 with the buoyancy perturbation db in b's place (a read-once stream dm, a write-once
 // stream lap_out = s, and db handled like b: described at the kernel); kBornAdd is the step of the
 // perturbation field that adds it, u = G (((2 u1 - G u2) + m lap) + s) (one read-once stream, q = s).
-enum MarchMode { kPlain = 0, kSave = 1, kImage = 2, kBorn = 3, kScatter = 4, kBornAdd = 5 };
+// Source illumination (the diagonal of the pseudo-Hessian): kIllum is the plain step, kSaveIllum the
+// save step, that also does h = h + lap * lap at the lane's own nodes, the product rounded before the
+// add: one more read-modify-write stream (h), like image mode's acc without its q.
+enum MarchMode {
+    kPlain = 0,
+    kSave = 1,
+    kImage = 2,
+    kBorn = 3,
+    kScatter = 4,
+    kBornAdd = 5,
+    kIllum = 6,
+    kSaveIllum = 7
+};
+constexpr bool saves_lap(int mode) { return mode == kSave || mode == kSaveIllum; }
+constexpr bool illuminates(int mode) { return mode == kIllum || mode == kSaveIllum; }
 
 constexpr int kNt = 2;  // cache policy of the read-once and write-once streams: non-temporal
 
-// The extra read streams of image mode (q and acc), Born mode (q and dm), scatter mode (dm alone) and
-// Born-add mode (q = s alone), at the lane's own nodes: two-slot register rings prefetched one plane
-// ahead like m; plane x in slot (x - ib) & 1.
+// The extra read streams of image mode (q and acc), Born mode (q and dm), scatter mode (dm alone),
+// Born-add mode (q = s alone) and the illumination modes (h alone, in the `a` ring), at the lane's own
+// nodes: two-slot register rings prefetched one plane ahead like m; plane x in slot (x - ib) & 1.
 template <class T, int R, int MODE>
 struct AuxRings {
     static constexpr bool kQ = MODE == kImage || MODE == kBorn || MODE == kBornAdd;
-    static constexpr bool kA = MODE == kImage || MODE == kBorn || MODE == kScatter;
+    static constexpr bool kA = MODE == kImage || MODE == kBorn || MODE == kScatter || illuminates(MODE);
     T q[kQ ? 2 : 1][kQ ? R : 1], a[kA ? 2 : 1][kA ? R : 1];
 
     static __device__ __forceinline__ const T* second(const MediumParams<T>& p) {
-        return MODE == kImage ? p.acc : p.dm;
+        return MODE == kImage ? p.acc : illuminates(MODE) ? p.illum : p.dm;
     }
     // plane ib into slot 0
     __device__ __forceinline__ void prime(const Tile<T, R>& t, const MediumParams<T>& p, const unsigned (&os)[R]) {
@@ -210,7 +226,7 @@ __device__ __forceinline__ T medium_update(T c, T u2, T lap, T m, T gxi, T gyz, 
 template <class T, int MODE>
 __device__ __forceinline__ T side_value(T c, T lap, T a, T q, T m = T(0)) {
 #pragma clang fp contract(off)
-    if constexpr (MODE == kSave) {
+    if constexpr (saves_lap(MODE)) {
         return lap;
     } else if constexpr (MODE == kImage) {
         const T pr = c * q;
@@ -223,11 +239,24 @@ __device__ __forceinline__ T side_value(T c, T lap, T a, T q, T m = T(0)) {
     }
 }
 
-// stores of plane i: own plane + fused periodic wrap (buffer stores, masked lanes dropped), and
-// the mode's side stream xv (side_value)
+// The new illumination of a node, a + lap lap (a = h), the product rounded before the add; 0, and
+// unused, in the other modes
+template <class T, int MODE>
+__device__ __forceinline__ T illum_value(T lap, T a) {
+#pragma clang fp contract(off)
+    if constexpr (illuminates(MODE)) {
+        const T pr = lap * lap;
+        return a + pr;
+    } else {
+        return T(0);
+    }
+}
+
+// stores of plane i: own plane + fused periodic wrap (buffer stores, masked lanes dropped), the
+// mode's side stream xv (side_value) and the illumination modes' hx (illum_value)
 template <int MODE, class T, int R>
 __device__ __forceinline__ void store_plane(const Tile<T, R>& t, const MediumParams<T>& p, int i, const T (&vv)[R],
-                                            const T (&xv)[R], const unsigned (&os)[R]) {
+                                            const T (&xv)[R], const T (&hx)[R], const unsigned (&os)[R]) {
     const auto rs = t.prs(p.u, i);
 #pragma unroll
     for (int r = 0; r < R; ++r) bst<kNt>(vv[r], rs, os[r]);
@@ -238,10 +267,15 @@ __device__ __forceinline__ void store_plane(const Tile<T, R>& t, const MediumPar
 #pragma unroll
             for (int r = 0; r < R; ++r) bst<kNt>(vv[r], rw, os[r]);
         }
-    if constexpr (MODE == kSave || MODE == kImage || MODE == kScatter) {
+    if constexpr (saves_lap(MODE) || MODE == kImage || MODE == kScatter) {
         const auto rx = t.prs(MODE == kImage ? p.acc : p.lap_out, i);
 #pragma unroll
         for (int r = 0; r < R; ++r) bst<kNt>(xv[r], rx, os[r]);
+    }
+    if constexpr (illuminates(MODE)) {
+        const auto rh = t.prs(p.illum, i);
+#pragma unroll
+        for (int r = 0; r < R; ++r) bst<kNt>(hx[r], rh, os[r]);
     }
 }
 
@@ -334,7 +368,7 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
         __syncthreads();
 
         const T gxi = sponge.next(p, i);
-        T vv[R], xv[R];
+        T vv[R], xv[R], hx[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int lr = 1 + w * R + r;
@@ -347,9 +381,10 @@ __global__ void __launch_bounds__(kThreads) k_march_m(const MediumParams<T> p) {
                 laplace7_cr(c, u1[S0][r], u1[S2][r], jm, jp, km, kp, p.hx2, p.hy2, p.hz2, p.yx2, p.yy2, p.yz2);
             const T a = aux.av(Ph<H0>{}, r), q = aux.qv(Ph<H0>{}, r);
             xv[r] = side_value<T, MODE>(c, lap, a, q);
+            hx[r] = illum_value<T, MODE>(lap, a);
             vv[r] = medium_update<T, FIRST, TAPER, MODE>(c, u2[H0][r], lap, mm[H0][r], gxi, sponge.yz(r), a, q);
         }
-        store_plane<MODE>(t, p, i, vv, xv, os);
+        store_plane<MODE>(t, p, i, vv, xv, hx, os);
         plane_stats(p, i, vv, valid, chk, ma);
     };
     march_planes<4>(ib, t.ie, plane);
@@ -517,7 +552,7 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
         __syncthreads();
 
         const T gxi = sponge.next(p, i);
-        T vv[R], xv[R];
+        T vv[R], xv[R], hx[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int lr = M + w * R + r;
@@ -535,9 +570,10 @@ __global__ void __launch_bounds__(kThreads) k_march_mh(const MediumParamsH<T> p)
             const T lap = sum_div<T>(tx, ty, tz, p);
             const T a = aux.av(Ph<H0>{}, r), q = aux.qv(Ph<H0>{}, r);
             xv[r] = side_value<T, MODE>(c, lap, a, q);
+            hx[r] = illum_value<T, MODE>(lap, a);
             vv[r] = medium_update<T, FIRST, TAPER, MODE>(c, u2[H0][r], lap, mm[H0][r], gxi, sponge.yz(r), a, q);
         }
-        store_plane<MODE>(t, p, i, vv, xv, os);
+        store_plane<MODE>(t, p, i, vv, xv, hx, os);
         plane_stats(p, i, vv, valid, chk, ma);
     };
     march_planes<NS>(ib, t.ie, plane);
@@ -687,7 +723,7 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
         __syncthreads();
 
         const T gxi = sponge.next(p, i);
-        T vv[R], xv[R];
+        T vv[R], xv[R], hx[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int lr = 1 + w * R + r;
@@ -714,9 +750,10 @@ __global__ void __launch_bounds__(kThreads) k_march_mb(const MediumParamsB<T> p)
                 q = sum_div<T>(rx, ry, rz, p);
             }
             xv[r] = side_value<T, MODE>(c, lap, a, q, mm[H0][r]);
+            hx[r] = illum_value<T, MODE>(lap, a);
             vv[r] = medium_update<T, FIRST, TAPER, MODE>(c, u2[H0][r], lap, mm[H0][r], gxi, sponge.yz(r), a, q);
         }
-        store_plane<MODE>(t, p, i, vv, xv, os);
+        store_plane<MODE>(t, p, i, vv, xv, hx, os);
         plane_stats(p, i, vv, valid, chk, ma);
     };
     march_planes<4>(ib, t.ie, plane);
@@ -738,6 +775,8 @@ auto select_march(bool first, bool taper, int mode, F pick) {
         case kBorn: return with_taper(std::false_type{}, Ph<kBorn>{});
         case kScatter: return with_taper(std::false_type{}, Ph<kScatter>{});
         case kBornAdd: return with_taper(std::false_type{}, Ph<kBornAdd>{});
+        case kIllum: return with_taper(std::false_type{}, Ph<kIllum>{});
+        case kSaveIllum: return with_taper(std::false_type{}, Ph<kSaveIllum>{});
         default: break;
     }
     return first ? with_taper(std::true_type{}, Ph<kPlain>{}) : with_taper(std::false_type{}, Ph<kPlain>{});
@@ -851,7 +890,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                         const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
                         const double h2[3], u64* err, int chunk, hipStream_t s, int variant, const T* gx,
                         const T* gy, const T* gz, T* lap_out, const T* q, T* acc, int order, const int* mirror,
-                        const T* b, const T* dm, const T* db, const T* sadd) {
+                        const T* b, const T* dm, const T* db, const T* sadd, T* illum) {
     W3D_REQUIRE(order == 2 || order == 4 || order == 8, "space order must be 2, 4 or 8, not " + std::to_string(order));
     W3D_REQUIRE(!b || order == 2, "variable density (b) exists for space order 2 only");
     const int M = order / 2;
@@ -895,7 +934,23 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
         // q and dm are read while u is written (own plane and wrap planes): no shared memory
         W3D_REQUIRE(!overlaps<T>(u, q, span) && !overlaps<T>(u, dm, span), "Born mode: q or dm shares memory with u");
     }
-    const int mode = scatter ? kScatter : born_add ? kBornAdd : save ? kSave : image ? kImage : born ? kBorn : kPlain;
+    // Illumination modes (illum, alone or with lap_out): leapfrog steps of the default variant only
+    if (illum) {
+        W3D_REQUIRE(!first, "illumination modes (illum): not on the Taylor start (first)");
+        W3D_REQUIRE(!q && !acc && !dm && !db && !sadd,
+                    "illumination modes (illum) cannot be combined with image, Born, scatter or Born-add mode");
+        W3D_REQUIRE(variant == 1 || M > 1,
+                    "illumination modes (illum) are instantiated for the default variant only (nt, 4 rows per lane)");
+        for (const T* o : {(const T*)u, u1, u2, m, b, (const T*)lap_out})
+            W3D_REQUIRE(!o || !overlaps<T>(illum, o, span), "illumination modes: illum shares memory with another grid");
+    }
+    const int mode = illum     ? (save ? kSaveIllum : kIllum)
+                     : scatter ? kScatter
+                     : born_add ? kBornAdd
+                     : save     ? kSave
+                     : image    ? kImage
+                     : born     ? kBorn
+                                : kPlain;
     // reflecting faces of k_march_mh: (j_lo, j_hi, k_lo, k_hi), +-2^29 where there is none
     int mir[4] = {kNoMirror, -kNoMirror, kNoMirror, -kNoMirror};
     bool has[4] = {false, false, false, false};
@@ -935,6 +990,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     p.q = born_add ? sadd : scatter ? db : q;
     p.acc = acc;
     p.dm = dm;
+    p.illum = illum;
     for (int q = 0; q < nbox; ++q) {
         const Box& bx = boxes[q];
         if (bx.empty()) continue;
@@ -998,7 +1054,7 @@ void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int
                                         const Box*, int, int, int, const Wrap&, const double[3], u64*, \
                                         int, hipStream_t, int, const T*, const T*, const T*, T*,       \
                                         const T*, T*, int, const int*, const T*, const T*, const T*,   \
-                                        const T*);                                                      \
+                                        const T*, T*);                                                  \
     template void launch_inject<T>(T*, const T*, const GridView&, const int*, const T*, int,           \
                                    const Wrap&, hipStream_t);                                          \
     template void launch_record<T>(const T*, const GridView&, const int*, T*, int, hipStream_t);

@@ -73,6 +73,16 @@ namespace wave3d {
 // u = G (((2 u1 - G u2) + m D_b u1) + s); s is read once at the box nodes with the strides of u and
 // must not share memory with it. The wrap, err[0] and the non-finite flag are those of the updated
 // values, as in Born mode. Per node in fp64: 48 B.
+//
+// Source illumination (illum non-null; all three march kernels, leapfrog steps only, variant 1 at
+// order 2): the plain step (illum mode), or with lap_out the save step (save+illum mode), that also does
+// illum = illum + lap * lap at the box nodes, lap being the value that entered the update (D_b u1 with
+// b), the product rounded before the add. One read-modify-write stream with the strides of u; nothing
+// outside the boxes is written and the wrap does not apply to it. u, the wrap, err and lap_out are
+// those of the plain step and of save mode bit for bit. Rejected before the launch: illum with first,
+// with a non-default variant at order 2, with q, acc, dm, db or sadd (image, Born, scatter and Born-add
+// modes), and an illum that shares memory with u, u1, u2, m, b or lap_out. Per node in fp64: 48 B
+// (illum), 56 B (save+illum); with b 56 B and 64 B.
 constexpr int kNoMirror = -(1 << 29);
 template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
@@ -81,7 +91,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                         const T* gx = nullptr, const T* gy = nullptr, const T* gz = nullptr,
                         T* lap_out = nullptr, const T* q = nullptr, T* acc = nullptr, int order = 2,
                         const int* mirror = nullptr, const T* b = nullptr, const T* dm = nullptr,
-                        const T* db = nullptr, const T* sadd = nullptr);
+                        const T* db = nullptr, const T* sadd = nullptr, T* illum = nullptr);
 
 // Central second-derivative weight c_d of the star stencil of `order` (2, 4, 8), d = 0 .. order / 2:
 // the double quotient of its two integers (order 4: -5/2, 4/3, -1/12; order 8: -205/72, 8/5, -1/5,

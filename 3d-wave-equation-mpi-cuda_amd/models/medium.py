@@ -371,7 +371,8 @@ class MediumSolver:
 
     # ---- misfit gradients (adjoint state; ops/reference.py has the mathematics) ------------
 
-    def gradient(self, observed, *, segment: int | None = None, wrt_density: bool = False) -> "MediumGradient":
+    def gradient(self, observed, *, segment: int | None = None, wrt_density: bool = False,
+                 illumination: bool = False) -> "MediumGradient":
         """Misfit ``J = 1/2 sum_{n=1..K} sum_r (trace[n, r] - observed[n, r])^2`` and its gradients
         with respect to ``speed2`` and the wavelet (full-waveform-inversion gradient / reverse-time
         migration image). ``observed``: ``[timesteps + 1, len(receivers)]``, row 0 is ignored.
@@ -396,6 +397,21 @@ class MediumSolver:
         and density, ...). "hip": each segment then also keeps the levels u^n of its steps beside q,
         ``min(segment, K - 1)`` more levels plus one accumulator, and every adjoint step is followed
         by one ``k_face_corr`` call; the other results do not change by a bit.
+
+        ``illumination=True`` also returns the source illumination and the diagonal of Shin's
+        pseudo-Hessian for ``speed2``, the usual scaling of the gradient (:func:`precondition`) and
+        preconditioner of a Gauss-Newton iteration: ``illumination = sum_{n=1..K-1} q^n q^n`` at the
+        stencil nodes, q^n the Laplacian (``div(b grad u^n)`` with a density) that entered forward step
+        n + 1, the very values the gradient correlates with the adjoint field; each product is rounded,
+        then added, in ascending n. ``pseudo_hessian_speed2 = illumination (w w)`` with
+        ``w = (G tau) tau [rho]``, G the sponge factor of the node, finished on the host in the working
+        dtype (``ops.reference.finish_illumination``). Both follow the convention of ``grad_speed2``
+        (plane N a copy of plane 0, the Dirichlet faces 0). The pseudo-Hessian ignores the source term
+        of dJ/dm at the source nodes. ``variant`` must be None. "hip": one more level; the forward pass
+        proper runs its steps 2..K in the illum mode of ``ops.kernels.step_medium`` (save+illum in the
+        last segment) and the recomputed steps stay in save mode, so every q^n is added exactly once,
+        in ascending n, and the result does not depend on ``segment`` by a bit; the other results do not
+        change by a bit either.
         """
         p = self.problem
         K = p.timesteps
@@ -409,16 +425,19 @@ class MediumSolver:
                              f"not {tuple(obs.shape)}")
         if segment is not None and int(segment) < 1:
             raise ValueError(f"segment must be >= 1 step, not {segment}")
-        wrt_density = bool(wrt_density)
+        wrt_density, illumination = bool(wrt_density), bool(illumination)
+        if illumination and self.variant is not None:
+            raise ValueError(f"gradient(illumination=True) exists for the default kernel variant only: build the "
+                             f"MediumSolver with variant=None, not {self.variant!r}")
         if wrt_density and p.density is None:
             raise ValueError("gradient(wrt_density=True) needs a density model: build the MediumProblem with "
                              "density=... (a scalar such as 1.0 is fine)")
         obs = obs.detach().cpu()
         if self.backend == "cpu":
-            return self._gradient_cpu(obs, wrt_density)
-        return self._gradient_hip(obs, segment, wrt_density)
+            return self._gradient_cpu(obs, wrt_density, illumination)
+        return self._gradient_hip(obs, segment, wrt_density, illumination)
 
-    def _gradient_cpu(self, obs, wrt_density: bool = False) -> "MediumGradient":
+    def _gradient_cpu(self, obs, wrt_density: bool = False, illumination: bool = False) -> "MediumGradient":
         import time
 
         from ..ops import reference
@@ -426,15 +445,20 @@ class MediumSolver:
         p = self.problem
         t0 = time.perf_counter()
         fn = reference.gradient_medium_density if wrt_density else reference.gradient_medium
-        J, gs, gw, tr, *gd = fn(p.N, p.timesteps, p.speed2, obs, sources=self.sources, wavelet=self.wavelet,
-                                receivers=self.receivers, taper=self.taper, L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi,
-                                dtype=p.torch_dtype, order=p.space_order, density=p.density)
+        kw = dict(illumination=True) if illumination else {}
+        J, gs, gw, tr, *more = fn(p.N, p.timesteps, p.speed2, obs, sources=self.sources, wavelet=self.wavelet,
+                                  receivers=self.receivers, taper=self.taper, L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi,
+                                  dtype=p.torch_dtype, order=p.space_order, density=p.density, **kw)
+        il, ph = more[-2:] if illumination else (None, None)
         return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr,
-                              total_ms=(time.perf_counter() - t0) * 1e3, grad_density=gd[0] if gd else None,
+                              total_ms=(time.perf_counter() - t0) * 1e3,
+                              grad_density=more[0] if wrt_density else None, illumination=il,
+                              pseudo_hessian_speed2=ph,
                               extra=dict(segment=None, levels=None, recomputed_steps=0, space_order=p.space_order,
-                                         density=p.density is not None, wrt_density=wrt_density))
+                                         density=p.density is not None, wrt_density=wrt_density,
+                                         illumination=illumination))
 
-    def _gradient_hip(self, obs, segment, wrt_density: bool = False) -> "MediumGradient":
+    def _gradient_hip(self, obs, segment, wrt_density: bool = False, illumination: bool = False) -> "MediumGradient":
         import time
 
         from ..ops import kernels, reference
@@ -445,12 +469,13 @@ class MediumSolver:
         dev, c, M, box, wrap, h2, level = s.dev, s.c, s.M, s.box, s.wrap, s.h2, s.level
         with torch.cuda.device(dev):
             if segment is None:
-                segment = best_gradient_segment(K, wrt_density=wrt_density)
+                segment = best_gradient_segment(K, wrt_density=wrt_density, illumination=illumination)
                 what = "the smallest schedule"
             else:
                 segment = int(segment)
                 what = f"the schedule of segment = {segment}"
-            nlev = gradient_levels(K, segment, density=p.density is not None, wrt_density=wrt_density)
+            nlev = gradient_levels(K, segment, density=p.density is not None, wrt_density=wrt_density,
+                                   illumination=illumination)
             s.require_levels(nlev, f"gradient(): {what}")
             # forward steps 2..K in segments [a, b]; the last one keeps its q, the others a checkpoint
             segs = [(a, min(a + segment - 1, K)) for a in range(2, K + 1, segment)]
@@ -464,6 +489,7 @@ class MediumSolver:
             # (its own data: with one segment the adjoint ring overwrites the forward ring), and accb
             ub = [level() for _ in range(qlen)] if wrt_density else None
             accb = level() if wrt_density else None
+            hl = level() if illumination else None  # h = sum q^n q^n, added to by the forward pass proper alone
             ck = [(level(), level()) for _ in segs[:-1]]
             mc = s.medium(m, lv[0])
             step_kw, tt, taper, gsrc, g, src, rec = s.step_kw, s.tt, s.taper, s.gsrc, s.g, s.src, s.rec
@@ -475,11 +501,11 @@ class MediumSolver:
                 if wrt_density:
                     ub[n - (a - 1)]._base.copy_(lv[n % 3]._base)
 
-            def forward_step(n, slot, save):
+            def forward_step(n, slot, save, illum=None):
                 u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
                 kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=slot, stat_i=(M, N + M), wrap=wrap,
                                     variant=None if save is not None else self.variant, taper=taper, lap_out=save,
-                                    **step_kw)
+                                    illum=illum, **step_kw)
                 kernels.inject(u, m, src, g[n - 1], wrap)
 
             # forward pass: run()'s steps; checkpoints before the segments, q of the last segment
@@ -496,7 +522,7 @@ class MediumSolver:
                 if last:
                     keep_level(a - 1, a)
                 for n in range(a, b + 1):
-                    forward_step(n, stat[3 * n:3 * n + 3], qb[n - a] if last else None)
+                    forward_step(n, stat[3 * n:3 * n + 3], qb[n - a] if last else None, hl)
                     kernels.record(lv[n % 3], rec, traces[n])
                     if last and n < b:
                         keep_level(n, a)
@@ -547,12 +573,16 @@ class MediumSolver:
             if wrt_density:
                 gd = reference.finish_gradient_density(acc_c, accb.cpu(), a_c, gsrc, mc, tt, self.sources, N,
                                                        c["tau"], p.speed2, p.density, M)
+            il = ph = None
+            if illumination:
+                il, ph = reference.finish_illumination(hl.cpu(), tt, N, c["tau"], M, p.density)
             torch.cuda.synchronize(dev)
             ms = (time.perf_counter() - t0) * 1e3
             return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr, total_ms=ms, grad_density=gd,
+                                  illumination=il, pseudo_hessian_speed2=ph,
                                   extra=dict(segment=segment, levels=nlev, recomputed_steps=recomputed,
                                              space_order=p.space_order, density=p.density is not None,
-                                             wrt_density=wrt_density,
+                                             wrt_density=wrt_density, illumination=illumination,
                                              forward_ms=ev[0].elapsed_time(ev[1]), reverse_ms=ev[2].elapsed_time(ev[3])))
 
 
@@ -695,7 +725,7 @@ class MediumSolver:
                                          ddensity=dr is not None, loop_ms=ev0.elapsed_time(ev1)))
 
     def gauss_newton(self, dspeed2=None, dwavelet=None, ddensity=None, *, segment: int | None = None,
-                     wrt_density: bool | None = None) -> "MediumGradient":
+                     wrt_density: bool | None = None, illumination: bool = False) -> "MediumGradient":
         """The Gauss-Newton Hessian applied to a perturbation: one :meth:`born` run, then
         :meth:`gradient` with ``observed = traces - dtraces``, so that the residuals are ``dtraces`` and
         ``grad_speed2``, ``grad_wavelet`` are ``J^T J [dspeed2; dwavelet]`` (``misfit`` is
@@ -704,11 +734,13 @@ class MediumSolver:
 
         ``ddensity``: the density block of the perturbation (:meth:`born`). ``wrt_density`` (default:
         whether ``ddensity`` is given) also returns ``grad_density``, the density row of
-        ``J^T J [dspeed2; dwavelet; ddensity]``, with the wall convention of :meth:`gradient`."""
+        ``J^T J [dspeed2; dwavelet; ddensity]``, with the wall convention of :meth:`gradient`.
+        ``illumination``: passed through to :meth:`gradient` (the pseudo-Hessian diagonal, the usual
+        preconditioner of a conjugate-gradient iteration on these products)."""
         b = self.born(dspeed2, dwavelet, ddensity)
         if wrt_density is None:
             wrt_density = ddensity is not None
-        r = self.gradient(b.traces - b.dtraces, segment=segment, wrt_density=wrt_density)
+        r = self.gradient(b.traces - b.dtraces, segment=segment, wrt_density=wrt_density, illumination=illumination)
         r.extra["dtraces"] = b.dtraces
         r.extra["born_ms"] = b.total_ms
         return r
@@ -827,25 +859,52 @@ class MediumGradient:
     extra: dict = field(default_factory=dict)
     # gradient(wrt_density=True): (N+1)^3, dJ/drho at fixed speed2 on the stencil nodes (plane N = plane 0, faces 0)
     grad_density: torch.Tensor | None = None
+    # gradient(illumination=True): (N+1)^3 each, sum_n q^n q^n and the pseudo-Hessian diagonal for speed2
+    # (plane N = plane 0, faces 0)
+    illumination: torch.Tensor | None = None
+    pseudo_hessian_speed2: torch.Tensor | None = None
 
 
-def gradient_levels(K: int, segment: int, density: bool = False, wrt_density: bool = False) -> int:
+def precondition(grad, pseudo_hessian, eps: float = 1e-3):
+    """``grad / (pseudo_hessian + eps * pseudo_hessian.max())``: a gradient such as ``grad_speed2`` scaled
+    by the diagonal ``pseudo_hessian_speed2`` of :meth:`MediumSolver.gradient` (``illumination=True``),
+    the water level ``eps > 0`` keeping the nodes the sources hardly reach finite. The pseudo-Hessian
+    must have a positive maximum. The output follows the convention of the two inputs (plane N a
+    copy of plane 0, the Dirichlet faces 0)."""
+    g, ph = torch.as_tensor(grad), torch.as_tensor(pseudo_hessian)
+    if tuple(g.shape) != tuple(ph.shape):
+        raise ValueError(f"grad and pseudo_hessian must have the same shape, not {tuple(g.shape)} and "
+                         f"{tuple(ph.shape)}")
+    if not (isinstance(eps, (int, float)) and math.isfinite(eps) and eps > 0):
+        raise ValueError(f"eps must be finite and > 0, not {eps!r}")
+    top = ph.max() if ph.numel() else None
+    if top is None or not bool(torch.isfinite(top)) or not bool(top > 0):
+        raise ValueError("pseudo_hessian must have a finite, positive maximum")
+    return g / (ph + eps * top)
+
+
+def gradient_levels(K: int, segment: int, density: bool = False, wrt_density: bool = False,
+                    illumination: bool = False) -> int:
     """Number of grid levels the "hip" schedule of :meth:`MediumSolver.gradient` holds for K
     timesteps cut into segments of ``segment`` steps (steps 2..K): the forward ring (3), m, acc, the
     q buffer (one level per step of a segment), a checkpoint pair per segment but the last, and,
     when there is anything to recompute, a second ring for the adjoint field. ``density``: one more
     level, the buoyancy of a problem with a density model. ``wrt_density``: the levels u^n of a segment's
-    steps beside its q buffer and the accumulator of the density gradient, ``min(segment, K - 1) + 1`` more."""
+    steps beside its q buffer and the accumulator of the density gradient, ``min(segment, K - 1) + 1`` more.
+    ``illumination``: one more level, the accumulator of the source illumination."""
     K, segment = int(K), int(segment)
     if K < 1 or segment < 1:
         raise ValueError(f"need K >= 1 and segment >= 1, not K={K} segment={segment}")
     nseg = -(-(K - 1) // segment)
     nq = min(segment, K - 1)
-    return 5 + bool(density) + nq + (nq + 1 if wrt_density else 0) + (2 * (nseg - 1) + 3 if nseg > 1 else 0)
+    return (5 + bool(density) + bool(illumination) + nq + (nq + 1 if wrt_density else 0)
+            + (2 * (nseg - 1) + 3 if nseg > 1 else 0))
 
 
-def best_gradient_segment(K: int, wrt_density: bool = False) -> int:
+def best_gradient_segment(K: int, wrt_density: bool = False, illumination: bool = False) -> int:
     """The segment length with the fewest levels (``wrt_density``: of the schedule with the density
-    gradient); every schedule recomputes less than one extra forward pass, and of equal level counts
-    the longer segment (less recomputation) wins."""
-    return min(range(1, max(K - 1, 1) + 1), key=lambda s: (gradient_levels(K, s, wrt_density=wrt_density), -s))
+    gradient; ``illumination``: with the illumination's level, the same for every segment); every schedule
+    recomputes less than one extra forward pass, and of equal level counts the longer segment (less
+    recomputation) wins."""
+    return min(range(1, max(K - 1, 1) + 1),
+               key=lambda s: (gradient_levels(K, s, wrt_density=wrt_density, illumination=illumination), -s))

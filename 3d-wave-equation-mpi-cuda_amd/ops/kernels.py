@@ -355,7 +355,7 @@ def _check_taper(taper, u) -> list[int]:
 
 def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None, chunk: int = 0,
                 variant: str | None = None, taper=None, lap_out=None, image=None, order: int = 2,
-                mirror=None, buoyancy=None, born=None, scatter=None, born_add=None) -> None:
+                mirror=None, buoyancy=None, born=None, scatter=None, born_add=None, illum=None) -> None:
     """One layer of ``u_tt = c^2 (lap u + f)`` over ``boxes``: ``u = (2 u1 - u2) + m lap(u1)``, on
     the Taylor start (``first``) ``u = u1 + (0.5 m) lap(u1)``, with ``m = c^2 tau^2`` per node.
 
@@ -417,6 +417,16 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     ``u = G (((2 u1 - G u2) + m D_b u1) + s)``; ``s`` is read at the box nodes and must not share memory
     with ``u``; the wrap and ``stat`` are those of the updated values. All these grids match ``u`` in
     shape, dtype, device and strides.
+
+    ``illum = h`` (illum mode; with ``lap_out`` save+illum mode): the step also does ``h = h + lap * lap``
+    at the box nodes, ``lap`` being the value that entered the update (``div(b grad u1)`` with
+    ``buoyancy``), the product rounded before the add: the source illumination of
+    ``MediumSolver.gradient(illumination=True)``. ``u``, the wrap, ``stat`` and ``lap_out`` stay those of
+    the plain step and of save mode bit for bit; nothing outside the boxes is written and the wrap does
+    not apply to ``h``. It matches ``u`` in shape, dtype, device and strides and must not share memory
+    with ``u``, ``u1``, ``u2``, ``m``, ``buoyancy`` or ``lap_out``. For leapfrog steps of the default
+    variant only, at every order and with a buoyancy; combinable with ``lap_out`` alone, not with
+    ``image``, ``born``, ``scatter`` or ``born_add``.
     """
     if order not in (2, 4, 8):
         raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
@@ -480,9 +490,30 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
             extra = [lap_out]
         if not all(isinstance(t, torch.Tensor) for t in extra):
             raise ValueError("lap_out, q and acc must be tensors")
+    if illum is not None:
+        if image is not None or born is not None or scatter is not None or born_add is not None:
+            raise ValueError("illumination modes (illum) cannot be combined with image mode (image), Born mode "
+                             "(born), scatter mode (scatter) or Born-add mode (born_add)")
+        if first:
+            raise ValueError("illumination modes (illum): not on the Taylor start (first=True)")
+        if variant not in (None, "nt"):
+            raise ValueError(f"illumination modes (illum) exist for the default variant only, not {variant!r}")
+        if order == 2:
+            variant = "nt"
+        if not isinstance(illum, torch.Tensor):
+            raise ValueError("illum must be a tensor")
+        extra = extra + [illum]
     if buoyancy is not None:
         extra = extra + [buoyancy]
     gv = _check_grid_strided(u1, u2, m, u, *extra)
+    if illum is not None:
+        h_0, h_1 = _grid_span(illum)
+        for t, name in zip((u, u1, u2, m, buoyancy, lap_out), ("u", "u1", "u2", "m", "buoyancy", "lap_out")):
+            if t is None:
+                continue
+            t0, t1 = _grid_span(t)
+            if h_0 < t1 and t0 < h_1:
+                raise ValueError(f"illumination modes: illum shares memory with {name}")
     if born is not None:
         u_0, u_1 = _grid_span(u)
         for t, name in zip(born, ("q", "dm")):
@@ -531,7 +562,8 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
        buoyancy.data_ptr() if buoyancy is not None else 0,
        born[1].data_ptr() if born is not None else scatter[1].data_ptr() if scatter is not None else 0,
        scatter[2].data_ptr() if scatter is not None else 0,
-       born_add.data_ptr() if born_add is not None else 0)
+       born_add.data_ptr() if born_add is not None else 0,
+       illum.data_ptr() if illum is not None else 0)
 
 
 def _grid_span(t: torch.Tensor) -> tuple[int, int]:

@@ -772,10 +772,35 @@ def finish_gradient_density(acc, accb, a, g, m, tt, sources, N: int, tau: float,
     return _unique_node_convention(part1 + part2, N)
 
 
+def finish_illumination(h, tt, N: int, tau: float, ghost: int = 1, density=None):
+    """The host-side end of the source illumination, shared by both backends. h
+    ``[N+1+2 ghost][N+1][N+1]`` = sum_{n=1..K-1} q^n q^n in storage, a CPU tensor of the working dtype;
+    tt = the ``taper_tables`` (None: G = 1). Returns (illumination, pseudo_hessian_speed2), both
+    ``(N+1)^3`` in the convention of dJ/dspeed2 (plane N a copy of plane 0, the Dirichlet faces 0).
+
+    The Born step injects ``G dm q^n`` for a perturbation of speed2 at a node, ``dm = rho tau^2 dspeed2``
+    (rho = 1 without a density), so the diagonal of Shin's pseudo-Hessian for speed2 is
+    ``illumination * (w * w)`` with ``w = (G tau) tau [rho]``, G = gx[i] (gy[j] gz[k]) rounded like
+    ``step_medium``, every operation in the working dtype. The source term of dJ/dm at the source nodes
+    is not part of it."""
+    illum = h[ghost:N + 1 + ghost].clone()
+    if tt is None:
+        G = torch.ones((), dtype=h.dtype)
+    else:
+        G = tt[0][ghost:N + 1 + ghost, None, None] * (tt[1][None, :, None] * tt[2][None, None, :])
+    w = (G * tau) * tau
+    if density is not None:
+        w = w * _node_field(density, N, "density").to(h.dtype)
+    ph = illum * (w * w)
+    return _unique_node_convention(illum, N), _unique_node_convention(ph, N)
+
+
 def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, receivers, taper, L, T, pi, dtype,
-                    order: int, density, wrt_density: bool):
+                    order: int, density, wrt_density: bool, illumination: bool = False):
     """The forward run and the adjoint loop shared by ``gradient_medium`` and
-    ``gradient_medium_density``: everything their host-side ends need, as a dict."""
+    ``gradient_medium_density``: everything their host-side ends need, as a dict. ``illumination``: also
+    ``h = h + q^n q^n`` over the forward run's q^1 .. q^{K-1} in that order, the product rounded before
+    the add, on the stencil nodes in storage (``finish_illumination`` has the rest)."""
     fwd = forward_medium_autograd(N, K, speed2, sources=sources, wavelet=wavelet, receivers=receivers,
                                   taper=taper, L=L, T=T, pi=pi, dtype=dtype, keep_lap=True, order=order,
                                   density=density, keep_levels=wrt_density)
@@ -792,6 +817,11 @@ def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, recei
     shape = (N + 1 + 2 * M, N + 1, N + 1)
     own = (slice(M, N + 1 + M), slice(1, N), slice(1, N))
     a = torch.zeros(K, len(snodes), dtype=dtype)
+    h = None
+    if illumination:  # ascending n, the q^n the adjoint loop correlates with mu^{n+1}
+        h = torch.zeros(shape, dtype=dtype)
+        for q in laps:
+            h[own] = h[own] + q * q
 
     def finish_level(mu, n):  # inject G rho^n, wrap, sample mu^n at the sources
         for e, nd in enumerate(anodes):
@@ -815,12 +845,12 @@ def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, recei
         mu[own] = vals
         finish_level(mu, n)
         mu2, mu1 = mu1, mu
-    return dict(J=J, traces=traces, acc=acc, accb=accb, a=a, g=g, m=m, tt=tt, c=c, M=M)
+    return dict(J=J, traces=traces, acc=acc, accb=accb, a=a, g=g, m=m, tt=tt, c=c, M=M, h=h)
 
 
 def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,
                     L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, order: int = 2,
-                    density=None):
+                    density=None, illumination: bool = False):
     """Misfit J of the traces against ``observed`` ``[K+1, R]`` (row 0 ignored) and its gradients by
     the hand-written adjoint above: (J, dJ/dspeed2 ``(N+1)^3``, dJ/dwavelet ``[K, S]``, traces).
 
@@ -836,23 +866,31 @@ def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=Non
 
     density: rho of ``solve_medium`` (order 2), held fixed: ``laplace_density`` is symmetric on the
     unique nodes too, so the adjoint field runs on the same density step, and dJ/dspeed2 is the
-    derivative at fixed rho (``finish_gradient_medium``). dJ/drho: ``gradient_medium_density``."""
+    derivative at fixed rho (``finish_gradient_medium``). dJ/drho: ``gradient_medium_density``.
+
+    illumination: two more results, (source illumination, pseudo-Hessian diagonal for speed2), both
+    ``(N+1)^3`` (``finish_illumination``): sum_{n=1..K-1} q^n q^n over the q^n above, added in ascending
+    n, the product rounded before the add. The other results do not change."""
     with torch.no_grad():
         r = _adjoint_medium(N, K, speed2, observed, sources=sources, wavelet=wavelet, receivers=receivers,
                             taper=taper, L=L, T=T, pi=pi, dtype=dtype, order=order, density=density,
-                            wrt_density=False)
+                            wrt_density=False, illumination=illumination)
         c = r["c"]
         grad, gw = finish_gradient_medium(r["acc"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"], c["hx"],
                                           c["hy"], c["hz"], r["M"], density)
-        return r["J"], grad, gw, r["traces"]
+        out = (r["J"], grad, gw, r["traces"])
+        if illumination:
+            out += finish_illumination(r["h"], r["tt"], N, c["tau"], r["M"], density)
+        return out
 
 
 def gradient_medium_density(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,
                             L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
-                            order: int = 2, density=None):
+                            order: int = 2, density=None, illumination: bool = False):
     """``gradient_medium`` of a problem with a ``density`` (required; order 2), plus the gradient with
     respect to it: (J, dJ/dspeed2 at fixed rho, dJ/dwavelet, traces, dJ/drho at fixed speed2). The
-    first four are those of ``gradient_medium`` bit for bit.
+    first four are those of ``gradient_medium`` bit for bit. ``illumination``: ``gradient_medium``'s two
+    more results, after the five.
 
     Beside ``acc`` the adjoint loop accumulates ``accb = accb + C(mu^{n+1}, u^n)`` (``face_correlation``)
     for n = K-1 .. 1 in that order, mu^{n+1} injected and wrapped; by summation by parts (mu is 0 on
@@ -866,13 +904,16 @@ def gradient_medium_density(N: int, K: int, speed2, observed, *, sources=(), wav
     with torch.no_grad():
         r = _adjoint_medium(N, K, speed2, observed, sources=sources, wavelet=wavelet, receivers=receivers,
                             taper=taper, L=L, T=T, pi=pi, dtype=dtype, order=order, density=density,
-                            wrt_density=True)
+                            wrt_density=True, illumination=illumination)
         c = r["c"]
         grad, gw = finish_gradient_medium(r["acc"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"], c["hx"],
                                           c["hy"], c["hz"], r["M"], density)
         gd = finish_gradient_density(r["acc"], r["accb"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"],
                                      speed2, density, r["M"])
-        return r["J"], grad, gw, r["traces"], gd
+        out = (r["J"], grad, gw, r["traces"], gd)
+        if illumination:
+            out += finish_illumination(r["h"], r["tt"], N, c["tau"], r["M"], density)
+        return out
 
 
 # ---- Born (linearised) modelling of the medium solver ---------------------------------------

@@ -5,7 +5,7 @@
                                  [--variants default,plain,r2,r2nt] [--repeat 3] [--no-yardstick]
                                  [--taper WIDTH] [--order 2,4,8] [--density]
     python tools/bench_medium.py --gradient [--N 512] [--steps 100] [--dtypes fp64,fp32] [--segment 10]
-                                 [--order 2,8] [--kernels-only] [--density]
+                                 [--order 2,8] [--kernels-only] [--density] [--illum]
     python tools/bench_medium.py --gradient --density --wrt-density [--N 512] [--steps 100] [--segment 10]
     python tools/bench_medium.py --born [--N 512] [--steps 100] [--dtypes fp64,fp32] [--order 2,4,8]
                                  [--kernels-only] [--density]
@@ -26,7 +26,11 @@ process: ms/step of the plain step, the save step (+ lap_out: 40 B per node in f
 the image step (+ q, acc read, acc written: 56 B), `--repeat` rounds of 20 launches each, the three
 alternating inside each round, with and without a sponge of 16 nodes; then, alternating as well,
 one forward run() and gradient() with every q stored (segment = steps) and with `--segment`: the
-device time of the passes beside run()'s time loop, and the wall time of the whole call.
+device time of the passes beside run()'s time loop, and the wall time of the whole call. `--illum`
+adds the illum step (+ h read and written: 48 B per node in fp64, 1.5 times the plain step) and the
+save+illum step (56 B, 1.4 times the save step: `ratio_to_save`) to the alternating kernel rounds, and
+gradient(illumination=True) beside each schedule (`passes_vs_without`: its two passes over those of
+the same schedule without the flag, in the same job).
 
 `--born` measures Born (linearised) modelling instead (MediumSolver.born), with `--gradient`'s layout:
 ms/step of the plain step, the save step and the Born step (+ q, dm read: 48 B per node in fp64
@@ -335,6 +339,7 @@ def gradient_bench(a) -> int:
     out = {"N": N, "steps": K, "orders": orders, "device": torch.cuda.get_device_name(0), "kernels": [],
            "born" if a.born else "gradient": []}
     third = "born" if a.born else "image"
+    illum = a.illum and not a.born
     if a.density:
         out["density"] = "two layers: 1, 2"
         if not a.kernels_only:
@@ -356,7 +361,7 @@ def gradient_bench(a) -> int:
         sets = {}
         for o in orders:
             M = 1 if o == "2d" else o // 2
-            lv = [kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev) for _ in range(6)]
+            lv = [kernels.alloc_level(N + 1 + 2 * M, N + 1, N + 1, dt, dev) for _ in range(7 if illum else 6)]
             lv[2].copy_(reference.medium_coefficient(speed2, c["tau"], N, dt, M, rho if o == "2d" else None))
             for t in (lv[0], lv[1], lv[5]):
                 t[:, 1:N, 1:N] = seed[1:N, 1:N]
@@ -372,17 +377,21 @@ def gradient_bench(a) -> int:
         stat = kernels.new_err(1, device=dev)
         reps = 20
         for tp_name in ("", "sponge"):
-            modes = ("plain", "save", third)
+            modes = ("plain", "save", third) + (("illum", "save_illum") if illum else ())
             ms = {(k, o): [] for k in modes for o in orders}
             for rnd in range(a.repeat + 1):  # round 0 warms up
                 for name in modes:
                     for o in orders:  # the orders alternate inside each round
                         S = sets[o]
-                        u1, u2, m, u, x, q = S["lv"]
+                        u1, u2, m, u, x, q = S["lv"][:6]
+                        hl = S["lv"][6] if illum else None
                         kw = {"plain": {}, "save": {"lap_out": x}, "image": {"image": (q, x)},
-                              "born": {"born": (q, x)}}[name]
+                              "born": {"born": (q, x)}, "illum": {"illum": hl},
+                              "save_illum": {"lap_out": x, "illum": hl}}[name]
                         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         x.zero_()
+                        if illum:
+                            hl.zero_()
                         if name == "born":  # x is dm here: smooth values instead of zeros
                             x.copy_(q)
                         e0.record()
@@ -395,7 +404,8 @@ def gradient_bench(a) -> int:
                         if rnd:
                             ms[(name, o)].append(e0.elapsed_time(e1) / reps)
             for o in orders:
-                for name, bpn in (("plain", 4), ("save", 5), ("born", 6) if a.born else ("image", 7)):
+                for name, bpn in ((("plain", 4), ("save", 5), ("born", 6) if a.born else ("image", 7))
+                                  + ((("illum", 6), ("save_illum", 7)) if illum else ())):
                     best = min(ms[(name, o)])
                     if o == "2d":
                         bpn += 1  # the buoyancy stream
@@ -410,10 +420,13 @@ def gradient_bench(a) -> int:
                         row["expected_vs_constant"] = round(bpn / (bpn - 1), 4)
                     elif 2 in orders:
                         row["vs_order2"] = round(best / min(ms[(name, 2)]), 4)
+                    if name == "save_illum":
+                        row["ratio_to_save"] = round(best / min(ms[("save", o)]), 4)
+                        row["expected_ratio_to_save"] = round(bpn / (bpn - 2), 4)
                     out["kernels"].append(row)
                     print(f"bench_medium: {dtype} order {o} {name} {tp_name}: {best:.4f} ms/step", file=sys.stderr,
                           flush=True)
-        del sets, lv, u1, u2, m, u, x, q, S
+        del sets, lv, u1, u2, m, u, x, q, S, hl
         torch.cuda.empty_cache()
         if a.kernels_only:
             continue
@@ -454,17 +467,20 @@ def gradient_bench(a) -> int:
                                        receivers=[(mid - K // 5, mid, mid), (mid, mid - K // 4, mid + 3)],
                                        taper=sponge) for o in orders}
         obs = {o: 0.9 * sols[o].run().traces for o in orders}  # warm-up
-        cfgs = [("run", None), ("all_q", K), (f"segment_{a.segment}", a.segment)]
-        rows = {(n, o): [] for n, _ in cfgs for o in orders}
+        cfgs = [("run", None, False), ("all_q", K, False), (f"segment_{a.segment}", a.segment, False)]
+        if illum:  # each schedule is followed by the same one with the illumination
+            cfgs = [d for c in cfgs for d in ((c, (c[0] + "_illum", c[1], True)) if c[1] is not None else (c,))]
+        rows = {(n, o): [] for n, _, _ in cfgs for o in orders}
         for _ in range(a.repeat):
-            for name, seg in cfgs:
+            for name, seg, il in cfgs:
                 for o in orders:
                     if seg is None:
                         r = sols[o].run()
                         rows[(name, o)].append({"loop_ms": round(r.total_ms, 2)})
                     else:
-                        r = sols[o].gradient(obs[o], segment=seg)
+                        r = sols[o].gradient(obs[o], segment=seg, illumination=il)
                         assert math.isfinite(r.misfit) and r.misfit > 0
+                        assert (r.illumination is not None) == il and (not il or float(r.illumination.max()) > 0)
                         rows[(name, o)].append({"wall_ms": round(r.total_ms, 1),
                                                 "forward_ms": round(r.extra["forward_ms"], 2),
                                                 "reverse_ms": round(r.extra["reverse_ms"], 2),
@@ -475,13 +491,17 @@ def gradient_bench(a) -> int:
                     torch.cuda.empty_cache()
         for o in orders:
             run_ms = min(v["loop_ms"] for v in rows[("run", o)])
-            for name, seg in cfgs[1:]:
+            for name, seg, il in cfgs[1:]:
                 best = min(rows[(name, o)], key=lambda v: v["forward_ms"] + v["reverse_ms"])
                 passes = best["forward_ms"] + best["reverse_ms"]
-                out["gradient"].append({"dtype": dtype, "order": o, "schedule": name, **best,
-                                        "passes_ms": round(passes, 2), "run_loop_ms": run_ms,
-                                        "passes_vs_run": round(passes / run_ms, 3),
-                                        "wall_ms_all": [v["wall_ms"] for v in rows[(name, o)]]})
+                row = {"dtype": dtype, "order": o, "schedule": name, **best, "passes_ms": round(passes, 2),
+                       "run_loop_ms": run_ms, "passes_vs_run": round(passes / run_ms, 3),
+                       "wall_ms_all": [v["wall_ms"] for v in rows[(name, o)]]}
+                if il:  # against the row of the same schedule without the flag, just before it
+                    base = out["gradient"][-1]
+                    row["passes_vs_without"] = round(passes / base["passes_ms"], 3)
+                    row["forward_vs_without"] = round(best["forward_ms"] / base["forward_ms"], 3)
+                out["gradient"].append(row)
     print(json.dumps(out))
     return 0
 
@@ -505,6 +525,8 @@ def main(argv=None) -> int:
                     help="also time the variable-density step (two-layer rho), alternating with the constant-density one")
     ap.add_argument("--wrt-density", action="store_true",
                     help="--gradient --density: time k_face_corr and gradient(wrt_density=True) instead")
+    ap.add_argument("--illum", action="store_true",
+                    help="--gradient: also time the illum and save+illum steps and gradient(illumination=True)")
     ap.add_argument("--ddensity", action="store_true",
                     help="--born --density: time the scatter and Born-add steps and born(ddensity=...) instead")
     a = ap.parse_args(argv)
@@ -524,6 +546,8 @@ def main(argv=None) -> int:
         ap.error("--order: a comma-separated list of 2, 4, 8")
     if a.density and 2 not in orders:
         ap.error("--density: order 2 must be among the orders")
+    if a.illum and (not a.gradient or a.wrt_density):
+        ap.error("--illum goes with --gradient (without --wrt-density)")
     if a.wrt_density:
         if not (a.gradient and a.density) or orders != [2]:
             ap.error("--wrt-density goes with --gradient --density at order 2")
