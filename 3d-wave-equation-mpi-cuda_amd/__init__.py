@@ -26,10 +26,14 @@ def __getattr__(name):
         return getattr(wave, name)
     if name in ("MediumProblem", "MediumSolver", "MediumResult", "MediumGradient", "MediumBorn", "ricker",
                 "sponge_taper", "gradient_levels", "best_gradient_segment", "born_levels", "cfl_limit",
-                "precondition"):
+                "precondition", "grid_position"):
         from .models import medium
 
         return getattr(medium, name)
+    if name == "interp_tables":
+        from .ops import reference
+
+        return reference.interp_tables
     if name == "presets":
         from .models import presets
 

@@ -379,6 +379,30 @@ void k_record(uintptr_t u, const std::vector<i64>& g, uintptr_t nodes, uintptr_t
     launch_record<T>(P<T>(u), gview(g), P<int>(nodes), P<T>(out), n, (hipStream_t)stream);
 }
 
+// Off-grid receivers (k_record_w): index / weight = device [n][3][8] (int32 / T), out: n device values
+template <class T>
+void k_record_w(uintptr_t u, const std::vector<i64>& g, uintptr_t index, uintptr_t weight, uintptr_t out, int n,
+                uintptr_t stream) {
+    launch_record_w<T>(P<T>(u), gview(g), P<int>(index), P<T>(weight), P<T>(out), n, (hipStream_t)stream);
+}
+
+// Row lists (k_inject_rows / k_rows_dot): nodes = device int32 [nrows][3], rowptr int32 [nrows + 1],
+// col int32 [nnz], w T [nnz], vals T [ng]
+template <class T>
+void k_inject_rows(uintptr_t u, uintptr_t m, const std::vector<i64>& g, uintptr_t nodes, uintptr_t rowptr,
+                   uintptr_t col, uintptr_t w, uintptr_t vals, int nrows, int nnz, int ng,
+                   const std::vector<int>& wrap, uintptr_t stream) {
+    launch_inject_rows<T>(P<T>(u), P<T>(m), gview(g), P<int>(nodes), P<int>(rowptr), P<int>(col), P<T>(w), P<T>(vals),
+                          nrows, nnz, ng, towrap(wrap), (hipStream_t)stream);
+}
+
+template <class T>
+void k_rows_dot(uintptr_t u, const std::vector<i64>& g, uintptr_t nodes, uintptr_t rowptr, uintptr_t col, uintptr_t w,
+                uintptr_t vals, int nrows, int nnz, int ng, uintptr_t sacc, uintptr_t stream) {
+    launch_rows_dot<T>(P<T>(u), gview(g), P<int>(nodes), P<int>(rowptr), P<int>(col), P<T>(w), P<T>(vals), nrows, nnz,
+                       ng, P<T>(sacc), (hipStream_t)stream);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_wave3d_C, m) {
@@ -649,6 +673,12 @@ PYBIND11_MODULE(_wave3d_C, m) {
     m.def("k_inject_f32", &k_inject<float>);
     m.def("k_record_f64", &k_record<double>);
     m.def("k_record_f32", &k_record<float>);
+    m.def("k_record_w_f64", &k_record_w<double>);
+    m.def("k_record_w_f32", &k_record_w<float>);
+    m.def("k_inject_rows_f64", &k_inject_rows<double>);
+    m.def("k_inject_rows_f32", &k_inject_rows<float>);
+    m.def("k_rows_dot_f64", &k_rows_dot<double>);
+    m.def("k_rows_dot_f32", &k_rows_dot<float>);
     m.def("medium_variant", &medium_variant);
     m.def("medium_weight", &medium_weight);
     m.attr("no_mirror") = kNoMirror;

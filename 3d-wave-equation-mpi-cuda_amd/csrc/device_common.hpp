@@ -215,6 +215,19 @@ __device__ __forceinline__ int find_box(const P& p, int bid) {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Storage of a level for the kernels that address single nodes (hip_medium.hip k_inject / k_record,
+// hip_medium_points.hip): strides and extents, storage indices 0 .. n-1 per axis.
+struct NodeGrid {
+    i64 si;
+    int sj;
+    int nx, ny, nz;  // storage extents: indices 0 .. n-1 exist
+};
+
+inline NodeGrid node_grid(const GridView& gv) {
+    W3D_REQUIRE(gv.G == 1 && gv.poff == 0, "medium kernels: one ghost layer");
+    return NodeGrid{gv.si, gv.sj, gv.X + 2, gv.Y + 2, gv.Z + 2};
+}
+
 // Planes per marching work item: `best` (measured at N = 512) unless that leaves fewer than
 // ~4 workgroups per CU; then shorter chunks (>= 8 planes) trade prologue work for occupancy.
 inline int auto_chunk(int best, int planes, int tiles) {

@@ -782,12 +782,6 @@ auto select_march(bool first, bool taper, int mode, F pick) {
     return first ? with_taper(std::true_type{}, Ph<kPlain>{}) : with_taper(std::false_type{}, Ph<kPlain>{});
 }
 
-struct NodeGrid {
-    i64 si;
-    int sj;
-    int nx, ny, nz;  // storage extents: indices 0 .. n-1 exist
-};
-
 __device__ __forceinline__ bool node_offset(const NodeGrid& g, const int* nodes, int e, int& i, i64& row) {
     i = nodes[3 * e];
     const int j = nodes[3 * e + 1], k = nodes[3 * e + 2];
@@ -822,11 +816,6 @@ __global__ void k_record(const T* u, NodeGrid gr, const int* nodes, T* out, int 
     i64 row;
     if (!node_offset(gr, nodes, e, i, row)) return;
     out[e] = u[i64(i) * gr.si + row];
-}
-
-NodeGrid node_grid(const GridView& gv) {
-    W3D_REQUIRE(gv.G == 1 && gv.poff == 0, "medium kernels: one ghost layer");
-    return NodeGrid{gv.si, gv.sj, gv.X + 2, gv.Y + 2, gv.Z + 2};
 }
 
 // k_march_m: the plain step exists in four variants (R, NTM); the modes for the default one only

@@ -124,6 +124,35 @@ template <class T>
 void launch_face_corr(const T* a, const T* v, T* acc, const GridView& gv, const Box* boxes, int nbox,
                       const double h2[3], int chunk, hipStream_t s);
 
+// Off-grid sources and receivers (hip_medium_points.hip): positions between the nodes act through
+// 8 slots per axis (ops/reference.py interp_tables; the slots carry the periodic wrap in x and the odd
+// reflection at the y/z faces already, as storage indices and signed weights).
+//
+// Weighted record (k_record_w): out[r] = sum over the 8 x 8 x 8 slots of receiver r, one wave64 per
+// receiver. index / weight = n x 3 x 8 (x, y, z slots; storage indices). Lane 8a + b forms
+// s = s + wz[c] u(ix[a], iy[b], iz[c]) for c = 0 .. 7 from s = 0, then t = (wx[a] wy[b]) s, and the wave
+// sums t by the xor butterfly 32, 16, 8, 4, 2, 1; every product is rounded before its add. An index
+// outside the storage contributes 0 and is never dereferenced.
+template <class T>
+void launch_record_w(const T* u, const GridView& gv, const int* index, const T* weight, T* out, int n,
+                     hipStream_t s);
+
+// Row injection (k_inject_rows): a CSR list of touched nodes, row = (i, j, k) storage indices with the
+// entries rowptr[row] .. rowptr[row + 1] - 1, each a weight w[e] and a column col[e] of g (ng values:
+// one time row of the compact source or residual table). Per row, one lane: val = val + w[e] g[col[e]]
+// from val = 0 in entry order, then u = u + m val and the ghost-plane copies of launch_inject. The
+// rows name distinct nodes (the caller checks); rows, entries and columns outside their tables are
+// skipped.
+template <class T>
+void launch_inject_rows(T* u, const T* m, const GridView& gv, const int* nodes, const int* rowptr, const int* col,
+                        const T* w, const T* g, int nrows, int nnz, int ng, const Wrap& wrap, hipStream_t s);
+
+// Row dot (k_rows_dot, an instantiation of k_inject_rows): sacc[row] = sacc[row] + u(row) val with the
+// val above, for the first `nrows` rows; nothing else is written. sacc must not share memory with u.
+template <class T>
+void launch_rows_dot(const T* u, const GridView& gv, const int* nodes, const int* rowptr, const int* col, const T* w,
+                     const T* g, int nrows, int nnz, int ng, T* sacc, hipStream_t s);
+
 // default variant of launch_step_medium: 1 ("nt"), or env WAVE3D_MEDIUM_VARIANT = "plain" (0),
 // "r2" (2), "r2nt" (3) for ablation
 int medium_variant();

@@ -156,6 +156,17 @@ def ricker(f0: float, t0: float, K: int, tau: float) -> torch.Tensor:
     return (1 - 2 * a) * torch.exp(-a)
 
 
+def grid_position(problem: MediumProblem, xyz) -> torch.Tensor:
+    """Physical coordinates ``(x, y, z)`` (``[3]`` or ``[count, 3]``) as the fractional node coordinates
+    ``(x / hx, y / hy, z / hz)`` that ``MediumSolver(source_positions=..., receiver_positions=...)`` takes
+    (float64; h = L / N per axis)."""
+    p = torch.as_tensor(xyz, dtype=torch.float64)
+    if p.shape[-1:] != (3,) or p.dim() > 2:
+        raise ValueError(f"xyz must have shape [3] or [count, 3], not {tuple(p.shape)}")
+    h = torch.tensor([v / problem.N for v in problem.lengths()], dtype=torch.float64)
+    return p / h
+
+
 def sponge_taper(problem: MediumProblem, width: int, sigma_max: float | None = None, power: float = 2,
                  reflection: float = 0.02, axes: str = "xyz"):
     """Per-axis factors ``(gx, gy, gz)`` of an absorbing sponge layer for :class:`MediumSolver`.
@@ -219,16 +230,40 @@ class MediumSolver:
                 step becomes ``u = G ((2 u1 - G u2) + m lap u1)``; the source term is not damped in
                 its own step. gx[0] must equal gx[N] (one periodic plane).
 
+    source_positions / receiver_positions
+                off-grid points in place of ``sources`` / ``receivers`` (each side exclusive with its
+                node list): ``[S, 3]`` / ``[R, 3]`` fractional node coordinates (xi, eta, zeta) = (x / hx,
+                y / hy, z / hz) (:func:`grid_position`), ``0 <= xi <= N``; a source needs ``0 < eta, zeta < N``,
+                a receiver ``0 <= eta, zeta <= N``; needs N >= 8. Two sources may share a position. A
+                point acts through 8 x 8 x 8 nodes (``ops.reference.interp_tables``): periodic wrap in x,
+                odd reflection at the y/z faces, and a position on a node is that node alone, so
+                integer positions reproduce the node lists. The wavelet stays ``[timesteps, S]``.
+    interp      "sinc8" (8-point Kaiser-windowed sinc, b = 6.31; the default) or "linear"
+
     With ``problem.density`` every step, forward, recomputed and adjoint, uses the density operator;
     the source term stays ``m g`` with ``m = rho c^2 tau^2``, so f is a rate of volume injection.
     """
 
     def __init__(self, problem: MediumProblem, backend: str = "hip", *, u0=None, sources=(), wavelet=None,
                  receivers=(), check_every: int = 0, device: int | None = None, variant: str | None = None,
-                 taper=None):
+                 taper=None, source_positions=None, receiver_positions=None, interp: str = "sinc8"):
+        from ..ops import reference
+
         if backend not in ("hip", "cpu"):
             raise ValueError(f"unknown backend {backend!r}")
         N, K = problem.N, problem.timesteps
+        if interp not in reference.INTERP_KINDS:
+            raise ValueError(f"interp must be one of {reference.INTERP_KINDS}, not {interp!r}")
+        self.interp = interp
+        if source_positions is not None and len(sources):
+            raise ValueError("give sources or source_positions, not both")
+        if receiver_positions is not None and len(receivers):
+            raise ValueError("give receivers or receiver_positions, not both")
+        self.source_positions = self.receiver_positions = None
+        if source_positions is not None and len(source_positions):
+            self.source_positions = reference.check_positions(source_positions, N, "source")
+        if receiver_positions is not None and len(receiver_positions):
+            self.receiver_positions = reference.check_positions(receiver_positions, N, "receiver")
         self.problem, self.backend, self.check_every, self.device = problem, backend, int(check_every), device
         self.variant = variant
         self.sources = [tuple(int(v) for v in s) for s in sources]
@@ -246,12 +281,14 @@ class MediumSolver:
         for r in self.receivers:
             if len(r) != 3 or not all(0 <= v <= N for v in r):
                 raise ValueError(f"receiver {r} outside the grid 0..{N}")
-        if self.sources:
+        self.nsrc = len(self.sources) if self.source_positions is None else int(self.source_positions.shape[0])
+        self.nrec = len(self.receivers) if self.receiver_positions is None else int(self.receiver_positions.shape[0])
+        if self.nsrc:
             if wavelet is None:
                 raise ValueError("sources need a wavelet of shape [timesteps, len(sources)]")
             w = torch.as_tensor(wavelet, dtype=torch.float64)
-            if tuple(w.shape) != (K, len(self.sources)):
-                raise ValueError(f"wavelet must have shape {(K, len(self.sources))} (timesteps x sources), "
+            if tuple(w.shape) != (K, self.nsrc):
+                raise ValueError(f"wavelet must have shape {(K, self.nsrc)} (timesteps x sources), "
                                  f"not {tuple(w.shape)}")
             self.wavelet = w
         else:
@@ -295,6 +332,18 @@ class MediumSolver:
         kw = {} if order == 2 else dict(order=order, mirror=(0, N, 0, N))
         return M, box, tuple(wrap), kw
 
+    def _points_kw(self) -> dict:
+        """The source / receiver keywords of the ``ops.reference`` oracles."""
+        return dict(sources=self.sources, receivers=self.receivers, source_positions=self.source_positions,
+                    receiver_positions=self.receiver_positions, interp=self.interp)
+
+    def _points_extra(self, **counts) -> dict:
+        """``extra`` entries of a run with positions (none without): the interpolation and the row and
+        entry counts given."""
+        if self.source_positions is None and self.receiver_positions is None:
+            return {}
+        return dict(interp=self.interp, **counts)
+
     def run(self) -> MediumResult:
         return self._run_cpu() if self.backend == "cpu" else self._run_hip()
 
@@ -311,12 +360,13 @@ class MediumSolver:
 
         p = self.problem
         t0 = time.perf_counter()
-        tr, uf, mx = reference.solve_medium(p.N, p.timesteps, p.speed2, u0=self.u0, sources=self.sources,
-                                            wavelet=self.wavelet, receivers=self.receivers,
+        tr, uf, mx = reference.solve_medium(p.N, p.timesteps, p.speed2, u0=self.u0, wavelet=self.wavelet,
                                             L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
-                                            taper=self.taper, order=p.space_order, density=p.density)
+                                            taper=self.taper, order=p.space_order, density=p.density,
+                                            **self._points_kw())
         return self._result(tr, uf, mx, (time.perf_counter() - t0) * 1e3,
-                            extra=dict(space_order=p.space_order, density=p.density is not None))
+                            extra=dict(space_order=p.space_order, density=p.density is not None,
+                                       **self._points_extra()))
 
     def _run_hip(self) -> MediumResult:
         from ..ops import kernels, reference
@@ -329,14 +379,14 @@ class MediumSolver:
             lv = [s.level() for _ in range(3)]
             m = s.level()
             s.medium(m, lv[0])
-            step_kw, taper, g, src, rec = s.step_kw, s.taper, s.g, s.src, s.rec
+            step_kw, taper, g = s.step_kw, s.taper, s.g
             if self.u0 is not None:
                 lv[0][M:N + 1 + M] = self.u0.to(dt).to(dev)
                 reference._wrap_x(lv[0], N, M)
-            traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
+            traces = torch.zeros(K + 1, self.nrec, dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
             mx0 = reference.max_abs_field(lv[0][M:N + 1 + M, 1:N, 1:N])
-            kernels.record(lv[0], rec, traces[0])
+            s.record(lv[0], traces[0])
             abort = {}
             done = K
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -350,8 +400,8 @@ class MediumSolver:
                     u[:, :, N] = 0
                 kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=stat[3 * n:3 * n + 3],
                                     stat_i=(M, N + M), wrap=wrap, variant=self.variant, taper=taper, **step_kw)
-                kernels.inject(u, m, src, g[n - 1], wrap)
-                kernels.record(u, rec, traces[n])
+                s.inject(u, m, g[n - 1])
+                s.record(u, traces[n])
                 if self.check_every > 0 and n % self.check_every == 0:
                     bad = _nonfinite_layer(stat, n)  # one read-back: the flags of layers 0..n
                     if bad is not None:
@@ -363,7 +413,7 @@ class MediumSolver:
             ms = ev0.elapsed_time(ev1)
             dec = kernels.decode_err(stat)  # the one read-back of the statistics
             mx = [mx0] + [dec[n][0] for n in range(1, done + 1)]
-            extra = dict(space_order=p.space_order, density=p.density is not None)
+            extra = dict(space_order=p.space_order, density=p.density is not None, **s.points_extra())
             if not abort and any(d[2] for d in dec[1:]):  # ran to the end, but not on finite values
                 extra["nonfinite_layer"] = next(n for n in range(1, K + 1) if dec[n][2])
             uf = lv[done % 3][M:N + 1 + M].cpu()
@@ -417,11 +467,11 @@ class MediumSolver:
         K = p.timesteps
         if self.u0 is not None:
             raise ValueError("gradient() starts from rest: u0 is not supported")
-        if not self.receivers:
+        if not self.nrec:
             raise ValueError("gradient() needs at least one receiver")
         obs = torch.as_tensor(observed)
-        if tuple(obs.shape) != (K + 1, len(self.receivers)):
-            raise ValueError(f"observed must have shape {(K + 1, len(self.receivers))} (timesteps + 1 x receivers), "
+        if tuple(obs.shape) != (K + 1, self.nrec):
+            raise ValueError(f"observed must have shape {(K + 1, self.nrec)} (timesteps + 1 x receivers), "
                              f"not {tuple(obs.shape)}")
         if segment is not None and int(segment) < 1:
             raise ValueError(f"segment must be >= 1 step, not {segment}")
@@ -446,9 +496,9 @@ class MediumSolver:
         t0 = time.perf_counter()
         fn = reference.gradient_medium_density if wrt_density else reference.gradient_medium
         kw = dict(illumination=True) if illumination else {}
-        J, gs, gw, tr, *more = fn(p.N, p.timesteps, p.speed2, obs, sources=self.sources, wavelet=self.wavelet,
-                                  receivers=self.receivers, taper=self.taper, L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi,
-                                  dtype=p.torch_dtype, order=p.space_order, density=p.density, **kw)
+        J, gs, gw, tr, *more = fn(p.N, p.timesteps, p.speed2, obs, wavelet=self.wavelet, taper=self.taper,
+                                  L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype, order=p.space_order,
+                                  density=p.density, **self._points_kw(), **kw)
         il, ph = more[-2:] if illumination else (None, None)
         return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr,
                               total_ms=(time.perf_counter() - t0) * 1e3,
@@ -456,7 +506,7 @@ class MediumSolver:
                               pseudo_hessian_speed2=ph,
                               extra=dict(segment=None, levels=None, recomputed_steps=0, space_order=p.space_order,
                                          density=p.density is not None, wrt_density=wrt_density,
-                                         illumination=illumination))
+                                         illumination=illumination, **self._points_extra()))
 
     def _gradient_hip(self, obs, segment, wrt_density: bool = False, illumination: bool = False) -> "MediumGradient":
         import time
@@ -492,8 +542,8 @@ class MediumSolver:
             hl = level() if illumination else None  # h = sum q^n q^n, added to by the forward pass proper alone
             ck = [(level(), level()) for _ in segs[:-1]]
             mc = s.medium(m, lv[0])
-            step_kw, tt, taper, gsrc, g, src, rec = s.step_kw, s.tt, s.taper, s.gsrc, s.g, s.src, s.rec
-            traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
+            step_kw, tt, taper, gsrc, g = s.step_kw, s.tt, s.taper, s.gsrc, s.g
+            traces = torch.zeros(K + 1, self.nrec, dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
             scratch = kernels.new_err(1, device=dev)  # statistics of the recomputed steps (those of `stat` again)
 
@@ -506,14 +556,14 @@ class MediumSolver:
                 kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=slot, stat_i=(M, N + M), wrap=wrap,
                                     variant=None if save is not None else self.variant, taper=taper, lap_out=save,
                                     illum=illum, **step_kw)
-                kernels.inject(u, m, src, g[n - 1], wrap)
+                s.inject(u, m, g[n - 1])
 
             # forward pass: run()'s steps; checkpoints before the segments, q of the last segment
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             ev[0].record()
-            kernels.record(lv[0], rec, traces[0])
+            s.record(lv[0], traces[0])
             forward_step(1, stat[3:6], None)
-            kernels.record(lv[1], rec, traces[1])
+            s.record(lv[1], traces[1])
             for si, (a, b) in enumerate(segs):
                 last = si == len(segs) - 1
                 if not last:
@@ -523,26 +573,22 @@ class MediumSolver:
                     keep_level(a - 1, a)
                 for n in range(a, b + 1):
                     forward_step(n, stat[3 * n:3 * n + 3], qb[n - a] if last else None, hl)
-                    kernels.record(lv[n % 3], rec, traces[n])
+                    s.record(lv[n % 3], traces[n])
                     if last and n < b:
                         keep_level(n, a)
             ev[1].record()
             _require_finite(stat, "gradient()", "forward pass")
             tr = traces.cpu()
             J, res = reference.misfit_medium(tr, obs)
-            anodes, atab = reference.adjoint_source_table(res, self.receivers, N, tt, M)
-            adj = kernels.source_nodes(anodes, lv[0])
-            ag = atab.to(dev)
-            snodes = kernels.receiver_nodes(reference.source_unique_nodes(self.sources, N, M), lv[0])
-            a_dev = torch.zeros(K, len(snodes), dtype=dt, device=dev)
+            finish_level = s.adjoint_points(res, lv[0], m)  # injects G rho^n, samples mu^n at the sources
+            a_dev = torch.zeros(K, self.nsrc, dtype=dt, device=dev)
             astat = kernels.new_err(K + 1, device=dev)
 
             # reverse pass: mu^K into zero levels, then mu^n for n = K-1 .. 1, level mu^n in ad[n % 3]
             ev[2].record()
             ad[(K + 1) % 3].zero_()
             ad[K % 3].zero_()
-            kernels.inject(ad[K % 3], m, adj, ag[K], wrap)
-            kernels.record(ad[K % 3], snodes, a_dev[K - 1])
+            finish_level(ad[K % 3], K, a_dev[K - 1])
             recomputed = 0
             for si in range(len(segs) - 1, -1, -1):
                 a, b = segs[si]
@@ -560,19 +606,19 @@ class MediumSolver:
                     kernels.step_medium(u1, u2, m, u, box, first=False, h2=h2, stat=astat[3 * n:3 * n + 3],
                                         stat_i=(M, N + M), wrap=wrap, taper=taper, image=(qb[n + 1 - a], acc),
                                         **step_kw)
-                    kernels.inject(u, m, adj, ag[n], wrap)
-                    kernels.record(u, snodes, a_dev[n - 1])
+                    finish_level(u, n, a_dev[n - 1])
                     if wrt_density:  # u1 = mu^{n+1}, injected and wrapped; its level is reused two steps on
                         kernels.face_correlation(u1, ub[n - (a - 1)], accb, box, h2=h2)
             ev[3].record()
             _require_finite(astat, "gradient()", "adjoint pass")
             acc_c, a_c = acc.cpu(), a_dev.cpu()
+            srows = s.source_rows_host()  # off-grid sources: (rows, the time sums of rows_dot)
             gs, gw = reference.finish_gradient_medium(acc_c, a_c, gsrc, mc, tt, self.sources, N, c["tau"],
-                                                      c["hx"], c["hy"], c["hz"], M, p.density)
+                                                      c["hx"], c["hy"], c["hz"], M, p.density, srows)
             gd = None
             if wrt_density:
                 gd = reference.finish_gradient_density(acc_c, accb.cpu(), a_c, gsrc, mc, tt, self.sources, N,
-                                                       c["tau"], p.speed2, p.density, M)
+                                                       c["tau"], p.speed2, p.density, M, srows)
             il = ph = None
             if illumination:
                 il, ph = reference.finish_illumination(hl.cpu(), tt, N, c["tau"], M, p.density)
@@ -583,7 +629,8 @@ class MediumSolver:
                                   extra=dict(segment=segment, levels=nlev, recomputed_steps=recomputed,
                                              space_order=p.space_order, density=p.density is not None,
                                              wrt_density=wrt_density, illumination=illumination,
-                                             forward_ms=ev[0].elapsed_time(ev[1]), reverse_ms=ev[2].elapsed_time(ev[3])))
+                                             forward_ms=ev[0].elapsed_time(ev[1]), reverse_ms=ev[2].elapsed_time(ev[3]),
+                                             **s.points_extra()))
 
 
     # ---- Born (linearised) modelling and Gauss-Newton products -------------------------------
@@ -617,7 +664,7 @@ class MediumSolver:
         N, K = p.N, p.timesteps
         if self.u0 is not None:
             raise ValueError("born() starts from rest: u0 is not supported")
-        if not self.receivers:
+        if not self.nrec:
             raise ValueError("born() needs at least one receiver")
         if dspeed2 is None and dwavelet is None and ddensity is None:
             raise ValueError("born() needs a perturbation: dspeed2, dwavelet, ddensity or any of them together")
@@ -628,11 +675,11 @@ class MediumSolver:
         dr = None if ddensity is None else reference.perturbation_field(ddensity, N, "ddensity")
         dw = None
         if dwavelet is not None:
-            if not self.sources:
+            if not self.nsrc:
                 raise ValueError("dwavelet needs sources")
             dw = torch.as_tensor(dwavelet, dtype=torch.float64).detach().cpu()
-            if tuple(dw.shape) != (K, len(self.sources)):
-                raise ValueError(f"dwavelet must have shape {(K, len(self.sources))} (timesteps x sources), "
+            if tuple(dw.shape) != (K, self.nsrc):
+                raise ValueError(f"dwavelet must have shape {(K, self.nsrc)} (timesteps x sources), "
                                  f"not {tuple(dw.shape)}")
             if not bool(torch.isfinite(dw).all()):
                 raise ValueError("dwavelet must be finite")
@@ -645,14 +692,14 @@ class MediumSolver:
 
         p = self.problem
         t0 = time.perf_counter()
-        tr, dtr, duf, mx = reference.born_medium(p.N, p.timesteps, p.speed2, ds, dw, sources=self.sources,
-                                                 wavelet=self.wavelet, receivers=self.receivers, taper=self.taper,
-                                                 L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
-                                                 order=p.space_order, density=p.density, ddensity=dr)
+        tr, dtr, duf, mx = reference.born_medium(p.N, p.timesteps, p.speed2, ds, dw, wavelet=self.wavelet,
+                                                 taper=self.taper, L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi,
+                                                 dtype=p.torch_dtype, order=p.space_order, density=p.density,
+                                                 ddensity=dr, **self._points_kw())
         return MediumBorn(traces=tr, dtraces=dtr, du_final=duf, max_abs_du=mx,
                           total_ms=(time.perf_counter() - t0) * 1e3,
                           extra=dict(levels=None, space_order=p.space_order, density=p.density is not None,
-                                     ddensity=dr is not None))
+                                     ddensity=dr is not None, **self._points_extra()))
 
     def _born_hip(self, ds, dw, dr=None) -> "MediumBorn":
         import time
@@ -672,7 +719,7 @@ class MediumSolver:
             m, dm, q = level(), level(), level()  # with ddensity, q holds s = dm q + m D_db u instead
             db = None if dr is None else level()
             s.medium(m, lv[0], dwavelet=dw)
-            step_kw, taper, g, dg, src, rec = s.step_kw, s.taper, s.g, s.dg, s.src, s.rec
+            step_kw, taper, g, dg = s.step_kw, s.taper, s.g, s.dg
             if ds is not None:  # None: dm = 0, the scattering term adds zeros
                 dm.copy_(reference.medium_coefficient(ds, c["tau"], N, dt, M, p.density))
             if dr is not None:  # born_medium's dm and db
@@ -681,8 +728,8 @@ class MediumSolver:
                     dmr = reference.medium_coefficient(ds, c["tau"], N, dt, M, p.density) + dmr
                 dm.copy_(dmr)
                 db.copy_(reference.dbuoyancy_field(dr, p.density, N, dt, M))
-            traces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
-            dtraces = torch.zeros(K + 1, len(rec), dtype=dt, device=dev)
+            traces = torch.zeros(K + 1, self.nrec, dtype=dt, device=dev)
+            dtraces = torch.zeros(K + 1, self.nrec, dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
             dstat = kernels.new_err(K + 1, device=dev)
             common = dict(h2=h2, stat_i=(M, N + M), wrap=wrap, taper=taper, **step_kw)
@@ -702,15 +749,15 @@ class MediumSolver:
                     save, read = dict(scatter=(q, dm, db)), dict(born_add=q)
                 kernels.step_medium(u1, u2, m, u, box, first=first, stat=stat[3 * n:3 * n + 3],
                                     variant=self.variant if first else None, **save, **common)
-                kernels.inject(u, m, src, g[n - 1], wrap)
+                s.inject(u, m, g[n - 1])
                 # the step of du with the scattering term, then the perturbed source terms
                 kernels.step_medium(d1, d2, m, d, box, first=first, stat=dstat[3 * n:3 * n + 3],
                                     variant=self.variant if first else None, **read, **common)
-                kernels.inject(d, dm, src, g[n - 1], wrap)
+                s.inject(d, dm, g[n - 1])
                 if dg is not None:
-                    kernels.inject(d, m, src, dg[n - 1], wrap)
-                kernels.record(u, rec, traces[n])
-                kernels.record(d, rec, dtraces[n])
+                    s.inject(d, m, dg[n - 1])
+                s.record(u, traces[n])
+                s.record(d, dtraces[n])
             ev1.record()
             ev1.synchronize()
             _require_finite(stat, "born()", "background field")
@@ -722,7 +769,8 @@ class MediumSolver:
             return MediumBorn(traces=tr, dtraces=dtr, du_final=duf, max_abs_du=mx,
                               total_ms=(time.perf_counter() - t0) * 1e3,
                               extra=dict(levels=nlev, space_order=p.space_order, density=p.density is not None,
-                                         ddensity=dr is not None, loop_ms=ev0.elapsed_time(ev1)))
+                                         ddensity=dr is not None, loop_ms=ev0.elapsed_time(ev1),
+                                         **s.points_extra()))
 
     def gauss_newton(self, dspeed2=None, dwavelet=None, ddensity=None, *, segment: int | None = None,
                      wrt_density: bool | None = None, illumination: bool = False) -> "MediumGradient":
@@ -787,7 +835,9 @@ class _HipSetup:
         ``taper`` on the device, None without a sponge), the source entries, the source table of the
         wavelet (``gsrc`` on the host, ``g`` its columns on the device, one per storage node; ``dg``
         those of ``dwavelet``) and the source and receiver nodes ``src`` / ``rec`` in the strides of
-        the level ``lv0``."""
+        the level ``lv0``. With positions the tables stay compact, ``g`` ``[K, S]``, and ``src_rows`` (the CSR
+        row list of the sources) / ``rec_tab`` (the receivers' gather tables) take the node lists' place;
+        :meth:`inject` and :meth:`record` dispatch on them."""
         from ..ops import kernels, reference
 
         sv, c, M, dev = self.solver, self.c, self.M, self.dev
@@ -801,18 +851,92 @@ class _HipSetup:
             self.step_kw = dict(self.step_kw, buoyancy=bu)
         self.tt = None if sv.taper is None else reference.taper_tables(sv.taper, N, dt, M)
         self.taper = None if self.tt is None else tuple(t.to(dev) for t in self.tt)
-        ent = reference.source_entries(sv.sources, N, M)
-        cols = [s for _, s in ent]  # one column per storage node
-
         def table(w):
-            return reference.source_table(w, K, len(sv.sources), c["hx"], c["hy"], c["hz"], dt)
+            return reference.source_table(w, K, sv.nsrc, c["hx"], c["hy"], c["hz"], dt)
 
         self.gsrc = table(sv.wavelet)
-        self.g = self.gsrc[:, cols].contiguous().to(dev)
-        self.dg = None if dwavelet is None else table(dwavelet)[:, cols].contiguous().to(dev)
-        self.src = kernels.source_nodes([nd for nd, _ in ent], lv0)
-        self.rec = kernels.receiver_nodes([(i + M, j, k) for i, j, k in sv.receivers], lv0)
+        self.src = self.rec = self.src_rows = self.rec_tab = self.host_rows = None
+        self.counts = {}
+        if sv.source_positions is None:
+            ent = reference.source_entries(sv.sources, N, M)
+            cols = [s for _, s in ent]  # one column per storage node
+            self.g = self.gsrc[:, cols].contiguous().to(dev)
+            self.dg = None if dwavelet is None else table(dwavelet)[:, cols].contiguous().to(dev)
+            self.src = kernels.source_nodes([nd for nd, _ in ent], lv0)
+        else:  # the compact [K, S] tables; the rows carry the weights
+            self.host_rows = reference.point_rows(sv.source_positions, N, dt, sv.interp, M)
+            self.src_rows = kernels.row_list(self.host_rows, lv0)
+            self.g = self.gsrc.contiguous().to(dev)
+            self.dg = None if dwavelet is None else table(dwavelet).contiguous().to(dev)
+            self.counts.update(source_rows=len(self.host_rows), source_entries=self.host_rows.entries)
+        if sv.receiver_positions is None:
+            self.rec = kernels.receiver_nodes([(i + M, j, k) for i, j, k in sv.receivers], lv0)
+        else:
+            self.rec_tab = kernels.point_tables(*reference.receiver_tables(sv.receiver_positions, N, dt, sv.interp, M),
+                                                lv0)
         return mc
+
+    def inject(self, u, m, g) -> None:
+        """The source terms of one step into ``u``: ``g`` = the step's row of ``self.g`` / ``self.dg``."""
+        from ..ops import kernels
+
+        if self.src_rows is not None:
+            kernels.inject_rows(u, m, self.src_rows, g, self.wrap)
+        else:
+            kernels.inject(u, m, self.src, g, self.wrap)
+
+    def record(self, u, out) -> None:
+        from ..ops import kernels
+
+        if self.rec_tab is not None:
+            kernels.record_weighted(u, self.rec_tab, out)
+        else:
+            kernels.record(u, self.rec, out)
+
+    def points_extra(self) -> dict:
+        return self.solver._points_extra(**self.counts)
+
+    def adjoint_points(self, res, lv0, m):
+        """The adjoint pass's end of a level for the residuals ``res`` ``[K+1, R]`` (host): returns
+        ``finish_level(mu, n, a_row)``, which injects ``G rho^n`` into the stepped level mu^n (wrap copies
+        included) and samples it at the sources into ``a_row``; with off-grid sources it also adds
+        ``mu^n[p] val_p(g[n-1])`` to the time sums of the unique source rows (:meth:`source_rows_host`)."""
+        from ..ops import kernels, reference
+
+        sv, M, dev, wrap = self.solver, self.M, self.dev, self.wrap
+        N, dt = sv.problem.N, sv.problem.torch_dtype
+        if sv.receiver_positions is None:
+            anodes, atab = reference.adjoint_source_table(res, sv.receivers, N, self.tt, M)
+            adj, ag = kernels.source_nodes(anodes, lv0), atab.to(dev)
+            inject = lambda mu, n: kernels.inject(mu, m, adj, ag[n], wrap)  # noqa: E731
+        else:  # the compact [K+1, R] residual table; the rows' weights carry G
+            arows = reference.point_rows(sv.receiver_positions, N, dt, sv.interp, M, self.tt)
+            adj, ag = kernels.row_list(arows, lv0), res.contiguous().to(dev)
+            self.counts.update(receiver_rows=len(arows), receiver_entries=arows.entries)
+            inject = lambda mu, n: kernels.inject_rows(mu, m, adj, ag[n], wrap)  # noqa: E731
+        self.sacc = None
+        if sv.source_positions is None:
+            snodes = kernels.receiver_nodes(reference.source_unique_nodes(sv.sources, N, M), lv0)
+            sample = lambda mu, n, a_row: kernels.record(mu, snodes, a_row)  # noqa: E731
+        else:
+            gtab = kernels.point_tables(*reference.receiver_tables(sv.source_positions, N, dt, sv.interp, M,
+                                                                   over_taper=self.tt), lv0)
+            self.sacc = torch.zeros(self.src_rows.unique, dtype=dt, device=dev)
+
+            def sample(mu, n, a_row):
+                kernels.record_weighted(mu, gtab, a_row)
+                kernels.rows_dot(mu, self.src_rows, self.g[n - 1], self.sacc)
+
+        def finish_level(mu, n, a_row):
+            inject(mu, n)
+            sample(mu, n, a_row)
+
+        return finish_level
+
+    def source_rows_host(self):
+        """(rows, sacc) for ``ops.reference.finish_gradient_medium`` after the adjoint pass, None with a
+        node list of sources."""
+        return None if self.sacc is None else (self.host_rows, self.sacc.cpu())
 
 
 def _nonfinite_layer(stat, upto: int | None = None):

@@ -5,7 +5,8 @@ device; they are passed to the native kernels as raw pointers on torch's current
 Shapes are validated here *before* any launch (the kernels index with the boxes given).
 The solver itself uses an aligned, padded layout (``csrc/hip_kernels.hpp``); these entry
 points use pitch = nz, which the kernels accept as well; the medium ops (``step_medium``,
-``face_correlation``, ``inject``, ``record``) also take views in that padded layout (``alloc_level``).
+``face_correlation``, ``inject``, ``record``, ``inject_rows``, ``record_weighted``, ``rows_dot``) also take
+views in that padded layout (``alloc_level``).
 """
 from __future__ import annotations
 
@@ -628,3 +629,167 @@ def record(u, nodes, out) -> None:
     if len(nl) == 0:
         return
     getattr(_C(), "k_record_" + _sfx(u))(u.data_ptr(), gv, nl.dev.data_ptr(), out.data_ptr(), len(nl), _stream())
+
+
+# ---- off-grid sources and receivers (csrc/hip_medium_points.hip) ---------------------------
+
+class PointTables:
+    """Validated gather tables of :func:`record_weighted`, uploaded once: ``index`` int ``[R, 3, 8]``
+    (x, y, z slots, storage indices of the grid ``shape``) and ``weight`` ``[R, 3, 8]`` of ``dtype``
+    (``ops.reference.receiver_tables`` builds them). Every index must lie inside the storage."""
+
+    def __init__(self, index, weight, shape, device, dtype):
+        nx, ny, nz = (int(v) for v in shape)
+        if not isinstance(index, torch.Tensor) or not isinstance(weight, torch.Tensor):
+            raise ValueError("index and weight must be tensors")
+        if index.dtype not in (torch.int32, torch.int64) or index.dim() != 3 or tuple(index.shape[1:]) != (3, 8):
+            raise ValueError(f"index must be an integer [R, 3, 8] tensor, not {index.dtype} {tuple(index.shape)}")
+        if weight.dtype != dtype or tuple(weight.shape) != tuple(index.shape):
+            raise ValueError(f"weight must be a {dtype} tensor of shape {tuple(index.shape)}, not {weight.dtype} "
+                             f"{tuple(weight.shape)}")
+        ic = index.detach().cpu().long()
+        for axis, n in enumerate((nx, ny, nz)):
+            bad = (ic[:, axis] < 0) | (ic[:, axis] >= n)
+            if bool(bad.any()):
+                r = int(bad.any(1).nonzero()[0])
+                raise ValueError(f"receiver {r}: index outside the storage of a {nx}x{ny}x{nz} grid on axis {axis}")
+        if not bool(torch.isfinite(weight).all()):
+            raise ValueError("weights must be finite")
+        self.shape, self.dtype, self.n = (nx, ny, nz), dtype, int(index.shape[0])
+        self.index = ic.to(torch.int32).contiguous().to(device)
+        self.weight = weight.detach().contiguous().to(device)
+        self.device = self.index.device
+
+    def __len__(self):
+        return self.n
+
+
+class RowList:
+    """A validated CSR list of touched nodes for :func:`inject_rows` / :func:`rows_dot`, uploaded once
+    (``ops.reference.point_rows`` builds it): ``nodes`` ``[rows, 3]`` distinct storage nodes inside the
+    owned region of the grid ``shape``, ``rowptr`` ``[rows + 1]`` non-decreasing from 0 to the number
+    of entries, per entry a column ``col`` in 0 .. ``ncols`` - 1 and a weight ``w`` of ``dtype``.
+    ``unique``: the leading rows :func:`rows_dot` runs on (the rest are plane-N duplicates)."""
+
+    def __init__(self, nodes, rowptr, col, w, *, ncols: int, unique: int | None, shape, device, dtype):
+        nx, ny, nz = (int(v) for v in shape)
+        for t, name in ((nodes, "nodes"), (rowptr, "rowptr"), (col, "col")):
+            if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{name} must be an integer tensor")
+        if nodes.dim() != 2 or nodes.shape[1] != 3:
+            raise ValueError(f"nodes must have shape [rows, 3], not {tuple(nodes.shape)}")
+        nrows = int(nodes.shape[0])
+        if rowptr.dim() != 1 or rowptr.numel() != nrows + 1:
+            raise ValueError(f"rowptr must have {nrows + 1} values, not shape {tuple(rowptr.shape)}")
+        if not isinstance(w, torch.Tensor) or w.dtype != dtype or w.dim() != 1 or col.dim() != 1 \
+                or w.numel() != col.numel():
+            raise ValueError(f"col and w must be 1-D with one value per entry, w of {dtype}")
+        nnz = int(col.numel())
+        nc, pc, cc = nodes.detach().cpu().long(), rowptr.detach().cpu().long(), col.detach().cpu().long()
+        for axis, n in enumerate((nx, ny, nz)):
+            bad = (nc[:, axis] < 1) | (nc[:, axis] > n - 2)
+            if bool(bad.any()):
+                nd = tuple(int(v) for v in nc[int(bad.nonzero()[0])])
+                raise ValueError(f"row node {nd} outside the owned region of a {nx}x{ny}x{nz} grid")
+        key = (nc[:, 0] * ny + nc[:, 1]) * nz + nc[:, 2]
+        if torch.unique(key).numel() != nrows:
+            raise ValueError("a node is named by more than one row")
+        if int(pc[0]) != 0 or int(pc[-1]) != nnz or bool((pc[1:] < pc[:-1]).any()):
+            raise ValueError(f"rowptr must not decrease and must run from 0 to the {nnz} entries")
+        ncols = int(ncols)
+        if nnz and (int(cc.min()) < 0 or int(cc.max()) >= ncols):
+            raise ValueError(f"col must lie in 0..{ncols - 1}")
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("weights must be finite")
+        unique = nrows if unique is None else int(unique)
+        if not 0 <= unique <= nrows:
+            raise ValueError(f"unique = {unique} outside 0..{nrows}")
+        self.shape, self.dtype, self.nrows, self.nnz, self.ncols, self.unique = (nx, ny, nz), dtype, nrows, nnz, ncols, unique
+        self.nodes = nc.to(torch.int32).contiguous().to(device)
+        self.rowptr = pc.to(torch.int32).contiguous().to(device)
+        self.col = cc.to(torch.int32).contiguous().to(device)
+        self.w = w.detach().contiguous().to(device)
+        self.device = self.nodes.device
+
+    def __len__(self):
+        return self.nrows
+
+
+def point_tables(index, weight, u) -> PointTables:
+    """Tables for :func:`record_weighted` in the storage of the grid ``u``."""
+    return PointTables(index, weight, u.shape, u.device, u.dtype)
+
+
+def row_list(rows, u) -> RowList:
+    """An ``ops.reference.PointRows`` list for :func:`inject_rows` / :func:`rows_dot` on the grid ``u``."""
+    return RowList(rows.nodes, rows.rowptr, rows.col, rows.w, ncols=rows.ncols, unique=rows.unique, shape=u.shape,
+                   device=u.device, dtype=u.dtype)
+
+
+def _check_points(t, u, cls, what: str):
+    if not isinstance(t, cls):
+        raise ValueError(f"{what} must be a {cls.__name__}")
+    if t.shape != tuple(u.shape) or t.dtype != u.dtype or t.device != u.device:
+        raise ValueError(f"{what} was built for another grid")
+    return t
+
+
+def _check_values(t, u, n: int, name: str):
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != u.device or t.dtype != u.dtype
+            or t.dim() != 1 or not t.is_contiguous() or t.numel() < n):
+        raise ValueError(f"{name} must be a contiguous 1-D {u.dtype} tensor of >= {n} values on {u.device}")
+
+
+def _check_apart(t, u, name: str):
+    u0, u1 = _grid_span(u)
+    t0, t1 = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+    if u0 < t1 and t0 < u1:
+        raise ValueError(f"{name} shares memory with u")
+
+
+def record_weighted(u, tables: PointTables, out) -> None:
+    """Off-grid receivers (``k_record_w``): ``out[r]`` = the weighted sum of ``u`` over the 8 x 8 x 8 slots
+    of receiver r, one wave per receiver, in the fixed order of ``ops.reference.record_weighted`` (fp64
+    and fp32 results are bitwise equal to it). ``tables``: :func:`point_tables`; ``out``: one value per
+    receiver, not sharing memory with ``u``. Every violation is a ``ValueError`` before any launch."""
+    gv = _check_grid_strided(u)
+    tb = _check_points(tables, u, PointTables, "tables")
+    _check_values(out, u, len(tb), "out")
+    _check_apart(out, u, "out")
+    if len(tb) == 0:
+        return
+    getattr(_C(), "k_record_w_" + _sfx(u))(u.data_ptr(), gv, tb.index.data_ptr(), tb.weight.data_ptr(),
+                                          out.data_ptr(), len(tb), _stream())
+
+
+def inject_rows(u, m, rows: RowList, g, wrap=None) -> None:
+    """Off-grid sources (``k_inject_rows``): per row (touched node) ``val = val + w[e] g[col[e]]`` over its
+    entries in order, then ``u[node] += m[node] val`` and the ghost-plane copy of a node on a wrap source
+    plane, like :func:`inject`. ``rows``: :func:`row_list`; ``g``: one value per column (one time row of
+    the compact ``[K, S]`` / ``[K+1, R]`` table). A single entry of weight 1 gives :func:`inject`'s bits."""
+    gv = _check_grid_strided(u, m)
+    rl = _check_points(rows, u, RowList, "rows")
+    _check_values(g, u, rl.ncols, "g")
+    _check_apart(g, u, "g")
+    w = _check_wrap(wrap, gv)
+    if len(rl) == 0:
+        return
+    getattr(_C(), "k_inject_rows_" + _sfx(u))(u.data_ptr(), m.data_ptr(), gv, rl.nodes.data_ptr(), rl.rowptr.data_ptr(),
+                                             rl.col.data_ptr(), rl.w.data_ptr(), g.data_ptr(), len(rl), rl.nnz,
+                                             rl.ncols, w, _stream())
+
+
+def rows_dot(u, rows: RowList, g, sacc) -> None:
+    """``sacc[row] += u[node] val`` with the ``val`` of :func:`inject_rows`, for the ``rows.unique`` leading
+    rows (``k_rows_dot``); nothing else is written. The per-node time sum behind the source term of
+    dJ/dm. ``sacc``: one value per unique row, not sharing memory with ``u``."""
+    gv = _check_grid_strided(u)
+    rl = _check_points(rows, u, RowList, "rows")
+    _check_values(g, u, rl.ncols, "g")
+    _check_values(sacc, u, rl.unique, "sacc")
+    _check_apart(sacc, u, "sacc")
+    if rl.unique == 0:
+        return
+    getattr(_C(), "k_rows_dot_" + _sfx(u))(u.data_ptr(), gv, rl.nodes.data_ptr(), rl.rowptr.data_ptr(),
+                                          rl.col.data_ptr(), rl.w.data_ptr(), g.data_ptr(), rl.unique, rl.nnz,
+                                          rl.ncols, sacc.data_ptr(), _stream())

@@ -515,9 +515,279 @@ def taper_tables(taper, N: int, dtype, ghost: int = 1) -> tuple[torch.Tensor, to
     return gx, out[1].contiguous(), out[2].contiguous()
 
 
+# ---- off-grid sources and receivers ------------------------------------------------------------
+#
+# A position is given in fractional node coordinates (xi, eta, zeta) = (x / hx, y / hy, z / hz) and acts
+# through 8 slots per axis: slot a is node floor(p) - 3 + a with the offset x = node - p and a weight
+# w(x). The slots carry the boundary conditions: in x the node is taken modulo N onto the unique planes
+# 0 .. N-1, in y and z a node beyond a face is reflected oddly (node -n -> n, node N + n -> N - n, the
+# weight negated; laplace_star's convention) and a node on a face gets the weight 0. A position on a
+# node gives a Kronecker delta, so the node lists are the special case. The tables below are built on
+# the host once, shared by the oracle and the HIP front-end (models/medium.py), and the oracle ops
+# (record_weighted, rows_values, inject_rows, rows_dot) have the kernels' arithmetic operation for
+# operation (csrc/hip_medium_points.hip).
+
+INTERP_KINDS = ("sinc8", "linear")
+SINC8_B = 6.31  # the Kaiser window's shape parameter for the 8-point sinc
+MIN_POSITION_N = 8
+
+
+def interp_weight(x, kind: str = "sinc8") -> torch.Tensor:
+    """The interpolation weight w(x) of a node at the offset ``x = node - position`` (float64).
+    "sinc8": ``sinc(x) I0(b sqrt(1 - (x / 4)^2)) / I0(b)`` with b = 6.31 for |x| < 4, 0 beyond, exactly
+    1 at x == 0 and exactly 0 at every other integer; "linear": ``max(0, 1 - |x|)``."""
+    x = torch.as_tensor(x, dtype=torch.float64)
+    if kind == "linear":
+        return (1 - x.abs()).clamp(min=0)
+    if kind != "sinc8":
+        raise ValueError(f"interp must be one of {INTERP_KINDS}, not {kind!r}")
+    b = torch.tensor(SINC8_B, dtype=torch.float64)
+    w = torch.sinc(x) * torch.special.i0(b * (1 - (x / 4) ** 2).clamp(min=0).sqrt()) / torch.special.i0(b)
+    w = torch.where(x.abs() >= 4, torch.zeros_like(w), w)
+    return torch.where(x == x.round(), (x == 0).to(torch.float64), w)
+
+
+def check_positions(positions, N: int, what: str) -> torch.Tensor:
+    """Positions as a float64 ``[P, 3]`` CPU tensor of fractional node coordinates, validated: finite,
+    ``0 <= xi <= N``; a "source" needs ``0 < eta, zeta < N`` (off the Dirichlet faces), a "receiver"
+    ``0 <= eta, zeta <= N``; N >= 8."""
+    p = torch.as_tensor(positions, dtype=torch.float64).detach().cpu()
+    if p.dim() == 1 and p.numel() == 3:
+        p = p.reshape(1, 3)
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"{what} positions must have shape [count, 3] (xi, eta, zeta), not {tuple(p.shape)}")
+    if N < MIN_POSITION_N:
+        raise ValueError(f"{what} positions need N >= {MIN_POSITION_N}, not N = {N}")
+    if not bool(torch.isfinite(p).all()):
+        raise ValueError(f"{what} positions must be finite")
+    for q in range(p.shape[0]):
+        xi, eta, zeta = (float(v) for v in p[q])
+        if not (0 <= xi <= N and 0 <= eta <= N and 0 <= zeta <= N):
+            raise ValueError(f"{what} position {(xi, eta, zeta)} outside the grid 0..{N}")
+        if what == "source" and not (0 < eta < N and 0 < zeta < N):
+            raise ValueError(f"source position {(xi, eta, zeta)} lies on a Dirichlet face")
+    return p
+
+
+def _axis_intervals(N) -> tuple[int, int, int]:
+    """N as (Nx, Ny, Nz): the solver's grids have one N; the kernels' tests also use other boxes."""
+    return (int(N),) * 3 if isinstance(N, int) else tuple(int(v) for v in N)
+
+
+def _interp_axes(pos: torch.Tensor, N, kind: str, ghost: int):
+    """The slots of ``[P, 3]`` positions: (ix, iy, iz) int64 ``[P, 8]`` storage indices and (wx, wy, wz)
+    float64 ``[P, 8]`` weights (see ``interp_tables``)."""
+    if kind not in INTERP_KINDS:
+        raise ValueError(f"interp must be one of {INTERP_KINDS}, not {kind!r}")
+    NN = _axis_intervals(N)
+    node = (torch.floor(pos).to(torch.int64) - 3)[:, :, None] + torch.arange(8)  # [P, 3, 8]
+    w = interp_weight(node.to(torch.float64) - pos[:, :, None], kind)
+    idx, wt = [torch.remainder(node[:, 0], NN[0]) + ghost], [w[:, 0]]
+    for axis in (1, 2):
+        N = NN[axis]
+        n, v = node[:, axis], w[:, axis]
+        lo, hi = n < 0, n > N
+        n = torch.where(lo, -n, torch.where(hi, 2 * N - n, n))
+        v = torch.where(lo | hi, -v, v)
+        v = torch.where((n == 0) | (n == N), torch.zeros_like(v), v)
+        idx.append(n)
+        wt.append(v)
+    return (*idx, *wt)
+
+
+def interp_tables(position, N, kind: str = "sinc8", ghost: int = 1):
+    """The 8-slot tables of one position (xi, eta, zeta) in fractional node coordinates: three int64
+    index tables ``ix, iy, iz`` (storage indices; local i = global + ``ghost`` in x) and three float64
+    weight tables ``wx, wy, wz``, 8 values each (``[P, 8]`` each for ``[P, 3]`` positions).
+
+    Slot a of an axis is node ``floor(p) - 3 + a`` with the weight ``interp_weight(node - p, kind)``.
+    x: the node modulo N, on the unique planes 0 .. N-1. y and z: a node n < 0 becomes -n and a node
+    n > N becomes 2N - n, the weight negated (odd reflection); a node that lands on 0 or N gets the
+    weight 0. Two slots may name the same node; they stay separate slots. ``N``: the intervals per axis,
+    one number or (Nx, Ny, Nz)."""
+    pos = torch.as_tensor(position, dtype=torch.float64)
+    single = pos.dim() == 1
+    out = _interp_axes(pos.reshape(-1, 3), N, kind, int(ghost))
+    return tuple(t[0] for t in out) if single else out
+
+
+def receiver_tables(positions, N, dtype, kind: str = "sinc8", ghost: int = 1, over_taper=None):
+    """The gather tables of ``record_weighted`` for ``[R, 3]`` positions: (index int32 ``[R, 3, 8]``,
+    weight ``[R, 3, 8]`` of ``dtype``; x, y, z slots). ``over_taper`` = the ``taper_tables``: every
+    weight is divided, in ``dtype``, by the per-axis sponge factor of its slot's node, so that the
+    gather returns ``sum W u / G`` with the separable G (the wavelet gradient's tables)."""
+    pos = torch.as_tensor(positions, dtype=torch.float64).reshape(-1, 3)
+    ix, iy, iz, wx, wy, wz = _interp_axes(pos, N, kind, ghost)
+    index = torch.stack([ix, iy, iz], 1).to(torch.int32).contiguous()
+    weight = torch.stack([wx, wy, wz], 1).to(dtype)
+    if over_taper is not None:
+        for axis, (t, i) in enumerate(zip(over_taper, (ix, iy, iz))):
+            weight[:, axis] = weight[:, axis] / t[i]
+    return index, weight.contiguous()
+
+
+class PointRows:
+    """A CSR list of the nodes a set of points touches: ``nodes`` int32 ``[rows, 3]`` storage nodes,
+    ``rowptr`` int32 ``[rows + 1]``, and per entry the point ``col`` (int32) and the weight ``w``.
+    ``unique``: the leading rows without the plane-N duplicates; ``ncols``: the number of points."""
+
+    def __init__(self, nodes, rowptr, col, w, unique: int, ncols: int):
+        self.nodes, self.rowptr, self.col, self.w = nodes, rowptr, col, w
+        self.unique, self.ncols = int(unique), int(ncols)
+        self._pad = None
+
+    def __len__(self):
+        return int(self.nodes.shape[0])
+
+    @property
+    def entries(self) -> int:
+        return int(self.col.numel())
+
+    def ijk(self):
+        n = self.nodes.long()
+        return n[:, 0], n[:, 1], n[:, 2]
+
+    def padded(self):
+        """(col, w, mask), each ``[rows, longest row]``: the entries of every row in order, padded."""
+        if self._pad is None:
+            ptr = self.rowptr.long()
+            cnt = ptr[1:] - ptr[:-1]
+            width = int(cnt.max()) if len(cnt) else 0
+            e = ptr[:-1, None] + torch.arange(width)[None, :]
+            mask = torch.arange(width)[None, :] < cnt[:, None]
+            e = torch.where(mask, e, torch.zeros_like(e))
+            if self.entries:
+                self._pad = (self.col.long()[e], self.w[e], mask)
+            else:
+                self._pad = (e, torch.zeros(e.shape, dtype=self.w.dtype), mask)
+        return self._pad
+
+
+def point_rows(positions, N, dtype, kind: str = "sinc8", ghost: int = 1, tt=None) -> PointRows:
+    """The row list of ``[P, 3]`` points (sources, or receivers acting as adjoint sources): all 8^3 slot
+    triples of each point with the weight ``(wx[a] wy[b]) wz[c]``, every factor cast to ``dtype`` first
+    and the products formed in it; entries whose weight is exactly 0 are dropped and the rest grouped
+    by storage node. Rows are sorted by (i, j, k), the entries of a row by point, then (a, b, c); entries
+    of one point that fold onto the same node stay separate. A row on the unique plane 0 is emitted for
+    both storage planes, ``ghost`` and ``N + ghost``, like ``source_entries``; these duplicates are the
+    last rows. ``tt`` = the ``taper_tables``: each weight is multiplied once more, in ``dtype``, by
+    ``taper_at(tt, node)`` (the ``G rho`` of ``adjoint_source_table``)."""
+    pos = torch.as_tensor(positions, dtype=torch.float64).reshape(-1, 3)
+    P = pos.shape[0]
+    ix, iy, iz, wx, wy, wz = _interp_axes(pos, N, kind, ghost)
+    wx, wy, wz = wx.to(dtype), wy.to(dtype), wz.to(dtype)
+    W = ((wx[:, :, None, None] * wy[:, None, :, None]) * wz[:, None, None, :]).reshape(-1)
+    full = (P, 8, 8, 8)
+    I = ix[:, :, None, None].expand(full).reshape(-1)
+    J = iy[:, None, :, None].expand(full).reshape(-1)
+    Kk = iz[:, None, None, :].expand(full).reshape(-1)
+    col = torch.arange(P)[:, None].expand(P, 512).reshape(-1)
+    keep = W != 0
+    W, I, J, Kk, col = W[keep], I[keep], J[keep], Kk[keep], col[keep]
+    if tt is not None:
+        W = W * (tt[0][I] * (tt[1][J] * tt[2][Kk]))
+    Nx, ny1, nz1 = (v + d for v, d in zip(_axis_intervals(N), (0, 1, 1)))
+    key, order = torch.sort((I * ny1 + J) * nz1 + Kk, stable=True)  # keeps (point, a, b, c) within a node
+    W, col = W[order], col[order]
+    rows, cnt = torch.unique_consecutive(key, return_counts=True)
+    nodes = torch.stack([rows // (ny1 * nz1), (rows // nz1) % ny1, rows % nz1], 1)
+    ptr = torch.zeros(len(rows) + 1, dtype=torch.int64)
+    ptr[1:] = torch.cumsum(cnt, 0)
+    unique = len(rows)
+    dup = (nodes[:, 0] == ghost).nonzero().flatten()  # the unique plane 0 acts on plane N too
+    if len(dup):
+        e = torch.cat([torch.arange(int(ptr[r]), int(ptr[r + 1])) for r in dup])
+        twin = nodes[dup].clone()
+        twin[:, 0] = Nx + ghost
+        nodes = torch.cat([nodes, twin])
+        ptr = torch.cat([ptr, ptr[-1] + torch.cumsum(cnt[dup], 0)])
+        W, col = torch.cat([W, W[e]]), torch.cat([col, col[e]])
+    return PointRows(nodes.to(torch.int32).contiguous(), ptr.to(torch.int32), col.to(torch.int32).contiguous(),
+                     W.contiguous(), unique, P)
+
+
+def record_weighted(u: torch.Tensor, index: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """The weighted gather of ``k_record_w``: ``[R]`` values from the ``receiver_tables``. Per receiver
+    and slot pair (a, b): ``s = s + wz[c] u[ix[a], iy[b], iz[c]]`` for c = 0 .. 7 from s = 0, then
+    ``t = (wx[a] wy[b]) s``; the 64 values, l = 8a + b, are summed by ``v = v[:h] + v[h:2h]`` for
+    h = 32, 16, 8, 4, 2, 1, the kernel's xor butterfly as lane 0 sees it."""
+    idx = index.long()
+    ix, iy, iz = idx[:, 0], idx[:, 1], idx[:, 2]
+    U = u[ix[:, :, None, None], iy[:, None, :, None], iz[:, None, None, :]]  # [R, 8, 8, 8]
+    wx, wy, wz = weight[:, 0], weight[:, 1], weight[:, 2]
+    s = torch.zeros(U.shape[:3], dtype=u.dtype, device=u.device)
+    for c in range(8):
+        s = s + wz[:, None, None, c] * U[:, :, :, c]
+    v = ((wx[:, :, None] * wy[:, None, :]) * s).reshape(-1, 64)
+    for h in (32, 16, 8, 4, 2, 1):
+        v = v[:, :h] + v[:, h:2 * h]
+    return v[:, 0]
+
+
+def rows_values(rows: PointRows, g: torch.Tensor) -> torch.Tensor:
+    """``val[row] = val + w[e] g[col[e]]`` over the entries of every row in order, from 0: the row loop
+    of ``k_inject_rows``. ``g``: one value per point."""
+    colp, wp, mask = rows.padded()
+    val = torch.zeros(len(rows), dtype=rows.w.dtype)
+    for e in range(colp.shape[1]):
+        val = torch.where(mask[:, e], val + wp[:, e] * g[colp[:, e]], val)
+    return val
+
+
+def inject_rows(u: torch.Tensor, m: torch.Tensor, rows: PointRows, g: torch.Tensor) -> None:
+    """``u[node] = u[node] + m[node] val`` at the nodes of ``rows`` (in place), val = ``rows_values``."""
+    if len(rows) == 0:
+        return
+    i, j, k = rows.ijk()
+    u[i, j, k] = u[i, j, k] + m[i, j, k] * rows_values(rows, g)
+
+
+def rows_dot(u: torch.Tensor, rows: PointRows, g: torch.Tensor, sacc: torch.Tensor) -> torch.Tensor:
+    """``sacc[row] + u[node] val`` over the unique rows (``k_rows_dot``); returns the new ``[unique]`` sums."""
+    n = rows.unique
+    i, j, k = rows.ijk()
+    return sacc[:n] + u[i[:n], j[:n], k[:n]] * rows_values(rows, g)[:n]
+
+
+class _Points:
+    """The sources and receivers of an oracle run, node lists or positions on either side."""
+
+    def __init__(self, N: int, M: int, dtype, sources, receivers, source_positions, receiver_positions, interp):
+        if source_positions is not None and len(sources):
+            raise ValueError("give sources or source_positions, not both")
+        if receiver_positions is not None and len(receivers):
+            raise ValueError("give receivers or receiver_positions, not both")
+        if interp not in INTERP_KINDS:
+            raise ValueError(f"interp must be one of {INTERP_KINDS}, not {interp!r}")
+        self.N, self.M, self.dtype, self.interp = N, M, dtype, interp
+        self.spos = None if source_positions is None else check_positions(source_positions, N, "source")
+        self.rpos = None if receiver_positions is None else check_positions(receiver_positions, N, "receiver")
+        self.sources, self.receivers = sources, receivers
+        self.ent = source_entries(sources, N, M) if self.spos is None else None
+        self.rows = None if self.spos is None else point_rows(self.spos, N, dtype, interp, M)
+        self.rec = [(i + M, j, k) for i, j, k in receivers] if self.rpos is None else None
+        self.rtab = None if self.rpos is None else receiver_tables(self.rpos, N, dtype, interp, M)
+        self.S = len(sources) if self.spos is None else int(self.spos.shape[0])
+        self.R = len(receivers) if self.rpos is None else int(self.rpos.shape[0])
+
+    def inject(self, u, m, g) -> None:
+        """The source terms of one step: ``g`` = the step's row of the source table."""
+        if self.rows is not None:
+            inject_rows(u, m, self.rows, g)
+            return
+        for nd, s in self.ent:
+            u[nd] = u[nd] + m[nd] * g[s]
+
+    def sample(self, u) -> torch.Tensor:
+        if self.rtab is not None:
+            return record_weighted(u, *self.rtab)
+        return torch.stack([u[nd] for nd in self.rec]) if self.rec else torch.zeros(0, dtype=u.dtype, device=u.device)
+
+
 def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, receivers=(),
                  L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, device="cpu",
-                 taper=None, order: int = 2, density=None):
+                 taper=None, order: int = 2, density=None, source_positions=None, receiver_positions=None,
+                 interp: str = "sinc8"):
     """Whole single-domain solve of ``(1/c^2) u_tt = lap u + f`` from rest in PyTorch, in
     ``solve()``'s storage (x ghosts, local = global + 1).
 
@@ -538,17 +808,24 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
     density: rho, a scalar or ``(N+1)^3`` (order 2 only): ``(1/kappa) u_tt = div(b grad u) + f`` with
     ``kappa = rho c^2`` and ``b = 1 / rho``; m becomes ``kappa tau^2`` (``medium_coefficient``) and every
     step uses ``laplace_density``. None: the constant-density operations, unchanged.
+
+    source_positions / receiver_positions: ``[S, 3]`` / ``[R, 3]`` fractional node coordinates in place of
+    ``sources`` / ``receivers`` (each side exclusive with its node list; CPU only), acting through the
+    ``interp`` slots ("sinc8" or "linear"; ``interp_tables``): step n adds ``m[p] val_p(g[n-1])`` at every
+    touched node p (``inject_rows``) and a trace is the weighted gather ``record_weighted``.
     """
     c = tables(N, K, L, T, pi)[4]
     M, box, mirror = _medium_layout(N, order)
+    pts = _Points(N, M, dtype, sources, receivers, source_positions, receiver_positions, interp)
+    if (pts.rows is not None or pts.rtab is not None) and torch.device(device).type != "cpu":
+        raise ValueError("positions exist on the CPU oracle only")
     if taper is not None:
         taper = tuple(t.to(device) for t in taper_tables(taper, N, dtype, M))
     m = medium_coefficient(speed2, c["tau"], N, dtype, M, density).to(device)
     bu = _buoyancy(density, N, dtype, order, M)
     if bu is not None:
         bu = bu.to(device)
-    ent = source_entries(sources, N, M)
-    g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype).to(device)
+    g = source_table(wavelet, K, pts.S, c["hx"], c["hy"], c["hz"], dtype).to(device)
     lv = [torch.zeros(N + 1 + 2 * M, N + 1, N + 1, dtype=dtype, device=device) for _ in range(3)]
 
     def wrap(u):
@@ -560,12 +837,10 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
             raise ValueError(f"u0 must have shape {(N + 1,) * 3}, not {tuple(u0.shape)}")
         lv[0][M:N + 1 + M] = u0.to(dtype).to(device)
         wrap(lv[0])
-    rec = [(i + M, j, k) for i, j, k in receivers]
-    traces = torch.zeros(K + 1, len(rec), dtype=dtype, device=device)
+    traces = torch.zeros(K + 1, pts.R, dtype=dtype, device=device)
 
     def sample(n, u):
-        for r, nd in enumerate(rec):
-            traces[n, r] = u[nd]
+        traces[n] = pts.sample(u)
 
     sample(0, lv[0])
     mx = [max_abs_field(lv[0][M:N + 1 + M, 1:N, 1:N])]
@@ -576,8 +851,7 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
                            order=order, mirror=mirror, buoyancy=bu)
         mx.append(max_abs_field(vals))
         u[M:N + 1 + M, 1:N, 1:N] = vals
-        for nd, s in ent:
-            u[nd] = u[nd] + m[nd] * g[n - 1, s]
+        pts.inject(u, m, g[n - 1])
         wrap(u)
         sample(n, u)
     return traces, lv[K % 3][M:N + 1 + M].clone(), mx
@@ -626,7 +900,8 @@ def taper_at(tt, node):
 
 def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None, receivers=(), taper=None,
                             L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
-                            keep_lap: bool = False, order: int = 2, density=None, keep_levels: bool = False):
+                            keep_lap: bool = False, order: int = 2, density=None, keep_levels: bool = False,
+                            source_positions=None, receiver_positions=None, interp: str = "sinc8", points=None):
     """``solve_medium`` from rest, restated out of place: every level is a new tensor, so
     ``torch.autograd`` can differentiate the traces with respect to ``speed2`` (an ``(N+1)^3``
     tensor) and ``wavelet``. The operations and their order are those of ``solve_medium``: the traces
@@ -634,19 +909,19 @@ def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None,
     the stencil nodes (the value step n+1 uses). ``density``: as in ``solve_medium`` (a scalar, an
     ``(N+1)^3`` tensor or a leaf to differentiate with respect to; q^n is then ``laplace_density`` of
     u^n). ``keep_levels``: also return [u^1 .. u^{K-1}], whole levels in storage with their x ghosts
-    (after ``keep_lap``'s list if both are asked for)."""
+    (after ``keep_lap``'s list if both are asked for). ``source_positions`` / ``receiver_positions`` /
+    ``interp``: as in ``solve_medium``."""
     c = tables(N, K, L, T, pi)[4]
     M, box, mirror = _medium_layout(N, order)
+    pts = points or _Points(N, M, dtype, sources, receivers, source_positions, receiver_positions, interp)
     shape = (N + 1 + 2 * M, N + 1, N + 1)
     tt = None if taper is None else taper_tables(taper, N, dtype, M)
     m = medium_coefficient(speed2, c["tau"], N, dtype, M, density)
     bu = _buoyancy(density, N, dtype, order, M)
-    ent = source_entries(sources, N, M)
-    g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
-    rec = [(i + M, j, k) for i, j, k in receivers]
+    g = source_table(wavelet, K, pts.S, c["hx"], c["hy"], c["hz"], dtype)
     u2 = torch.zeros(shape, dtype=dtype)
     u1 = torch.zeros(shape, dtype=dtype)
-    rows = [torch.stack([u1[nd] for nd in rec]) if rec else torch.zeros(0, dtype=dtype)]
+    rows = [pts.sample(u1)]
     laps, levels = [], []
     for n in range(1, K + 1):
         if keep_lap and n >= 2:
@@ -657,10 +932,9 @@ def forward_medium_autograd(N: int, K: int, speed2, *, sources=(), wavelet=None,
                            order=order, mirror=mirror, buoyancy=bu)
         u = torch.zeros(shape, dtype=dtype)
         u[M:N + 1 + M, 1:N, 1:N] = vals
-        for nd, s in ent:
-            u[nd] = u[nd] + m[nd] * g[n - 1, s]
+        pts.inject(u, m, g[n - 1])
         _wrap_x(u, N, M)
-        rows.append(torch.stack([u[nd] for nd in rec]) if rec else torch.zeros(0, dtype=dtype))
+        rows.append(pts.sample(u))
         u2, u1 = u1, u
     traces = torch.stack(rows)
     out = (traces,) + ((laps,) if keep_lap else ()) + ((levels,) if keep_levels else ())
@@ -707,10 +981,18 @@ def source_unique_nodes(sources, N: int, ghost: int = 1):
     return [((i % N) + ghost, j, k) for i, j, k in sources]
 
 
-def _gradient_wrt_m(acc, a, g, m, tt, sources, N: int, ghost: int):
+def _gradient_wrt_m(acc, a, g, m, tt, sources, N: int, ghost: int, source_rows=None):
     """dJ/dm on the planes 0 .. N: ``acc / m`` plus the source term at the source nodes; also returns
-    the sources' unique storage nodes."""
+    the sources' unique storage nodes. ``source_rows = (rows, sacc)`` (off-grid sources): the source
+    term is ``sacc[p] / (m[p] G[p])`` at the unique rows p instead, sacc the time sums of ``rows_dot``."""
     gm = acc[ghost:N + 1 + ghost] / m[ghost:N + 1 + ghost]
+    if source_rows is not None:
+        rows, sacc = source_rows
+        n = rows.unique
+        i, j, k = (v[:n] for v in rows.ijk())
+        G = 1.0 if tt is None else tt[0][i] * (tt[1][j] * tt[2][k])
+        gm[i - ghost, j, k] = gm[i - ghost, j, k] + sacc[:n] / (m[i, j, k] * G)
+        return gm, []
     nodes = source_unique_nodes(sources, N, ghost)
     if nodes:
         dots = (a * g).sum(0)
@@ -731,19 +1013,22 @@ def _unique_node_convention(grad, N: int):
 
 
 def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: float, hy: float, hz: float,
-                           ghost: int = 1, density=None):
+                           ghost: int = 1, density=None, source_rows=None):
     """The host-side end of the gradient. acc ``[N+1+2 ghost][N+1][N+1]`` = sum mu^{n+1} q^n in storage
     (faces 0), a ``[K, S]`` with ``a[n, s] = mu^{n+1}[x_s]``, g = the ``source_table``, m = the
     ``medium_coefficient``, all CPU tensors of the working dtype. Returns (dJ/dspeed2 ``(N+1)^3``
     with respect to the unique nodes: plane N a copy of plane 0, faces 0; dJ/dwavelet ``[K, S]``).
     ``density`` (a scalar or ``(N+1)^3``): m = rho speed2 tau^2, so the gradient is multiplied by rho as
-    its last arithmetic operation: dJ/dspeed2 at fixed rho."""
-    gm, nodes = _gradient_wrt_m(acc, a, g, m, tt, sources, N, ghost)
+    its last arithmetic operation: dJ/dspeed2 at fixed rho.
+    ``source_rows = (rows, sacc)``: off-grid sources. ``a[n, s]`` is then the weighted gather
+    ``sum_p W[p, s] mu^{n+1}[p] / G[p]`` (``receiver_tables(over_taper=tt)``), so dJ/dwavelet only divides
+    it by ``hx hy hz``, and the source term of dJ/dm comes from ``sacc`` (``_gradient_wrt_m``)."""
+    gm, nodes = _gradient_wrt_m(acc, a, g, m, tt, sources, N, ghost, source_rows)
     grad = (gm * tau) * tau  # m = (speed2 tau) tau
     if density is not None:
         grad = grad * _node_field(density, N, "density").to(grad.dtype)
     _unique_node_convention(grad, N)
-    gw = torch.zeros_like(a)
+    gw = torch.zeros_like(a) if source_rows is None else a / (hx * hy * hz)
     for s, nd in enumerate(nodes):
         gw[:, s] = a[:, s] / taper_at(tt, nd) / (hx * hy * hz)
     if gw.shape[0] > 0:
@@ -752,7 +1037,7 @@ def finish_gradient_medium(acc, a, g, m, tt, sources, N: int, tau: float, hx: fl
 
 
 def finish_gradient_density(acc, accb, a, g, m, tt, sources, N: int, tau: float, speed2, density,
-                            ghost: int = 1):
+                            ghost: int = 1, source_rows=None):
     """The host-side end of the density gradient, shared by both backends. acc, a, g, m, tt, sources as
     in ``finish_gradient_medium``; accb ``[N+1+2 ghost][N+1][N+1]`` = sum_{n=K-1..1} C(mu^{n+1}, u^n)
     (``face_correlation``) in storage. rho enters the step through ``m = rho speed2 tau^2`` and through
@@ -765,7 +1050,7 @@ def finish_gradient_density(acc, accb, a, g, m, tt, sources, N: int, tau: float,
     unique x planes and j, k in 1 .. N-1: plane N a copy of plane 0 and the Dirichlet faces 0 (the wall
     nodes' densities do enter the adjacent half-face averages; they are held fixed and reported as 0,
     like the faces of dJ/dspeed2, which keeps the accumulation on ``step_medium``'s box)."""
-    gm, _ = _gradient_wrt_m(acc, a, g, m, tt, sources, N, ghost)
+    gm, _ = _gradient_wrt_m(acc, a, g, m, tt, sources, N, ghost, source_rows)
     rho = _node_field(density, N, "density").to(gm.dtype)
     part1 = ((gm * tau) * tau) * _node_field(speed2, N, "speed2").to(gm.dtype)
     part2 = (0.5 * accb[ghost:N + 1 + ghost]) / (rho * rho)
@@ -796,14 +1081,21 @@ def finish_illumination(h, tt, N: int, tau: float, ghost: int = 1, density=None)
 
 
 def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, receivers, taper, L, T, pi, dtype,
-                    order: int, density, wrt_density: bool, illumination: bool = False):
+                    order: int, density, wrt_density: bool, illumination: bool = False, source_positions=None,
+                    receiver_positions=None, interp: str = "sinc8"):
     """The forward run and the adjoint loop shared by ``gradient_medium`` and
     ``gradient_medium_density``: everything their host-side ends need, as a dict. ``illumination``: also
     ``h = h + q^n q^n`` over the forward run's q^1 .. q^{K-1} in that order, the product rounded before
-    the add, on the stencil nodes in storage (``finish_illumination`` has the rest)."""
-    fwd = forward_medium_autograd(N, K, speed2, sources=sources, wavelet=wavelet, receivers=receivers,
-                                  taper=taper, L=L, T=T, pi=pi, dtype=dtype, keep_lap=True, order=order,
-                                  density=density, keep_levels=wrt_density)
+    the add, on the stencil nodes in storage (``finish_illumination`` has the rest).
+
+    Off-grid receivers: the residuals ``[K+1, R]`` are injected through ``point_rows(.., tt)``, whose
+    weights carry G. Off-grid sources: ``a[n-1, s]`` is the weighted gather of mu^n with the
+    ``receiver_tables(over_taper=tt)`` and ``sacc = sacc + mu^n[p] val_p(g[n-1])`` is accumulated per
+    unique source row in the loop's order, n = K .. 1 (``rows_dot``)."""
+    M0 = _medium_layout(N, order)[0]
+    pts = _Points(N, M0, dtype, sources, receivers, source_positions, receiver_positions, interp)
+    fwd = forward_medium_autograd(N, K, speed2, wavelet=wavelet, taper=taper, L=L, T=T, pi=pi, dtype=dtype,
+                                  keep_lap=True, order=order, density=density, keep_levels=wrt_density, points=pts)
     traces, laps = fwd[0], fwd[1]
     J, res = misfit_medium(traces, observed)
     c = tables(N, K, L, T, pi)[4]
@@ -811,12 +1103,21 @@ def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, recei
     tt = None if taper is None else taper_tables(taper, N, dtype, M)
     m = medium_coefficient(speed2, c["tau"], N, dtype, M, density)
     bu = _buoyancy(density, N, dtype, order, M)
-    g = source_table(wavelet, K, len(sources), c["hx"], c["hy"], c["hz"], dtype)
-    anodes, atab = adjoint_source_table(res, receivers, N, tt, M)
-    snodes = source_unique_nodes(sources, N, M)
+    g = source_table(wavelet, K, pts.S, c["hx"], c["hy"], c["hz"], dtype)
+    arows = gtab = sacc = None
+    anodes, atab, snodes = [], None, []
+    if pts.rpos is None:
+        anodes, atab = adjoint_source_table(res, receivers, N, tt, M)
+    else:
+        arows = point_rows(pts.rpos, N, dtype, interp, M, tt)
+    if pts.spos is None:
+        snodes = source_unique_nodes(sources, N, M)
+    else:
+        gtab = receiver_tables(pts.spos, N, dtype, interp, M, over_taper=tt)
+        sacc = torch.zeros(pts.rows.unique, dtype=dtype)
     shape = (N + 1 + 2 * M, N + 1, N + 1)
     own = (slice(M, N + 1 + M), slice(1, N), slice(1, N))
-    a = torch.zeros(K, len(snodes), dtype=dtype)
+    a = torch.zeros(K, pts.S, dtype=dtype)
     h = None
     if illumination:  # ascending n, the q^n the adjoint loop correlates with mu^{n+1}
         h = torch.zeros(shape, dtype=dtype)
@@ -824,9 +1125,15 @@ def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, recei
             h[own] = h[own] + q * q
 
     def finish_level(mu, n):  # inject G rho^n, wrap, sample mu^n at the sources
+        nonlocal sacc
+        if arows is not None:
+            inject_rows(mu, m, arows, res[n])
         for e, nd in enumerate(anodes):
             mu[nd] = mu[nd] + m[nd] * atab[n, e]
         _wrap_x(mu, N, M)
+        if gtab is not None:
+            a[n - 1] = record_weighted(mu, *gtab)
+            sacc = rows_dot(mu, pts.rows, g[n - 1], sacc)
         for s, nd in enumerate(snodes):
             a[n - 1, s] = mu[nd]
 
@@ -845,12 +1152,14 @@ def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, recei
         mu[own] = vals
         finish_level(mu, n)
         mu2, mu1 = mu1, mu
-    return dict(J=J, traces=traces, acc=acc, accb=accb, a=a, g=g, m=m, tt=tt, c=c, M=M, h=h)
+    return dict(J=J, traces=traces, acc=acc, accb=accb, a=a, g=g, m=m, tt=tt, c=c, M=M, h=h,
+                source_rows=None if gtab is None else (pts.rows, sacc))
 
 
 def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,
                     L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, order: int = 2,
-                    density=None, illumination: bool = False):
+                    density=None, illumination: bool = False, source_positions=None, receiver_positions=None,
+                    interp: str = "sinc8"):
     """Misfit J of the traces against ``observed`` ``[K+1, R]`` (row 0 ignored) and its gradients by
     the hand-written adjoint above: (J, dJ/dspeed2 ``(N+1)^3``, dJ/dwavelet ``[K, S]``, traces).
 
@@ -870,14 +1179,19 @@ def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=Non
 
     illumination: two more results, (source illumination, pseudo-Hessian diagonal for speed2), both
     ``(N+1)^3`` (``finish_illumination``): sum_{n=1..K-1} q^n q^n over the q^n above, added in ascending
-    n, the product rounded before the add. The other results do not change."""
+    n, the product rounded before the add. The other results do not change.
+
+    source_positions / receiver_positions / interp: off-grid points as in ``solve_medium``. With W the
+    row weights, ``dJ/dg[n, s] = sum_p W[p, s] mu^{n+1}[p] / G[p]`` and the source term of dJ/dm at a touched
+    node p is ``(sum_n mu^{n+1}[p] val_p(g[n])) / (m[p] G[p])`` (``_adjoint_medium``)."""
     with torch.no_grad():
         r = _adjoint_medium(N, K, speed2, observed, sources=sources, wavelet=wavelet, receivers=receivers,
                             taper=taper, L=L, T=T, pi=pi, dtype=dtype, order=order, density=density,
-                            wrt_density=False, illumination=illumination)
+                            wrt_density=False, illumination=illumination, source_positions=source_positions,
+                            receiver_positions=receiver_positions, interp=interp)
         c = r["c"]
         grad, gw = finish_gradient_medium(r["acc"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"], c["hx"],
-                                          c["hy"], c["hz"], r["M"], density)
+                                          c["hy"], c["hz"], r["M"], density, r["source_rows"])
         out = (r["J"], grad, gw, r["traces"])
         if illumination:
             out += finish_illumination(r["h"], r["tt"], N, c["tau"], r["M"], density)
@@ -886,7 +1200,8 @@ def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=Non
 
 def gradient_medium_density(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,
                             L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
-                            order: int = 2, density=None, illumination: bool = False):
+                            order: int = 2, density=None, illumination: bool = False, source_positions=None,
+                            receiver_positions=None, interp: str = "sinc8"):
     """``gradient_medium`` of a problem with a ``density`` (required; order 2), plus the gradient with
     respect to it: (J, dJ/dspeed2 at fixed rho, dJ/dwavelet, traces, dJ/drho at fixed speed2). The
     first four are those of ``gradient_medium`` bit for bit. ``illumination``: ``gradient_medium``'s two
@@ -904,12 +1219,13 @@ def gradient_medium_density(N: int, K: int, speed2, observed, *, sources=(), wav
     with torch.no_grad():
         r = _adjoint_medium(N, K, speed2, observed, sources=sources, wavelet=wavelet, receivers=receivers,
                             taper=taper, L=L, T=T, pi=pi, dtype=dtype, order=order, density=density,
-                            wrt_density=True, illumination=illumination)
+                            wrt_density=True, illumination=illumination, source_positions=source_positions,
+                            receiver_positions=receiver_positions, interp=interp)
         c = r["c"]
         grad, gw = finish_gradient_medium(r["acc"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"], c["hx"],
-                                          c["hy"], c["hz"], r["M"], density)
+                                          c["hy"], c["hz"], r["M"], density, r["source_rows"])
         gd = finish_gradient_density(r["acc"], r["accb"], r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"],
-                                     speed2, density, r["M"])
+                                     speed2, density, r["M"], r["source_rows"])
         out = (r["J"], grad, gw, r["traces"], gd)
         if illumination:
             out += finish_illumination(r["h"], r["tt"], N, c["tau"], r["M"], density)
@@ -963,7 +1279,8 @@ def perturbation_field(v, N: int, name: str) -> torch.Tensor:
 
 def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=(), wavelet=None, receivers=(),
                 taper=None, L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64,
-                order: int = 2, density=None, ddensity=None):
+                order: int = 2, density=None, ddensity=None, source_positions=None, receiver_positions=None,
+                interp: str = "sinc8"):
     """Born modelling from rest: ``solve_medium``'s run and, in lock step, the first-order change of
     its field for the perturbations ``dspeed2`` of speed2 (a scalar or ``(N+1)^3``, finite, periodic
     in x, of any sign; the density stays fixed), ``dwavelet`` ``[K, S]`` of the wavelet and ``ddensity``
@@ -976,7 +1293,9 @@ def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=
     ``du += m dg[n-1, s]`` (each a rounded product, then the add), the wrap, the sample. Step 1 has
     no Born term. With ``ddensity`` the Born step is ``step_medium(born_add=s)`` with
     ``s = dm q + m r``, r = ``laplace_density`` of the same background level with the buoyancy
-    perturbation in b's place; without it every operation is the one above."""
+    perturbation in b's place; without it every operation is the one above.
+    ``source_positions`` / ``receiver_positions`` / ``interp``: off-grid points as in ``solve_medium``; the
+    perturbed source terms are then ``inject_rows`` with dm and g, and with m and dg."""
     if dspeed2 is None and dwavelet is None and ddensity is None:
         raise ValueError("born_medium needs a perturbation: dspeed2, dwavelet, ddensity or any of them together")
     if ddensity is not None and density is None:
@@ -996,8 +1315,8 @@ def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=
         dmr = medium_coefficient(speed2, c["tau"], N, dtype, M, dr)
         dm = dmr if dspeed2 is None else dm + dmr
         db = dbuoyancy_field(dr, density, N, dtype, M)
-    ent = source_entries(sources, N, M)
-    S = len(sources)
+    pts = _Points(N, M, dtype, sources, receivers, source_positions, receiver_positions, interp)
+    S = pts.S
     g = source_table(wavelet, K, S, c["hx"], c["hy"], c["hz"], dtype)
     dg = None
     if dwavelet is not None:
@@ -1009,9 +1328,8 @@ def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=
     own = (slice(M, N + 1 + M), slice(1, N), slice(1, N))
     lv = [torch.zeros(shape, dtype=dtype) for _ in range(3)]
     dl = [torch.zeros(shape, dtype=dtype) for _ in range(3)]
-    rec = [(i + M, j, k) for i, j, k in receivers]
-    traces = torch.zeros(K + 1, len(rec), dtype=dtype)
-    dtraces = torch.zeros(K + 1, len(rec), dtype=dtype)
+    traces = torch.zeros(K + 1, pts.R, dtype=dtype)
+    dtraces = torch.zeros(K + 1, pts.R, dtype=dtype)
     kw = dict(hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt, order=order, mirror=mirror, buoyancy=bu)
     mx = [0.0]  # du^0 = 0
     for n in range(1, K + 1):
@@ -1020,8 +1338,7 @@ def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=
         q = _lap_box(u1, box, c["hx2"], c["hy2"], c["hz2"], order, mirror, bu) if n >= 2 else None
         u.zero_()
         u[own] = step_medium(u1, u2, m, box, first=n == 1, **kw)
-        for nd, s in ent:
-            u[nd] = u[nd] + m[nd] * g[n - 1, s]
+        pts.inject(u, m, g[n - 1])
         _wrap_x(u, N, M)
         if db is None or n == 1:
             dvals = step_medium(d1, d2, m, box, first=n == 1, born=None if n == 1 else (q, dm), **kw)
@@ -1031,12 +1348,16 @@ def born_medium(N: int, K: int, speed2, dspeed2=None, dwavelet=None, *, sources=
         mx.append(max_abs_field(dvals))
         d.zero_()
         d[own] = dvals
-        for nd, s in ent:
-            d[nd] = d[nd] + dm[nd] * g[n - 1, s]
+        if pts.rows is not None:
+            inject_rows(d, dm, pts.rows, g[n - 1])
             if dg is not None:
-                d[nd] = d[nd] + m[nd] * dg[n - 1, s]
+                inject_rows(d, m, pts.rows, dg[n - 1])
+        else:
+            for nd, s in pts.ent:
+                d[nd] = d[nd] + dm[nd] * g[n - 1, s]
+                if dg is not None:
+                    d[nd] = d[nd] + m[nd] * dg[n - 1, s]
         _wrap_x(d, N, M)
-        for r, nd in enumerate(rec):
-            traces[n, r] = u[nd]
-            dtraces[n, r] = d[nd]
+        traces[n] = pts.sample(u)
+        dtraces[n] = pts.sample(d)
     return traces, dtraces, dl[K % 3][M:N + 1 + M].clone(), mx

@@ -10,6 +10,7 @@
     python tools/bench_medium.py --born [--N 512] [--steps 100] [--dtypes fp64,fp32] [--order 2,4,8]
                                  [--kernels-only] [--density]
     python tools/bench_medium.py --born --density --ddensity [--N 512] [--steps 100] [--kernels-only]
+    python tools/bench_medium.py --positions R [--N 256] [--steps 100] [--dtypes fp64,fp32] [--repeat 3]
 
 For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
 and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
@@ -70,6 +71,15 @@ step (48 B) and the Born step (56 B) of the same density problem; the plain dens
 (40 B), the yardstick, with and without the sponge. Then, alternating as well, the time loops of
 born(ddensity=...), born(dspeed2=...) and run() of the two-layer density problem. `--kernels-only` skips
 the loops.
+
+`--positions R` measures off-grid sources and receivers (k_inject_rows, k_record_w, k_rows_dot), per dtype
+in one process at N = 256 unless `--N` says otherwise: R receivers on a square array in the plane
+z = N / 8, each jittered by up to half a cell per axis, and one off-grid source, against the same
+problem with every point rounded to its nearest node (k_inject, k_record). Inside each repeat run() and
+gradient() (every q stored, so the reverse pass recomputes nothing) of the two alternate; reported are
+ms per step of run()'s time loop (step + inject + record) and of gradient()'s reverse pass (image step
++ the injection of R residuals + the record at the source, with positions also the row dot), the
+difference positions - nodes, and that difference over the node-list step.
 """
 import argparse
 import json
@@ -102,6 +112,64 @@ def two_layer_density(N: int):
     rho = torch.ones((N + 1,) * 3, dtype=torch.float64)
     rho[:, :, N // 2:] = 2.0
     return rho
+
+
+def positions_bench(a) -> int:
+    import math
+
+    import torch
+
+    import wave3d
+
+    N, K, R = a.N, a.steps, a.positions
+    h = 3.1415926535 / N
+    hi = (0.9 * wave3d.cfl_limit(2) * h * K) ** 2
+    speed2 = smooth_speed2(N, 0.5 * hi, hi)
+    side = max(1, math.isqrt(R))
+    g = torch.Generator().manual_seed(5)
+    q = torch.arange(R)
+    lo, span = 0.1 * N, 0.8 * N / max(side - 1, 1)
+    rpos = torch.stack([lo + span * (q % side), lo + span * ((q // side) % side),
+                        torch.full((R,), N / 8.0, dtype=torch.float64)], 1).to(torch.float64)
+    rpos = rpos + (torch.rand(R, 3, generator=g, dtype=torch.float64) - 0.5)
+    mid = N // 2
+    spos = torch.tensor([[mid + 0.3, mid - 0.4, mid + 0.2]], dtype=torch.float64)
+    out = {"N": N, "steps": K, "receivers": R, "device": torch.cuda.get_device_name(0), "runs": []}
+    for dtype in a.dtypes.split(","):
+        prob = wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype)
+        w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
+        sol = {"nodes": wave3d.MediumSolver(prob, "hip", sources=[tuple(int(v) for v in spos[0].round())], wavelet=w,
+                                            receivers=[tuple(int(v) for v in r) for r in rpos.round()]),
+               "positions": wave3d.MediumSolver(prob, "hip", source_positions=spos, wavelet=w,
+                                                receiver_positions=rpos)}
+        obs = 0.9 * sol["nodes"].run().traces  # warm-up as well
+        fwd, rev, extra = {k: [] for k in sol}, {k: [] for k in sol}, {}
+        for k in sol:
+            sol[k].gradient(obs, segment=K)
+        for _ in range(a.repeat):
+            for k in sol:
+                r = sol[k].run()
+                assert not r.aborted and math.isfinite(max(r.max_abs_u)), "the benchmark run diverged"
+                fwd[k].append(r.total_ms / K)
+            for k in sol:
+                gr = sol[k].gradient(obs, segment=K)
+                rev[k].append(gr.extra["reverse_ms"] / K)
+                extra[k] = gr.extra
+            print(f"bench_medium: {dtype} forward {fwd['nodes'][-1]:.4f} / {fwd['positions'][-1]:.4f} ms per step, "
+                  f"reverse {rev['nodes'][-1]:.4f} / {rev['positions'][-1]:.4f} (nodes / positions)",
+                  file=sys.stderr, flush=True)
+        row = {"dtype": dtype, "courant": round(prob.courant, 4)}
+        for name, t in (("forward", fwd), ("reverse", rev)):
+            a0, b0 = min(t["nodes"]), min(t["positions"])
+            row[name] = {"nodes_ms_per_step": round(a0, 4), "positions_ms_per_step": round(b0, 4),
+                         "extra_ms_per_step": round(b0 - a0, 4), "extra_over_nodes": round((b0 - a0) / a0, 4),
+                         "all_nodes": [round(v, 4) for v in t["nodes"]],
+                         "all_positions": [round(v, 4) for v in t["positions"]]}
+        row.update({k: extra["positions"][k] for k in ("interp", "source_rows", "source_entries", "receiver_rows",
+                                                      "receiver_entries")})
+        out["runs"].append(row)
+    print(json.dumps(out))
+    return 0
 
 
 def density_gradient_bench(a) -> int:
@@ -508,7 +576,7 @@ def gradient_bench(a) -> int:
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--N", type=int, default=512)
+    ap.add_argument("--N", type=int, default=None, help="default 512 (--positions: 256)")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--dtypes", default="fp64,fp32")
     ap.add_argument("--variants", default="default")
@@ -529,7 +597,11 @@ def main(argv=None) -> int:
                     help="--gradient: also time the illum and save+illum steps and gradient(illumination=True)")
     ap.add_argument("--ddensity", action="store_true",
                     help="--born --density: time the scatter and Born-add steps and born(ddensity=...) instead")
+    ap.add_argument("--positions", type=int, default=0, metavar="R",
+                    help="time off-grid sources and receivers instead: R receivers and one source, run() and gradient()")
     a = ap.parse_args(argv)
+    if a.N is None:
+        a.N = 256 if a.positions else 512
 
     import math
 
@@ -548,6 +620,10 @@ def main(argv=None) -> int:
         ap.error("--density: order 2 must be among the orders")
     if a.illum and (not a.gradient or a.wrt_density):
         ap.error("--illum goes with --gradient (without --wrt-density)")
+    if a.positions:
+        if a.positions < 1 or a.gradient or a.born or a.density or orders != [2]:
+            ap.error("--positions R >= 1 is a measurement of its own (order 2, no other mode)")
+        return positions_bench(a)
     if a.wrt_density:
         if not (a.gradient and a.density) or orders != [2]:
             ap.error("--wrt-density goes with --gradient --density at order 2")
