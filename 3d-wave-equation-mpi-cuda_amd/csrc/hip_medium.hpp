@@ -42,8 +42,8 @@ namespace wave3d {
 // and ignores `mirror`. Orders 4 and 8 run k_march_mh, a star stencil of 2M + 1 points per axis with
 // the central second-derivative weights c_0 .. c_M (medium_weight): per axis t = c_0 v, then
 // t = t + c_d (p_-d + p_+d) for d = 1 .. M, and lap = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2,
-// every operation rounded on its own, the divisions correctly rounded; the updates, the sponge and
-// the save / image modes are those above (any variant is accepted and ignored). The x neighbours
+// every operation rounded on its own, the divisions correctly rounded on div_const's range (the
+// paragraph "Division by h^2" below); the updates, the sponge and the save / image modes are those above (any variant is accepted and ignored). The x neighbours
 // come from storage: the boxes keep M planes from both ends of the storage. mirror = (j_lo, j_hi,
 // k_lo, k_hi), storage indices of reflecting (Dirichlet) faces, kNoMirror = none on that side
 // (nullptr: none at all): a neighbour beyond a face f is read as -u1[2 f - j], the face itself as
@@ -57,7 +57,8 @@ namespace wave3d {
 // D_b u1 = div(b grad u1): per axis, with centre c, neighbours u_-, u_+ and buoyancies b_c, b_-, b_+,
 // f_+ = (0.5 (b_c + b_+)) (u_+ - c), f_- = (0.5 (b_c + b_-)) (c - u_-), t = f_+ - f_-, and
 // D_b u1 = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2, every operation rounded on its own, the
-// divisions correctly rounded (ops/reference.py laplace_density). Save mode stores D_b u1. b is read
+// divisions correctly rounded on div_const's range ("Division by h^2" below; ops/reference.py
+// laplace_density). Save mode stores D_b u1. b is read
 // at the box nodes and their six neighbours, never written. Per node in fp64: 40 B (20 B in fp32).
 //
 // Born modelling with a density perturbation: two more modes of k_march_mb (b non-null, so order 2 and
@@ -83,6 +84,23 @@ namespace wave3d {
 // with a non-default variant at order 2, with q, acc, dm, db or sadd (image, Born, scatter and Born-add
 // modes), and an illum that shares memory with u, u1, u2, m, b or lap_out. Per node in fp64: 48 B
 // (illum), 56 B (save+illum); with b 56 B and 64 B.
+//
+// Division by h^2. All four march kernels and k_face_corr divide a numerator t by h^2 with div_const
+// (stencil_math.hpp: three operations with y = RN(1 / h^2)), not with an IEEE division. The quotient is
+// RN(t / h^2), the oracle's bits, for t = 0 and for 2^(emin + p + 1) <= |t| <= 2^(emax - ceil(log2 y)):
+// in fp32 2^-101 = 3.9e-31 up to 2^120 for h^2 = 0.011, in fp64 2^-968 = 4.0e-292 up to 2^1016 (for
+// h^2 >= 2 up to the largest finite value). Outside that range:
+//   * a smaller numerator (down to the subnormals) gives a quotient at most D = 1 unit in the last place
+//     from RN(t / h^2); measured by tests/test_div_const_cpu.py: up to 45 % of a binade's numerators
+//     around 2^-131 (fp32) and 58 % around 2^-1026 (fp64), none found from 2^-108 (fp32) and 2^-1005
+//     (fp64) on;
+//   * a larger one, and t = +-inf, gives NaN where true division gives a finite quotient or +-inf: an
+//     infinity in u1 makes its stencil neighbours NaN here and +-inf in the oracle, non-finite at the
+//     same nodes (the non-finite flag is set either way; max |u| ignores a NaN but not an infinity);
+//   * t = -0 gives +0; the 0 + ... in front of the sum hides it (true division's -0 ends as +0 too).
+// So "hip equals cpu bit for bit" holds for fields whose numerators are zero or in range. The precursor
+// ahead of a wave front decays through the lower bound; there the two backends may differ in the last
+// place of a quotient (tests/test_gpu_medium_bits.py bounds it).
 constexpr int kNoMirror = -(1 << 29);
 template <class T>
 void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
@@ -114,7 +132,8 @@ void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int
 // v = u^n). Per axis, with centre values a_c, v_c and neighbours a_-, a_+, v_-, v_+:
 // p_+ = (a_+ - a_c) (v_+ - v_c), p_- = (a_c - a_-) (v_c - v_-), t = p_+ + p_-, and
 // C = ((0 + t_x / hx2) + t_y / hy2) + t_z / hz2, every operation rounded on its own, the divisions
-// correctly rounded (ops/reference.py face_correlation); C(a, v) == C(v, a) bit for bit. a, v and
+// correctly rounded on div_const's range ("Division by h^2" above; ops/reference.py face_correlation);
+// C(a, v) == C(v, a) bit for bit. a, v and
 // acc are levels with the strides of `gv` (one ghost layer, x ghost planes of a and v filled); the
 // box contract is k_march_m's: boxes inside the owned region, so every box node has its six
 // neighbours in storage. a and v are never written and acc only at the box nodes. Rejected before

@@ -26,7 +26,7 @@ struct TileParams {
     int nbox;
     BoxLaunch box[kMaxBoxes];
     T hx2, hy2, hz2;
-    T yx2, yy2, yz2;  // RN(1/h^2) in T for the correctly rounded constant division
+    T yx2, yy2, yz2;  // RN(1/h^2) in T for the constant division (div_const)
 };
 
 template <class T>
@@ -146,7 +146,9 @@ __device__ __forceinline__ void march_planes(int ib, int ie, F& plane) {
     march_planes(ib, ie, plane, std::make_integer_sequence<int, N>{});
 }
 
-// ((0 + tx / hx2) + ty / hy2) + tz / hz2, the divisions correctly rounded (div_const)
+// ((0 + tx / hx2) + ty / hy2) + tz / hz2, the divisions by div_const: correctly rounded for numerators
+// that are zero or in 2^(emin + p + 1) <= |t| <= 2^(emax - ceil(log2 (1 / h2))), within D = 1 ulp of the
+// true quotient below that range, NaN above it and for t = +-inf (stencil_math.hpp)
 template <class T>
 __device__ __forceinline__ T sum_div(T tx, T ty, T tz, const TileParams<T>& p) {
 #pragma clang fp contract(off)

@@ -85,11 +85,18 @@ W3D_HD void accumulate_error(T u, T f, T& mabs, T& mrel) {
     if (er > mrel) mrel = er;
 }
 
-// ---- correctly rounded division by a constant ----------------------------------------
+// ---- division by a constant, correctly rounded on its range --------------------------
 // q = a*y, r = a - q*b (exact by FMA), q' = q + r*y with y = RN(1/b) is RN(a/b) absent
 // under/overflow (Markstein's theorem). Three FP ops instead of the ~10-instruction IEEE
-// division sequence, bitwise identical to a/b (checked against the reference's true
-// divisions by the CPU/GPU parity tests).
+// division sequence, bitwise identical to a/b on the range
+//     a = 0,  or  2^(emin + p + 1) <= |a| <= 2^(emax - ceil(log2 y))
+// (p = 24 / 53 bits, emin = -126 / -1022, emax = 127 / 1023: fp32 from 2^-101 = 3.9e-31, fp64 from
+// 2^-968 = 4.0e-292; the upper end is 2^120 / 2^1016 for b = 0.011 and the largest finite value for
+// b >= 2). Below it the residual r is no longer exact (it needs bits under the subnormal spacing) and
+// q' is at most D = 1 unit in the last place from RN(a/b); above it a*y overflows and q' = inf - inf
+// = NaN, as it is for a = +-inf (true division: +-inf); a = -0 gives +0 (true division: -0); NaN
+// gives NaN. tests/test_div_const_cpu.py sweeps every binade of both types against a/b and pins
+// the range, D and these special values; tests/bits.py division_range has the derivation.
 W3D_HD double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 W3D_HD float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 #ifdef __HIPCC__

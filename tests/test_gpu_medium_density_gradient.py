@@ -1,8 +1,9 @@
 """Density gradients on the GPU: k_face_corr (csrc/hip_medium_corr.hip) against the PyTorch oracle
 (ops/reference.py face_correlation), and MediumSolver.gradient(wrt_density=True), "hip" against "cpu".
 
-fp64 results must be bitwise equal: both sides round every operation in the same order. fp32 stays
-inside the bound of test_gpu_medium_order.py, measured on the oracle and never on the kernel:
+fp64 results must be bitwise equal: both sides round every operation in the same order; a single fp32
+launch of k_face_corr is bitwise equal too. The fp32 gradient stays inside the bound of
+test_gpu_medium_order.py, measured on the oracle and never on the kernel:
 |got - exp32| <= 4 max |exp32 - exp64|. Inputs: a, v in [0, 1], acc in [-0.5, 0.5].
 """
 import pytest
