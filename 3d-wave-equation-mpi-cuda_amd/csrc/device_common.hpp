@@ -113,7 +113,11 @@ __device__ __forceinline__ float nan_unless(bool v, float d) {
 // split into RN value + exact FMA residual, and the one IEEE division happens at the end.
 // RN is monotone, so value() = RN(max exact quotient) = max of the reference's RN quotients
 // (mpi_new.cpp:341-344): bitwise equal, including its NaN-ignoring `>` and the x/0 = inf case
-// (exact as long as the products are normal numbers, i.e. |errors| and |f| above ~1e-150).
+// (exact as long as the FMA residuals are: every product at an exponent >= emin + p - 1, fp64 2^-970,
+// fp32 2^-103, i.e. |errors| and |f| above ~1e-146 / ~1e-15. Below that the residuals are rounded; on
+// the tie pairs of tests/relarg_ties.py the answer stays right while the products are normal numbers
+// (one exception in fp32) and is the smaller quotient for about half of them once the products are
+// subnormal: tests/test_relarg_ties_cpu.py, pinned on the device by tests/test_gpu_sweep_bits.py).
 // add() takes the signed d = u - f and f: the |.| are source modifiers of the products and of
 // the selects (pick_abs), so num, den hold |d|, |f| without a v_and per node.
 template <class T>

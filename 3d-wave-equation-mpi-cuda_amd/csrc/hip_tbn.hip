@@ -468,13 +468,12 @@ k_tbn(const TbnParams<T> p) {
     }
     const T ortz = FM && k >= Bx.k0 && k <= Bx.k1 ? p.rtz[k] : T(0);
     const T* const txw = p.txy + (jt + w * R);
-    // om: 1 on valid own nodes, 0 on masked lanes (the non-finite detector); otzr: sz, a quiet
-    // NaN on masked lanes — their analytic values and so their errors are NaN, which max_abs,
-    // RelMax and RelArg ignore (no product or branch per node: profiles/deep_sweeps_r5.txt)
-    T om[R], otzr[R];
+    // otzr: sz, a quiet NaN on masked lanes — their analytic values and so their errors are NaN,
+    // which max_abs, RelMax and RelArg ignore (no product or branch per node:
+    // profiles/deep_sweeps_r5.txt)
+    T otzr[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        om[r] = ovalid[r] ? T(1) : T(0);
         otzr[r] = nan_unless(ovalid[r], k >= Bx.k0 && k <= Bx.k1 ? p.tz[k] : T(0));
     }
     // self-wrap ranges of O[0] / O[1] met by this work item (wave-uniform bits)
@@ -668,6 +667,15 @@ k_tbn(const TbnParams<T> p) {
     Rel mr[D];
 #pragma unroll
     for (int l = 0; l < D; ++l) ma[l] = T(kErrInit), chk[l] = T(0);
+    // The non-finite detector: the last layer's values summed per own row, one add per node, and
+    // the rows of masked lanes dropped once at the end (ovalid is fixed for the work item). A 0/1
+    // factor per node (fma(val, om, chk)) let a masked lane raise the flag, 0 * NaN = NaN: lanes of
+    // the k tile before the box's k0 and rows of the j tile past its j1 compute values from memory
+    // that is outside the box's cone, where a non-finite value is none of this sweep's business
+    // (tests/test_gpu_sweep_bits.py).
+    T chkr[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) chkr[r] = T(0);
 
     // layer-l arithmetic: lap() = Laplacian (exact) or the deferred coef*Laplacian (FM, FmLap:
     // the leapfrog takes it whole, stencil_math leap_fm); upd() = the Taylor start (layer 0 of
@@ -975,8 +983,12 @@ k_tbn(const TbnParams<T> p) {
                     else val = u[l][SE][r];
                     // chk (the non-finite detector) on the last layer only: a NaN / Inf in layer
                     // l reaches U_{D-1} at the same node within the sweep (through the centre
-                    // term, masked nodes included), so the sweep's last layer carries the flag
-                    if constexpr (l == D - 1) chk[l] = fma_t(val, om[r], chk[l]);
+                    // term, masked nodes included), so the sweep's last layer carries the flag.
+                    // It is the flag of the box nodes: a non-finite input that reaches no box node of
+                    // the last layer (outside the L1 cone of the box: a frame corner, B at distance
+                    // D) leaves the outputs, the keys and the flag untouched, and the slots of the
+                    // earlier layers never carry a flag (tests/test_gpu_sweep_bits.py pins both).
+                    if constexpr (l == D - 1) chkr[r] += val;
                     if constexpr (FM) {
                         const T dv = val - fb[r] * p.ct[l];
                         ma[l] = max_abs(ma[l], dv);
@@ -1036,6 +1048,9 @@ k_tbn(const TbnParams<T> p) {
     }
     // no DMA may still be writing this workgroup's LDS when it exits
     vm_wait<0>();
+#pragma unroll
+    for (int r = 0; r < R; ++r)  // ovalid[r], formed again (no lane mask kept live through the loops)
+        chk[D - 1] += k >= Bx.k0 && k <= Bx.k1 && jt + w * R + r <= Bx.j1 ? chkr[r] : T(0);
     sfor<D>([&](auto lc) {
         constexpr int l = decltype(lc)::value;
         T rel;

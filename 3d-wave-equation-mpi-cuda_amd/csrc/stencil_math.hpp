@@ -167,6 +167,14 @@ W3D_HD T leapfrog_fma(T c, T u2, T l) {
 // 8 operations) biases the rounding of the O(|u|) sum and grows quadratically under the leapfrog:
 // 6.03381562e-07, which breaks the printed golden. fp32 keeps the composition above: its accuracy
 // rests on the exact (Sterbenz) differences. kc = fm_kc(cx, cy, cz), loop-invariant.
+// What pins this section: every function here is a fixed sequence of individually rounded operations,
+// and ops/reference.py writes the same sequence out in plain PyTorch with a correctly rounded software
+// fma (coef_lap_fma_field, taylor_fma_field, leap_fma_field, chained_layers_fma, chained_delta_layers_fma,
+// solve(math="fma")). The kernel tests compare k_tb3, k_tbn and k_march with it bit for bit in fp64 and
+// fp32 (tests/test_gpu_tb_kernels.py, tests/test_gpu_kernels.py), and tests/test_fma_oracle_cpu.py shows
+// that an unfused multiply-add, the other type's composition or the folded chain above changes bits on
+// those tests' inputs: a change of one operand or one rounding here fails at kernel level, not only
+// through a whole solve's per-layer maxima.
 template <class T>
 W3D_HD T fm_kc(T cx, T cy, T cz) {
     return T(-2) * ((cx + cy) + cz);

@@ -7,6 +7,12 @@ The solver itself uses an aligned, padded layout (``csrc/hip_kernels.hpp``); the
 points use pitch = nz, which the kernels accept as well; the medium ops (``step_medium``,
 ``face_correlation``, ``inject``, ``record``, ``inject_rows``, ``record_weighted``, ``rows_dot``) also take
 views in that padded layout (``alloc_level``).
+
+The sweep kernels behind ``step``, ``tb3_sweep`` and ``tbn_sweep`` are tested bit for bit, stored values and
+both error keys, in fp64 and fp32 and in both math modes, against ``ops.reference`` (the exact-form chains,
+and the FMA-form chains built on its software ``fma``); nothing there is compared within a tolerance. What
+is not bitwise: the FMA form against the exact form (the same scheme rounded differently), and fp32
+against fp64.
 """
 from __future__ import annotations
 
@@ -79,7 +85,9 @@ def decode_err(err: torch.Tensor) -> list[tuple[float, float, bool]]:
 
 def step(u1, u2, u, boxes, *, first: bool, err_i, tx, ty, tz, coefs, err,
          kernel: str = "march", wrap=None, chunk: int = 0, pack=None) -> None:
-    """One leapfrog layer over ``boxes`` (list of (i0,i1,j0,j1,k0,k1), local indices).
+    """One leapfrog layer over ``boxes`` (list of (i0,i1,j0,j1,k0,k1), local indices). fp64 and fp32
+    results and error keys are bitwise those of ``ops.reference.step``; ``kernel="marchf"`` / ``"march2f"``: the
+    --math fma instantiation, bitwise ``ops.reference.taylor_fma_field`` / ``leap_fma_field``.
 
     coefs = (hx2, hy2, hz2, coef, ct); err_i = (ei0, ei1) rows entering the error;
     wrap = (src0, dst0, src1, dst1) periodic self-wrap planes; pack = ([zbuf0, zbuf1,
@@ -177,7 +185,7 @@ def _check_box_g(box, gv) -> list[int]:
 
 def tbn_sweep(A, B, O0, O1, boxes, *, depth: int, first: bool, cdom, err_i, tx, ty, tz, coefs, errs,
               rows: int = 2, waves: int = 8, chunk: int = 0, ghost: int | None = None, fma: bool = False,
-              delta: bool = False) -> None:
+              delta: bool = False, check_finite: bool = True) -> None:
     """One deep sweep (k_tbn, ``depth`` layers u^m .. u^{m+depth-1}): the first depth-2 layers
     errors only, O0 = u^{m+depth-2}, O1 = u^{m+depth-1}. ``coefs[l]`` = (hx2, hy2, hz2, coef, ct)
     and ``errs[l]`` the error slot of layer m+l. ``delta``: the increment form (depth 4):
@@ -185,10 +193,16 @@ def tbn_sweep(A, B, O0, O1, boxes, *, depth: int, first: bool, cdom, err_i, tx, 
     A and B must be finite everywhere, ghosts included: the LDS-DMA staging reads whole frame
     rows (a row's neighbours past the box), and a masked Dirichlet node computes 0 * value, so a
     NaN there would spread into the interior (the solver's levels are zeroed at
-    allocation)."""
+    allocation). ``check_finite=False`` skips that one check and nothing else: for the tests that plant
+    a non-finite value on purpose and compare where it goes with the oracle (non-finite values are
+    data to the kernel, not faults; tests/test_gpu_sweep_bits.py). Leave it on everywhere else.
+
+    What is bitwise (tests/test_gpu_tb_kernels.py): the stored layers and both error keys, in fp64 and
+    fp32, equal ``ops.reference.chained_layers`` / ``chained_delta_layers`` (exact form) and
+    ``chained_layers_fma`` / ``chained_delta_layers_fma`` with ``rel_key_fma`` (``fma=True``)."""
     ghost = depth if ghost is None else ghost
     gv = _check_grid_g(ghost, A, B, O0, O1)
-    if not (bool(torch.isfinite(A).all()) and bool(torch.isfinite(B).all())):
+    if check_finite and not (bool(torch.isfinite(A).all()) and bool(torch.isfinite(B).all())):
         raise ValueError("k_tbn: A and B must be finite everywhere (ghost and padding cells included)")
     if ghost < depth:
         raise ValueError("k_tbn needs ghost depth >= depth")
@@ -215,7 +229,8 @@ def tb3_sweep(A, B, D, E, boxes, *, first: bool, cdom, err_i, tx, ty, tz, coefs_
               coefs_e, err_c, err_d, err_e, rows: int = 2, waves: int = 8, chunk: int = 0,
               ghost: int = 3, fma: bool = False) -> None:
     """One three-layer sweep (k_tb3): C = u^m (errors only), D = u^{m+1}, E = u^{m+2}.
-    ``fma``: the --math fma instantiation (coef/h^2 folded; not bitwise with the exact form)."""
+    ``fma``: the --math fma instantiation (coef/h^2 folded; not bitwise with the exact form, but a fixed
+    sequence of rounded operations of its own: bitwise equal to ``ops.reference.chained_layers_fma``)."""
     gv = _check_grid_g(ghost, A, B, D, E)
     if ghost < 3:
         raise ValueError("k_tb3 needs ghost depth >= 3")

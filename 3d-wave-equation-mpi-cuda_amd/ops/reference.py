@@ -69,12 +69,19 @@ def tables(N: int, K: int, L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref"
 
 
 def solve(N: int, K: int, L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref",
-          phase: float = 0.0, dtype=torch.float64, device="cpu", scheme: str = "leapfrog"):
+          phase: float = 0.0, dtype=torch.float64, device="cpu", scheme: str = "leapfrog", math: str = "exact"):
     """Whole single-domain solve in PyTorch; returns (max_abs[0..K], max_rel[0..K], u_K).
+    math "fma": the FMA form (``solve_fma``; CPU only), bit for bit the ``cpu`` backend's ``math="fma"``.
 
     Storage: x has ghost planes (local = global + 1), y/z none (faces are Dirichlet).
     scheme "delta": increment form, d^n = d^{n-1} + coef*lap u^{n-1}, u^n = u^{n-1} + d^n.
     """
+    if math == "fma":
+        if str(device) != "cpu":
+            raise ValueError("the FMA-form oracle runs on the CPU")
+        return solve_fma(N, K, L, T, pi, phase, dtype, scheme)
+    if math != "exact":
+        raise ValueError(f"math must be 'exact' or 'fma', not {math!r}")
     sx, sy, sz, ct, c = tables(N, K, L, T, pi, phase, dtype)
     sx, sy, sz = sx.to(device), sy.to(device), sz.to(device)
     g = [torch.zeros(N + 3, N + 1, N + 1, dtype=dtype, device=device) for _ in range(3)]
@@ -175,6 +182,297 @@ def chained_layers(A, B, nlayers: int, *, first: bool, mask, hx2, hy2, hz2, coef
         out.append(v)
         prev2, prev1 = prev1, v
     return out
+
+
+# ---- the --math fma form (csrc/stencil_math.hpp, FMA section), bit for bit ------------------------
+#
+# The FMA form is a fixed sequence of individually rounded operations, some of them fused
+# multiply-adds. PyTorch has no elementwise fma, so ``fma`` below builds the correctly rounded result
+# from error-free transformations; everything else is written out from stencil_math.hpp's comments
+# (second_diff, coef_lap_fma, fm_kc, leap_fm, leap_fm_masked) and from the launchers' coefficient
+# rule. Nothing here calls the native module. ``variant`` swaps in a subtly different arithmetic, for
+# the sensitivity tests alone: "unfused" (every fma as a rounded product and a rounded add), "swap"
+# (the fp32 composition on fp64 data and the reverse), "fold2c" (the chain with 2c folded into kc
+# that stencil_math.hpp records as rejected).
+
+FMA_VARIANTS = (None, "unfused", "swap", "fold2c")
+
+
+def _two_sum(a, b):
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _odd_sum(a, b):
+    """a + b rounded to odd (float64): the rounded sum, moved one step towards the exact sum where
+    the sum is inexact and its last bit is even."""
+    s, e = _two_sum(a, b)
+    iv = s.contiguous().view(torch.int64)
+    step = torch.where((e > 0) == (s > 0), torch.ones_like(iv), -torch.ones_like(iv))
+    fix = (e != 0) & ((iv & 1) == 0)
+    return torch.where(fix, iv + step, iv).view(torch.float64)
+
+
+def _split(a):
+    t = a * 134217729.0  # 2^27 + 1 (Veltkamp)
+    hi = t - (t - a)
+    return hi, a - hi
+
+
+def fma(a, b, c) -> torch.Tensor:
+    """``RN(a b + c)`` with one rounding, elementwise, for float64 or float32 tensors (broadcast like
+    ``a * b + c``; Python scalars are taken in the tensors' type).
+
+    float64: TwoProduct (Veltkamp split) gives ``a b = ph + pl`` exactly, TwoSum ``c + ph = sh + sl``
+    exactly, and ``RN(sh + RO(sl + pl))`` with RO the sum rounded to odd is the correctly rounded result
+    (Boldo and Melquiond). float32: the product is exact in float64 (48 bits), ``RO(ab + c)`` in float64
+    keeps 53 >= 2 * 24 + 2 bits, and its cast to float32 is the correctly rounded result.
+
+    Range: correctly rounded as long as the product neither overflows nor loses bits to underflow
+    and, in float64, the split does not overflow: float64 ``|a|, |b| < 2^996`` and either ``a b = 0`` or
+    ``2^-968 <= |a b| < 2^1023``; float32 whenever ``a b`` and ``c`` are normal float64 numbers or zero (every
+    float32 input) and the result does not overflow. Where an operand or the plain ``a * b + c`` is not
+    finite, and where a factor is zero (the product is then exact), the result is ``a * b + c``: infinities,
+    NaNs and the signs of zeros as the hardware instruction gives them."""
+    ts = [t for t in (a, b, c) if isinstance(t, torch.Tensor)]
+    if not ts or any(t.dtype != ts[0].dtype for t in ts) or ts[0].dtype not in (torch.float32, torch.float64):
+        raise TypeError("fma: float32 or float64 tensors of one type")
+    dt = ts[0].dtype
+    a, b, c = (t if isinstance(t, torch.Tensor) else torch.tensor(t, dtype=dt, device=ts[0].device) for t in (a, b, c))
+    a, b, c = torch.broadcast_tensors(a, b, c)
+    plain = a * b + c
+    if dt == torch.float32:
+        soft = _odd_sum(a.double() * b.double(), c.double()).to(torch.float32)
+    else:
+        ph = a * b
+        ah, al = _split(a)
+        bh, bl = _split(b)
+        pl = ((ah * bh - ph) + ah * bl + al * bh) + al * bl
+        sh, sl = _two_sum(c, ph)
+        soft = sh + _odd_sum(sl, pl)
+    ok = torch.isfinite(a) & torch.isfinite(b) & torch.isfinite(c) & torch.isfinite(plain) & (a != 0) & (b != 0)
+    return torch.where(ok, soft, plain)
+
+
+def _fma_v(a, b, c, variant):
+    return a * b + c if variant == "unfused" else fma(a, b, c)
+
+
+def fma_coefs(coef, hx2, hy2, hz2, dtype) -> tuple:
+    """(cx, cy, cz, kc) as the launchers form them: ``c_d = T(coef / h_d^2)``, the quotient in double and
+    then cast, and ``kc = fm_kc(cx, cy, cz) = -2 ((cx + cy) + cz)`` from the cast values, in T."""
+    cx, cy, cz = (torch.tensor(float(coef) / float(h), dtype=torch.float64).to(dtype) for h in (hx2, hy2, hz2))
+    return cx, cy, cz, -2 * ((cx + cy) + cz)
+
+
+def _nbrs(u):
+    i = slice(1, -1)
+    return (u[i, i, i], u[:-2, i, i], u[2:, i, i], u[i, :-2, i], u[i, 2:, i], u[i, i, :-2], u[i, i, 2:])
+
+
+def _second_diff(m, c, p, f32: bool):
+    """second_diff: fp64 ``fma(-2, c, m + p)`` (2c is exact, so one rounded sum and one rounded
+    difference); fp32 ``(m - c) + (p - c)``."""
+    return (m - c) + (p - c) if f32 else (m + p) - 2 * c
+
+
+def coef_lap_fma_field(u, fc, variant=None) -> torch.Tensor:
+    """coef_lap_fma on ``u[1:-1, 1:-1, 1:-1]``: ``fma(cx, sx, fma(cy, sy, cz sz))`` with the second
+    differences of the grid's type. ``fc`` = ``fma_coefs``."""
+    c, xm, xp, ym, yp, zm, zp = _nbrs(u)
+    f32 = (u.dtype == torch.float32) != (variant == "swap")
+    sx, sy, sz = _second_diff(xm, c, xp, f32), _second_diff(ym, c, yp, f32), _second_diff(zm, c, zp, f32)
+    return _fma_v(fc[0], sx, _fma_v(fc[1], sy, fc[2] * sz, variant), variant)
+
+
+def taylor_fma_field(u1, fc, variant=None) -> torch.Tensor:
+    """The Taylor start in FMA form: ``c + coef_lap_fma`` (fc from ``coef_first``)."""
+    return u1[1:-1, 1:-1, 1:-1] + coef_lap_fma_field(u1, fc, variant)
+
+
+def leap_fma_field(u1, u2, fc, m=None, variant=None) -> torch.Tensor:
+    """leap_fm on ``u1[1:-1, 1:-1, 1:-1]``. fp64: ``t = cz (zm + zp)``, ``t = fma(cy, ym + yp, t)``,
+    ``t = fma(cx, xm + xp, t)``, ``t = fma(kc, c, t)``, result ``(2c - u2) + t``; fp32: ``(2c - u2) +
+    coef_lap_fma``. ``2c - u2`` is ``fma(2, c, -u2)``: 2c is exact, so the difference carries the one
+    rounding. ``m`` (a 0/1 grid like the result): leap_fm_masked, ``fma(t, m, 2c - u2)``."""
+    c, xm, xp, ym, yp, zm, zp = _nbrs(u1)
+    cx, cy, cz, kc = fc
+    base = 2 * c - u2[1:-1, 1:-1, 1:-1]
+    chain = (u1.dtype == torch.float64) != (variant == "swap")
+    if variant == "fold2c":  # the rejected single chain: kc' = kc + 2, no separate 2c - u2
+        t = cz * (zm + zp)
+        t = fma(cy, ym + yp, t)
+        t = fma(cx, xm + xp, t)
+        t = fma(kc + 2, c, t)
+        return t - u2[1:-1, 1:-1, 1:-1] if m is None else fma(t, m, -u2[1:-1, 1:-1, 1:-1])
+    if chain:
+        t = cz * (zm + zp)
+        t = _fma_v(cy, ym + yp, t, variant)
+        t = _fma_v(cx, xm + xp, t, variant)
+        t = _fma_v(kc, c, t, variant)
+    else:
+        t = coef_lap_fma_field(u1, (cx, cy, cz), variant)
+    return base + t if m is None else _fma_v(t, m, base, variant)
+
+
+def _cmask(mask, dtype):
+    """The kernels' 0/1 factor of the computed-domain mask on the interior nodes."""
+    m = mask.clone()
+    m[0], m[-1], m[:, 0], m[:, -1], m[:, :, 0], m[:, :, -1] = (False,) * 6
+    return m[1:-1, 1:-1, 1:-1].to(dtype)
+
+
+def chained_layers_fma(A, B, nlayers: int, *, first: bool, mask, hx2, hy2, hz2, coefs, variant=None):
+    """``chained_layers`` in FMA form, as k_tbn / k_tb3 ``fma=True`` compute it. ``coefs[0]`` is the Taylor
+    start's coefficient when ``first``; every other layer uses ``coefs[1]`` (the sweeps keep one triple for
+    the non-first layers). The mask is a product, as in the kernels (``upd`` in hip_tbn.hip): layers 0 and
+    1 multiply the result by m, later layers carry m inside the last fma (leap_fm_masked), so a
+    non-finite value on a masked node gives NaN there, not 0. h^2 and coefs are taken as doubles."""
+    dt = A.dtype
+    m = _cmask(mask, dt)
+    f0 = fma_coefs(coefs[0], hx2, hy2, hz2, dt)
+    f1 = fma_coefs(coefs[1], hx2, hy2, hz2, dt)
+    out, prev2, prev1 = [], B, A
+    for q in range(nlayers):
+        v = torch.zeros_like(A)
+        if first and q == 0:
+            val = taylor_fma_field(prev1, f0, variant) * m
+        elif q <= 1:
+            val = leap_fma_field(prev1, prev2, f1, None, variant) * m
+        else:
+            val = leap_fma_field(prev1, prev2, f1, m, variant)
+        v[1:-1, 1:-1, 1:-1] = val
+        out.append(v)
+        prev2, prev1 = prev1, v
+    return out
+
+
+def chained_delta_layers_fma(A, Dm1, nlayers: int, *, first: bool, mask, hx2, hy2, hz2, coefs, variant=None):
+    """``chained_delta_layers`` in FMA form (k_tbn ``delta=True, fma=True``): ``d_l = d_{l-1} + coef_lap_fma
+    (U_{l-1})`` (layer 0 of the first sweep: coef_lap_fma alone, from ``coefs[0]``), then ``d_l = d_l m`` and
+    ``U_l = (U_{l-1} + d_l) m``. Returns ([U_0 .. U_{n-1}], d_{n-1})."""
+    dt = A.dtype
+    m = _cmask(mask, dt)
+    f0 = fma_coefs(coefs[0], hx2, hy2, hz2, dt)
+    f1 = fma_coefs(coefs[1], hx2, hy2, hz2, dt)
+    inner = (slice(1, -1),) * 3
+    out, u, d = [], A, Dm1
+    for q in range(nlayers):
+        t = first and q == 0
+        l_ = coef_lap_fma_field(u, f0 if t else f1, variant)
+        dn = torch.zeros_like(A)
+        dn[inner] = (l_ if t else d[inner] + l_) * m
+        un = torch.zeros_like(A)
+        un[inner] = (u[inner] + dn[inner]) * m
+        out.append(un)
+        u, d = un, dn
+    return out, d
+
+
+def div_const(a: torch.Tensor, h2: float) -> torch.Tensor:
+    """The kernels' division by a constant (csrc/stencil_math.hpp div_const), operation for operation:
+    ``b = T(h2)``, ``y = RN(1 / b)``, ``q = a y``, ``r = fma(-q, b, a)``, ``q' = fma(r, y, q)``. Equal to ``a / b`` on
+    ``tests/bits.py division_range``; an infinite numerator gives NaN (true division: the infinity) and
+    ``-0`` gives ``+0``, which is why the oracle of non-finite fields divides like the kernels."""
+    b = torch.tensor(h2, dtype=a.dtype)
+    y = torch.ones((), dtype=a.dtype) / b
+    q = a * y
+    return fma(fma(-q, b, a), y, q)
+
+
+def laplace7_cr(u: torch.Tensor, hx2, hy2, hz2) -> torch.Tensor:
+    """``laplace7`` with ``div_const`` in place of the three divisions (laplace7_cr in stencil_math.hpp)."""
+    c = u[1:-1, 1:-1, 1:-1]
+    two_c = 2 * c
+    ans = torch.zeros_like(c)
+    ans = ans + div_const(u[:-2, 1:-1, 1:-1] - two_c + u[2:, 1:-1, 1:-1], hx2)
+    ans = ans + div_const(u[1:-1, :-2, 1:-1] - two_c + u[1:-1, 2:, 1:-1], hy2)
+    ans = ans + div_const(u[1:-1, 1:-1, :-2] - two_c + u[1:-1, 1:-1, 2:], hz2)
+    return ans
+
+
+def chained_layers_kernel(A, B, nlayers: int, *, first: bool, mask, hx2, hy2, hz2, coefs):
+    """``chained_layers`` (exact form) with the two things k_tbn does differently on fields that are not
+    finite or not in range: the constant division (``laplace7_cr``) and the mask as a product, ``upd`` in
+    csrc/hip_tbn.hip: layers 0 and 1 ``value m``, later layers ``(2c - u2) + (coef m) lap``. So ``0 * NaN`` is
+    NaN on a masked node, and an infinite numerator gives NaN, as on the device. On finite in-range
+    fields it equals ``chained_layers`` up to the sign of a masked zero."""
+    dt = A.dtype
+    m = _cmask(mask, dt)
+    out, prev2, prev1 = [], B, A
+    inner = (slice(1, -1),) * 3
+    for q in range(nlayers):
+        lap = laplace7_cr(prev1, hx2, hy2, hz2)
+        c = prev1[inner]
+        coef = torch.tensor(coefs[q], dtype=dt)
+        if first and q == 0:
+            val = (c + coef * lap) * m
+        elif q <= 1:
+            val = ((2 * c - prev2[inner]) + coef * lap) * m
+        else:
+            val = (2 * c - prev2[inner]) + (coef * m) * lap
+        v = torch.zeros_like(A)
+        v[inner] = val
+        out.append(v)
+        prev2, prev1 = prev1, v
+    return out
+
+
+def rel_key_fma(d: torch.Tensor, tx, ty, tz, ct: float, init: float = -100.0) -> float:
+    """The --math fma relative-error key (RelMax in csrc/device_common.hpp), operation for operation:
+    ``w = (1 / |sx sy|) (1 / |sz|)`` from the reciprocal tables (each a correctly rounded quotient of 1),
+    the NaN-ignoring maximum of ``|d w|``, then times ``T(1 / |ct|)`` (the quotient in double, cast). ``d`` =
+    ``u - f`` on the error nodes, tx / ty / tz their table slices; the initial value comes back untouched."""
+    dt = d.dtype
+    one = torch.ones((), dtype=dt)
+    w = (one / (tx[:, None, None] * ty[None, :, None]).abs()) * (one / tz.abs())[None, None, :]
+    p = (d * w).abs()
+    neg = torch.tensor(-math.inf, dtype=dt)
+    mx = torch.where(torch.isnan(p), neg, p).max() if p.numel() else neg
+    if not bool(mx > init):
+        return float(init)
+    return (mx * torch.tensor(1.0 / abs(float(ct)), dtype=torch.float64).to(dt)).item()
+
+
+def solve_fma(N: int, K: int, L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", phase: float = 0.0,
+              dtype=torch.float64, scheme: str = "leapfrog", variant=None):
+    """``solve`` in FMA form (the ``cpu`` backend's ``math="fma"``): the Taylor start ``c + coef_lap_fma`` with
+    the coefficients of ``coef_first``, then leap_fm; scheme "delta": ``d = d + coef_lap_fma``, ``u = c + d``."""
+    sx, sy, sz, ct, c = tables(N, K, L, T, pi, phase, dtype)
+    g = [torch.zeros(N + 3, N + 1, N + 1, dtype=dtype) for _ in range(3)]
+
+    def wrap(u):
+        u[0] = u[N]
+        u[N + 2] = u[2]
+
+    f0 = analytic(sx, sy, sz, ct[0])
+    g[0][1:N + 2] = f0
+    wrap(g[0])
+    ma, mr = max_errors(f0, f0)
+    abs_e, rel_e = [ma], [mr]
+    fc1 = fma_coefs(c["coef_first"], c["hx2"], c["hy2"], c["hz2"], dtype)
+    fcn = fma_coefs(c["coef"], c["hx2"], c["hy2"], c["hz2"], dtype)
+    d = None
+    box = (slice(0, N + 1), slice(0, N - 1), slice(0, N - 1))  # interior index of x all, y/z 1..N-1
+    for n in range(1, K + 1):
+        u1, u2, u = g[(n + 2) % 3], g[(n + 1) % 3], g[n % 3]
+        u.zero_()
+        if scheme == "delta":
+            l_ = coef_lap_fma_field(u1, fc1 if n == 1 else fcn, variant)[box]
+            d = l_ if n == 1 else d + l_
+            vals = u1[1:N + 2, 1:N, 1:N] + d
+        elif n == 1:
+            vals = taylor_fma_field(u1, fc1, variant)[box]
+        else:
+            vals = leap_fma_field(u1, u2, fcn, None, variant)[box]
+        u[1:N + 2, 1:N, 1:N] = vals
+        wrap(u)
+        f = analytic(sx[1:N], sy[1:N], sz[1:N], torch.tensor(ct[n], dtype=dtype).item())
+        ma, mr = max_errors(u[2:N + 1, 1:N, 1:N], f)
+        abs_e.append(ma)
+        rel_e.append(mr)
+    return abs_e, rel_e, g[K % 3]
 
 
 # ---- heterogeneous medium: u_tt = c^2 (lap u + f) -----------------------------------------

@@ -4,6 +4,7 @@
 A plain helper module (``from bits import ...``): no fixtures, no pytest hooks.
 """
 import math
+from fractions import Fraction
 
 import torch
 
@@ -11,6 +12,23 @@ _INT = {torch.float32: torch.int32, torch.float64: torch.int64}
 # precision p (bits of the significand, the hidden one included), emin, emax
 _FORMAT = {torch.float32: (24, -126, 127), torch.float64: (53, -1022, 1023)}
 _I64_MAX = 2 ** 63 - 1
+
+
+def round_fraction(x: Fraction, p: int, emin: int) -> Fraction:
+    """x rounded to the nearest binary number of p significant bits (ties to even; below ``2^emin`` the
+    fixed subnormal spacing ``2^(emin - p + 1)``), by integer arithmetic alone. No overflow handling."""
+    if x == 0:
+        return Fraction(0)
+    s, a = (-1 if x < 0 else 1), abs(x)
+    e = a.numerator.bit_length() - a.denominator.bit_length()
+    if Fraction(2) ** e > a:
+        e -= 1
+    q = max(e, emin) - (p - 1)  # the exponent of one unit in the last place
+    scaled = a / Fraction(2) ** q
+    n, r = divmod(scaled.numerator, scaled.denominator)
+    if 2 * r > scaled.denominator or (2 * r == scaled.denominator and n & 1):
+        n += 1
+    return s * n * Fraction(2) ** q
 
 
 def _int_view(t: torch.Tensor) -> torch.Tensor:

@@ -1,12 +1,21 @@
 """HIP kernel numerics vs the plain-PyTorch reference (ops/reference.py).
 
-fp64 results must be *bitwise* equal (both sides round every operation in the reference's
-order, no FMA contraction); fp32 within a few ulps of the fp32 torch reference.
+The single-step kernels (k_march, k_naive) are compared bit for bit in fp64 and in fp32
+(``bits.assert_same_bits``, no tolerance): both sides round every operation in the reference's order,
+no FMA contraction, and the kernels' constant division equals true division on the numerators of
+these cases (tests/test_sweep_bits_cpu.py checks each against ``bits.division_range``). The fused error
+keys equal the oracle's maxima formed in the grid's own type. The --math fma instantiation of k_march
+("marchf", "march2f") is compared the same way with the FMA-form oracle (``reference.taylor_fma_field``,
+``leap_fma_field``); its relative error is RelArg's, so both keys equal ``reference.max_errors``.
 """
 import math
 
 import pytest
 import torch
+
+from bits import assert_same_bits
+from sweep_cases import STEP_CASES, STEP_COEFS, step_inputs
+
 
 pytestmark = pytest.mark.gpu
 
@@ -23,57 +32,72 @@ def _tables(shape, dtype, seed):
     return [(torch.rand(n, generator=g, dtype=torch.float64) * 2 - 1).to(dtype).to(DEV) for n in shape]
 
 
-def _ref_errors(u_box, f_box):
-    from wave3d.ops import reference
+def _check_step(u, err, exp_box, box, ei, tx, ty, tz, ct, dtype):
+    from wave3d.ops import kernels, reference
 
-    return reference.max_errors(u_box.double().cpu(), f_box.double().cpu())
+    shape = tuple(u.shape)
+    i0, i1, j0, j1, k0, k1 = box
+    got = u[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1].cpu()
+    assert_same_bits(got, exp_box)
+    # nodes outside the box untouched
+    mask = torch.ones(shape, dtype=torch.bool)
+    mask[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1] = False
+    assert bool((u.cpu()[mask] == -7.0).all())
+    # fused errors, formed in the grid's type
+    cast = lambda v: torch.tensor(v, dtype=dtype).item()  # noqa: E731
+    f = reference.analytic(tx.cpu(), ty.cpu(), tz.cpu(), cast(ct))
+    fb = f[ei[0]:ei[1] + 1, j0:j1 + 1, k0:k1 + 1]
+    assert fb.dtype == dtype
+    ea, er = reference.max_errors(exp_box[ei[0] - i0:, :, :], fb)
+    (ga, gr, bad), = kernels.decode_err(err)
+    assert ga == ea and gr == er, (ga, ea, gr, er)
+    assert not bad
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
 @pytest.mark.parametrize("kernel", ["march", "naive"])
 @pytest.mark.parametrize("first", [False, True])
-@pytest.mark.parametrize("shape,box,chunk", [
-    ((13, 21, 70), (1, 11, 1, 19, 1, 68), 0),      # whole owned region
-    ((13, 21, 70), (2, 10, 3, 17, 2, 66), 3),      # interior sub-box, short chunks
-    ((9, 40, 131), (1, 7, 5, 33, 60, 129), 2),     # k box across 64-lane tiles
-    ((6, 7, 9), (1, 4, 1, 5, 1, 7), 0),            # tiny
-])
+@pytest.mark.parametrize("shape,box,chunk", STEP_CASES)
 def test_step_matches_reference(C, dtype, kernel, first, shape, box, chunk):
     from wave3d.ops import kernels, reference
 
-    u1 = _rand_grid(shape, dtype, 1)
-    u2 = _rand_grid(shape, dtype, 2)
+    u1, u2, tx, ty, tz = (t.to(DEV) for t in step_inputs(shape, dtype))
     u = torch.full(shape, -7.0, dtype=dtype, device=DEV)
-    tx, ty, tz = _tables(shape, dtype, 3)
-    hx2, hy2, hz2, coef, ct = 0.011, 0.013, 0.017, 3.1e-4, -0.83
+    hx2, hy2, hz2, coef, ct = STEP_COEFS
     err = kernels.new_err(1)
     ei = (box[0] + 1, box[1])  # exclude the first box row from the error domain
     kernels.step(u1, u2, u, box, first=first, err_i=ei, tx=tx, ty=ty, tz=tz,
-                 coefs=(hx2, hy2, hz2, coef, ct), err=err, kernel=kernel, chunk=chunk)
+                 coefs=STEP_COEFS, err=err, kernel=kernel, chunk=chunk)
     torch.cuda.synchronize()
     cast = lambda v: torch.tensor(v, dtype=dtype).item()  # noqa: E731
     exp_box = reference.step(u1.cpu(), u2.cpu(), box, first=first, hx2=cast(hx2), hy2=cast(hy2),
                              hz2=cast(hz2), coef=cast(coef))
+    _check_step(u, err, exp_box, box, ei, tx, ty, tz, ct, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("kernel", ["marchf", "march2f"])
+@pytest.mark.parametrize("first", [False, True])
+@pytest.mark.parametrize("shape,box,chunk", STEP_CASES)
+def test_step_fma_matches_reference(C, dtype, kernel, first, shape, box, chunk):
+    """k_march's --math fma instantiation (reachable from ``ops.kernels.step`` as "marchf" / "march2f"): the
+    Taylor start ``c + coef_lap_fma`` and leap_fm, bit for bit against the FMA-form oracle, error keys
+    included (this kernel keeps RelArg, the exact relative error)."""
+    from wave3d.ops import kernels, reference
+
+    u1, u2, tx, ty, tz = (t.to(DEV) for t in step_inputs(shape, dtype))
+    u = torch.full(shape, -7.0, dtype=dtype, device=DEV)
+    hx2, hy2, hz2, coef, ct = STEP_COEFS
+    err = kernels.new_err(1)
+    ei = (box[0] + 1, box[1])
+    kernels.step(u1, u2, u, box, first=first, err_i=ei, tx=tx, ty=ty, tz=tz,
+                 coefs=STEP_COEFS, err=err, kernel=kernel, chunk=chunk)
+    torch.cuda.synchronize()
+    fc = reference.fma_coefs(coef, hx2, hy2, hz2, dtype)
+    full = reference.taylor_fma_field(u1.cpu(), fc) if first else reference.leap_fma_field(u1.cpu(), u2.cpu(), fc)
     i0, i1, j0, j1, k0, k1 = box
-    got = u[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1].cpu()
-    if dtype == torch.float64:
-        assert torch.equal(got, exp_box)
-    else:
-        torch.testing.assert_close(got, exp_box, rtol=2e-6, atol=2e-6)
-    # nodes outside the box untouched
-    mask = torch.ones(shape, dtype=torch.bool)
-    mask[i0:i1 + 1, j0:j1 + 1, k0:k1 + 1] = False
-    assert bool((u.cpu()[mask] == -7.0).all())
-    # fused errors
-    f = reference.analytic(tx.cpu(), ty.cpu(), tz.cpu(), cast(ct))
-    fb = f[ei[0]:ei[1] + 1, j0:j1 + 1, k0:k1 + 1]
-    ea, er = _ref_errors(got[ei[0] - i0:, :, :], fb)
-    (ga, gr, bad), = kernels.decode_err(err)
-    if dtype == torch.float64:
-        assert ga == ea and gr == er
-    else:
-        assert math.isclose(ga, ea, rel_tol=1e-5) and math.isclose(gr, er, rel_tol=1e-4)
-    assert not bad
+    exp_box = full[i0 - 1:i1, j0 - 1:j1, k0 - 1:k1]
+    _check_step(u, err, exp_box, box, ei, tx, ty, tz, ct, dtype)
 
 
 def test_step_wrap_and_fused_pack(C):

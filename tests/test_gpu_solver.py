@@ -310,6 +310,15 @@ def test_tb3_fp32_resume_and_fault(C, tmp_path):
     assert bad.aborted
 
 
+def _fields(p, layer=None, **kw):
+    """(oracle field, HIP field) of one solve each."""
+    import wave3d
+
+    _, ref = wave3d.WaveSolver(p, "cpu", threads=4).solve_field(layer)
+    _, got = wave3d.WaveSolver(p, "hip", **kw).solve_field(layer)
+    return ref, got
+
+
 @pytest.mark.parametrize("kernel,ranks,layer", [("auto", 0, None), ("march2", 3, None), ("tb3", 2, None),
                                                 ("tb4", 4, 10), ("flat", 0, None)])
 def test_field_bitwise_vs_cpu(C, kernel, ranks, layer):
@@ -319,8 +328,53 @@ def test_field_bitwise_vs_cpu(C, kernel, ranks, layer):
     import wave3d
 
     p = wave3d.WaveProblem(33, timesteps=11, ic="shifted")
-    _, ref = wave3d.WaveSolver(p, "cpu", threads=4).solve_field(layer)
-    _, got = wave3d.WaveSolver(p, "hip", kernel=kernel, ranks=ranks).solve_field(layer)
+    ref, got = _fields(p, layer, kernel=kernel, ranks=ranks)
+    assert np.array_equal(got, ref)
+
+
+@pytest.mark.parametrize("name,prob,kw,layer", [
+    ("fma tb4 one rank", dict(math="fma"), dict(kernel="tb4"), None),
+    ("fma tb4 2x2x2", dict(math="fma"), dict(kernel="tb4", ranks=8, dims=[2, 2, 2]), None),
+    ("delta fp32 fma", dict(scheme="delta", dtype="fp32", math="fma"), dict(kernel="auto"), None),
+    ("delta fp64 exact", dict(scheme="delta"), dict(kernel="tb4"), None),
+    ("fp32 exact tb3", dict(dtype="fp32"), dict(kernel="tb3"), None),
+    ("tb4 layer K-1, K = 11 = 2 sweeps + 3", dict(), dict(kernel="tb4"), 10),
+    ("fma tb4 layer K-1", dict(math="fma"), dict(kernel="tb4", ranks=2), 10),
+])
+def test_field_bitwise_vs_cpu_modes(C, name, prob, kw, layer):
+    """The same comparison of whole fields (a stale halo group or one misplaced lane below the maximum
+    error would pass a comparison of per-layer maxima) in the modes the five runs above leave out:
+    --math fma (the OpenMP oracle has the FMA form operation for operation), the increment form, fp32,
+    and layer K - 1 of tb4 with K = 11, no multiple of the sweep depth (the last sweep's first stored
+    layer plus single-step tails)."""
+    import numpy as np
+
+    import wave3d
+
+    p = wave3d.WaveProblem(33, timesteps=11, ic="shifted", **prob)
+    ref, got = _fields(p, layer, **kw)
+    assert np.array_equal(got, ref), name
+    assert np.abs(ref).max() > 0.1  # a field, not zeros
+
+
+@pytest.mark.parametrize("math_", ["exact", "fma"])
+def test_field_bitwise_after_graph_replays(C, math_):
+    """Graph replay: the field after the third replay of the captured IC + time loop (four solves of one
+    session) is the oracle's, bit for bit."""
+    import numpy as np
+
+    import wave3d
+
+    p = wave3d.WaveProblem(33, timesteps=11, ic="shifted", math=math_)
+    _, ref = wave3d.WaveSolver(p, "cpu", threads=4).solve_field()
+    a = wave3d.WaveSolver(p, "hip", kernel="tb4", graph="on").args()
+    sess = C.Session(a, "hip", None)
+    for _ in range(4):
+        res = sess.solve(a)
+    assert res["graph"]
+    (b,) = sess.field(p.timesteps)
+    got = np.asarray(b["data"]).reshape(b["ext"])
+    assert list(b["off"]) == [0, 0, 0] and list(b["ext"]) == [34, 34, 34]
     assert np.array_equal(got, ref)
 
 
@@ -731,6 +785,24 @@ def test_overlap_pipe_bitwise(C, dims, kernel, math, scheme):
         assert r.max_abs == ref.max_abs
         if math == "exact":
             assert r.max_rel == ref.max_rel
+    # The final field as well (a stale halo group below the maximum error would pass the maxima), on
+    # the smallest grid this decomposition pipelines with the default four slabs: every rank needs
+    # slabs x (depth + 1) planes in x (sizing.cpp pipe_slabs(): N = 39 for tb4 on two x ranks, 79 on
+    # four, 31 for tb3), found from the plan itself. K = 43 leaves a tail of single steps.
+    import numpy as np
+
+    def prob(N):
+        return wave3d.WaveProblem(N, Lx=1.3, Ly="pi", Lz=2.0, timesteps=43, ic="shifted", math=math, scheme=scheme)
+
+    def solver(N):
+        return wave3d.WaveSolver(prob(N), "hip", ranks=P, dims=list(dims), overlap="pipe", kernel=kernel)
+
+    N = next(n for n in range(8, 161) if C.memory_plan(solver(n).args(), P)["pipe_slabs"] == 4)
+    assert N < 160
+    res, got = solver(N).solve_field()
+    assert res.extra["overlap_order_run"] == "pipe"
+    _, want = wave3d.WaveSolver(prob(N), "cpu", threads=8).solve_field()
+    assert np.array_equal(got, want)
 
 
 def test_overlap_pipe_slab_counts_and_refusal(C):
