@@ -26,7 +26,7 @@ def __getattr__(name):
         return getattr(wave, name)
     if name in ("MediumProblem", "MediumSolver", "MediumResult", "MediumGradient", "MediumBorn", "ricker",
                 "sponge_taper", "gradient_levels", "best_gradient_segment", "born_levels", "cfl_limit",
-                "precondition", "grid_position"):
+                "precondition", "grid_position", "dft_bins", "gradient_dft_levels"):
         from .models import medium
 
         return getattr(medium, name)

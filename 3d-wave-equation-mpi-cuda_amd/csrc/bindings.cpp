@@ -367,6 +367,27 @@ void k_face_corr(uintptr_t a, uintptr_t v, uintptr_t acc, const std::vector<i64>
                         (hipStream_t)stream);
 }
 
+// Fourier accumulation (k_dft_acc): re[f] += u c_row[f], im[f] += u s_row[f] at the box nodes; re / im: one
+// level pointer per frequency, c_row / s_row: that many device values each; grid view as above. What the
+// launcher rejects is a ValueError here, like what ops.kernels.dft_accumulate rejects in front of it.
+template <class T>
+void k_dft_acc(uintptr_t u, const std::vector<uintptr_t>& re, const std::vector<uintptr_t>& im, uintptr_t c_row,
+               uintptr_t s_row, const std::vector<i64>& g, const std::vector<std::vector<int>>& boxes, int chunk,
+               uintptr_t stream) {
+    try {
+        W3D_REQUIRE(re.size() == im.size(), "dft accumulation: one im level per re level");
+        std::vector<Box> bx;
+        for (auto& e : boxes) bx.push_back(tobox(e));
+        std::vector<T*> r, i;
+        for (auto q : re) r.push_back(P<T>(q));
+        for (auto q : im) i.push_back(P<T>(q));
+        launch_dft_acc<T>(P<T>(u), r.data(), i.data(), int(r.size()), P<T>(c_row), P<T>(s_row), gview(g), bx.data(),
+                          int(bx.size()), chunk, (hipStream_t)stream);
+    } catch (const Error& e) {
+        throw py::value_error(e.what());
+    }
+}
+
 // nodes: device int32 [n][3] of (i, j, k); g / out: n device values
 template <class T>
 void k_inject(uintptr_t u, uintptr_t m, const std::vector<i64>& g, uintptr_t nodes, uintptr_t vals, int n,
@@ -669,6 +690,9 @@ PYBIND11_MODULE(_wave3d_C, m) {
 #undef W3D_STEP_MEDIUM_ARGS
     m.def("k_face_corr_f64", &k_face_corr<double>);
     m.def("k_face_corr_f32", &k_face_corr<float>);
+    m.def("k_dft_acc_f64", &k_dft_acc<double>);
+    m.def("k_dft_acc_f32", &k_dft_acc<float>);
+    m.attr("dft_nf") = kDftNF;
     m.def("k_inject_f64", &k_inject<double>);
     m.def("k_inject_f32", &k_inject<float>);
     m.def("k_record_f64", &k_record<double>);

@@ -143,6 +143,23 @@ template <class T>
 void launch_face_corr(const T* a, const T* v, T* acc, const GridView& gv, const Box* boxes, int nbox,
                       const double h2[3], int chunk, hipStream_t s);
 
+// On-the-fly Fourier accumulation (hip_medium_dft.hip, k_dft_acc): for f = 0 .. nf - 1 in ascending order
+// re[f] = re[f] + u c_row[f] and im[f] = im[f] + u s_row[f] at the nodes of `nbox` boxes, every product
+// rounded before its add (ops/reference.py dft_accumulate; fp64 and fp32 results are bitwise equal to it).
+// c_row / s_row: nf device values each, one row of the twiddle table cos(2 pi f p tau) / -sin(2 pi f p tau)
+// uploaded once, so no host value travels with a step. u and the 2 nf accumulators are levels with the
+// strides of `gv` (one ghost layer); the box contract is k_march_m's (boxes inside the owned region). u is
+// never written, the accumulators only at the box nodes. A launch carries up to kDftNF frequencies on one
+// read of u and a longer list is split into launches: with 4, u is 8 of a launch's 136 B per node in fp64,
+// so 8 frequencies per launch would save 3 % of the traffic at most and need twice the registers in flight
+// per lane. Rejected before any launch: nf < 1, a null pointer, a box that touches a storage edge, strides
+// smaller than the grid, and an accumulator that shares memory with u or with another accumulator. Per
+// node in fp64: 8 + 32 nf B for nf <= kDftNF (u read; re, im read and written), 4 + 16 nf B in fp32.
+constexpr int kDftNF = 4;
+template <class T>
+void launch_dft_acc(const T* u, T* const* re, T* const* im, int nf, const T* c_row, const T* s_row,
+                    const GridView& gv, const Box* boxes, int nbox, int chunk, hipStream_t s);
+
 // Off-grid sources and receivers (hip_medium_points.hip): positions between the nodes act through
 // 8 slots per axis (ops/reference.py interp_tables; the slots carry the periodic wrap in x and the odd
 // reflection at the y/z faces already, as storage indices and signed weights).

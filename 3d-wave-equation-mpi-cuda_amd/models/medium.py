@@ -212,6 +212,32 @@ class MediumResult:
     abort_layer: int = -1
     abort_reason: str = ""
     extra: dict = field(default_factory=dict)
+    # run(frequencies=...): complex [F, N+1, N+1, N+1] on the CPU, sum_n u^n exp(-i 2 pi f n tau) over the
+    # sampled layers (the Dirichlet faces 0)
+    spectra: torch.Tensor | None = None
+
+
+def dft_bins(problem: MediumProblem, every: int = 1, pairs: bool = False):
+    """``(frequencies, weights)``, float64 tensors, of the half spectrum of the sequence the on-the-fly
+    transform samples with ``dft_every = every``: p = 0, e, 2e, ... <= K, what
+    :meth:`MediumSolver.run` transforms, or with ``pairs=True`` p = e, 2e, ... <= K - 1, what
+    :meth:`MediumSolver.gradient_dft` pairs. With P samples ``f_k = k / (P e tau)`` for k = 0 .. P // 2 and
+    the weights ``2 / P``, except ``1 / P`` for k = 0 and, when P is even, for k = P / 2. For real sequences
+    a, b over those samples and their transforms A, B at these bins
+    ``sum_p a_p b_p = sum_k w_k (Re A_k Re B_k + Im A_k Im B_k)``."""
+    from ..ops import reference
+
+    e = reference.check_dft_every(every)
+    K = problem.timesteps
+    P = (K - 1) // e if pairs else K // e + 1
+    if P < 1:
+        raise ValueError(f"dft_every = {e} leaves no sample: the pairs are p = e, 2e, ... <= K - 1 = {K - 1}")
+    k = torch.arange(P // 2 + 1, dtype=torch.float64)
+    w = torch.full((P // 2 + 1,), 2.0 / P, dtype=torch.float64)
+    w[0] = 1.0 / P
+    if P % 2 == 0:
+        w[P // 2] = 1.0 / P
+    return k / (P * e * problem.tau), w
 
 
 class MediumSolver:
@@ -344,8 +370,28 @@ class MediumSolver:
             return {}
         return dict(interp=self.interp, **counts)
 
-    def run(self) -> MediumResult:
-        return self._run_cpu() if self.backend == "cpu" else self._run_hip()
+    def run(self, frequencies=None, dft_every: int = 1) -> MediumResult:
+        """The solve. ``frequencies`` (Hz; a non-empty 1-D list of finite values >= 0) also gives
+        ``spectra``, the on-the-fly discrete Fourier transform ``sum_n u^n exp(-i 2 pi f n tau)`` over the
+        layers n = 0, e, 2e, ... <= K with e = ``dft_every`` (n = 0: the initial field; every other level
+        after its source term), a complex ``[F, N+1, N+1, N+1]`` tensor with the Dirichlet faces 0
+        (``ops.reference.solve_medium`` has the definition; :func:`dft_bins` the bins of the half spectrum).
+        Every other result keeps its bits. "hip": 2 F more levels, checked against the free device memory
+        first, and one ``k_dft_acc`` pass over them per sampled layer (``ops.kernels.dft_accumulate``).
+        None: the plain run."""
+        from ..ops import reference
+
+        if frequencies is None:
+            if dft_every != 1:
+                reference.check_dft_every(dft_every)
+            dft = None
+        else:
+            dft = (reference.check_frequencies(frequencies), reference.check_dft_every(dft_every))
+        return self._run_cpu(dft) if self.backend == "cpu" else self._run_hip(dft)
+
+    @staticmethod
+    def _dft_extra(dft, samples: int) -> dict:
+        return {} if dft is None else dict(frequencies=dft[0].tolist(), dft_every=dft[1], dft_samples=samples)
 
     def _result(self, traces, u_final, mx, ms, **kw) -> MediumResult:
         p = self.problem
@@ -353,22 +399,24 @@ class MediumSolver:
         return MediumResult(traces=traces, u_final=u_final, max_abs_u=mx, courant=p.courant, total_ms=ms,
                             mpts_per_s=rate, **kw)
 
-    def _run_cpu(self) -> MediumResult:
+    def _run_cpu(self, dft=None) -> MediumResult:
         import time
 
         from ..ops import reference
 
         p = self.problem
         t0 = time.perf_counter()
-        tr, uf, mx = reference.solve_medium(p.N, p.timesteps, p.speed2, u0=self.u0, wavelet=self.wavelet,
-                                            L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
-                                            taper=self.taper, order=p.space_order, density=p.density,
-                                            **self._points_kw())
-        return self._result(tr, uf, mx, (time.perf_counter() - t0) * 1e3,
+        kw = {} if dft is None else dict(frequencies=dft[0], dft_every=dft[1])
+        tr, uf, mx, *spec = reference.solve_medium(p.N, p.timesteps, p.speed2, u0=self.u0, wavelet=self.wavelet,
+                                                   L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
+                                                   taper=self.taper, order=p.space_order, density=p.density,
+                                                   **self._points_kw(), **kw)
+        return self._result(tr, uf, mx, (time.perf_counter() - t0) * 1e3, spectra=spec[0] if spec else None,
                             extra=dict(space_order=p.space_order, density=p.density is not None,
-                                       **self._points_extra()))
+                                       **self._points_extra(),
+                                       **self._dft_extra(dft, dft and p.timesteps // dft[1] + 1)))
 
-    def _run_hip(self) -> MediumResult:
+    def _run_hip(self, dft=None) -> MediumResult:
         from ..ops import kernels, reference
 
         p = self.problem
@@ -376,6 +424,9 @@ class MediumSolver:
         s = _HipSetup(self)
         dev, M, box, wrap, h2 = s.dev, s.M, s.box, s.wrap, s.h2
         with torch.cuda.device(dev):
+            if dft is not None:
+                F = dft[0].numel()
+                s.require_levels(4 + 2 * F + (p.density is not None), f"run() with {F} frequencies")
             lv = [s.level() for _ in range(3)]
             m = s.level()
             s.medium(m, lv[0])
@@ -387,6 +438,13 @@ class MediumSolver:
             stat = kernels.new_err(K + 1, device=dev)
             mx0 = reference.max_abs_field(lv[0][M:N + 1 + M, 1:N, 1:N])
             s.record(lv[0], traces[0])
+            samples = 0
+            if dft is not None:  # the twiddle table goes up once; a sampled layer passes one of its rows
+                every = dft[1]
+                ctab, stab = (t.contiguous().to(dev) for t in reference.dft_tables(dft[0], range(K + 1), s.c["tau"], dt))
+                sre, sim = [s.level() for _ in range(F)], [s.level() for _ in range(F)]
+                kernels.dft_accumulate(lv[0], sre, sim, box, ctab[0], stab[0])
+                samples = 1
             abort = {}
             done = K
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -402,6 +460,9 @@ class MediumSolver:
                                     stat_i=(M, N + M), wrap=wrap, variant=self.variant, taper=taper, **step_kw)
                 s.inject(u, m, g[n - 1])
                 s.record(u, traces[n])
+                if dft is not None and n % every == 0:
+                    kernels.dft_accumulate(u, sre, sim, box, ctab[n], stab[n])
+                    samples += 1
                 if self.check_every > 0 and n % self.check_every == 0:
                     bad = _nonfinite_layer(stat, n)  # one read-back: the flags of layers 0..n
                     if bad is not None:
@@ -413,11 +474,13 @@ class MediumSolver:
             ms = ev0.elapsed_time(ev1)
             dec = kernels.decode_err(stat)  # the one read-back of the statistics
             mx = [mx0] + [dec[n][0] for n in range(1, done + 1)]
-            extra = dict(space_order=p.space_order, density=p.density is not None, **s.points_extra())
+            extra = dict(space_order=p.space_order, density=p.density is not None, **s.points_extra(),
+                         **self._dft_extra(dft, samples))
             if not abort and any(d[2] for d in dec[1:]):  # ran to the end, but not on finite values
                 extra["nonfinite_layer"] = next(n for n in range(1, K + 1) if dec[n][2])
             uf = lv[done % 3][M:N + 1 + M].cpu()
-            return self._result(traces.cpu(), uf, mx, ms, extra=extra, **abort)
+            spectra = None if dft is None else reference.spectra_tensor(sre, sim, N, M)
+            return self._result(traces.cpu(), uf, mx, ms, extra=extra, spectra=spectra, **abort)
 
     # ---- misfit gradients (adjoint state; ops/reference.py has the mathematics) ------------
 
@@ -632,6 +695,148 @@ class MediumSolver:
                                              forward_ms=ev[0].elapsed_time(ev[1]), reverse_ms=ev[2].elapsed_time(ev[3]),
                                              **s.points_extra()))
 
+    # ---- the checkpoint-free spectral gradient ------------------------------------------------
+
+    def gradient_dft(self, observed, frequencies, *, weights=None, dft_every: int = 1) -> "MediumGradient":
+        """:meth:`gradient` with the time sum ``sum_n mu^{n+1} q^n`` replaced by a sum over a few
+        frequencies of the on-the-fly spectra of q and mu (``ops.reference.gradient_medium_dft`` has the
+        definition): ``acc = sum_f weights_f (Re Q_f Re M_f + Im Q_f Im M_f)`` with
+        ``Q_f = sum_p q^p exp(-i 2 pi f p tau)``, ``M_f = sum_p mu^{p+1} exp(-i 2 pi f p tau)`` over the pairs
+        p = e, 2e, ... <= K - 1, e = ``dft_every``. Neither pass keeps a level of the other, so there are no
+        checkpoints and nothing is recomputed: :func:`gradient_dft_levels` levels whatever K is.
+
+        With ``dft_bins(problem, every=e, pairs=True)`` as ``frequencies`` and ``weights`` Parseval's identity
+        makes ``grad_speed2`` the time-domain sum over those pairs up to rounding (for e = 1 that of
+        :meth:`gradient`); a few bins give the band-limited gradient of multiscale inversion. ``misfit``,
+        ``grad_wavelet`` and ``traces`` are those of :meth:`gradient` bit for bit. ``weights`` None: ones.
+
+        Preconditions: those of :meth:`gradient` (from rest, at least one receiver, ``observed`` of shape
+        ``[timesteps + 1, receivers]``), ``variant`` None and ``dft_every <= K - 1``. Every space order, a
+        density model, the sponge and off-grid points work; ``wrt_density`` and ``illumination`` are not
+        offered. "hip": the forward pass runs its steps 2 .. K in save mode into one scratch level, followed
+        by ``k_dft_acc`` at the sampled indices; the adjoint field runs in the same ring with the plain step,
+        mu^{n+1} accumulated before each sampled step."""
+        from ..ops import reference
+
+        p = self.problem
+        K = p.timesteps
+        if self.u0 is not None:
+            raise ValueError("gradient_dft() starts from rest: u0 is not supported")
+        if not self.nrec:
+            raise ValueError("gradient_dft() needs at least one receiver")
+        if self.variant is not None:
+            raise ValueError(f"gradient_dft() exists for the default kernel variant only: build the MediumSolver "
+                             f"with variant=None, not {self.variant!r}")
+        obs = torch.as_tensor(observed)
+        if tuple(obs.shape) != (K + 1, self.nrec):
+            raise ValueError(f"observed must have shape {(K + 1, self.nrec)} (timesteps + 1 x receivers), "
+                             f"not {tuple(obs.shape)}")
+        f = reference.check_frequencies(frequencies)
+        every = reference.check_dft_every(dft_every)
+        if every > K - 1:
+            raise ValueError(f"dft_every = {every} leaves no pair to correlate: the pairs are p = e, 2e, ... <= "
+                             f"K - 1 = {K - 1}")
+        if weights is not None:
+            try:
+                w = torch.as_tensor(weights, dtype=torch.float64).cpu()
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise ValueError(f"weights must be a 1-D list of numbers: {e}") from None
+            if w.dim() != 1 or w.numel() != f.numel() or not bool(torch.isfinite(w).all()):
+                raise ValueError(f"weights must be {f.numel()} finite values, one per frequency")
+            weights = w
+        obs = obs.detach().cpu()
+        if self.backend == "cpu":
+            return self._gradient_dft_cpu(obs, f, weights, every)
+        return self._gradient_dft_hip(obs, f, weights, every)
+
+    def _gradient_dft_extra(self, f, every: int, levels) -> dict:
+        p = self.problem
+        return dict(segment=None, levels=levels, recomputed_steps=0, space_order=p.space_order,
+                    density=p.density is not None, wrt_density=False, illumination=False, frequencies=f.tolist(),
+                    dft_every=every, dft_samples=(p.timesteps - 1) // every)
+
+    def _gradient_dft_cpu(self, obs, f, weights, every: int) -> "MediumGradient":
+        import time
+
+        from ..ops import reference
+
+        p = self.problem
+        t0 = time.perf_counter()
+        J, gs, gw, tr = reference.gradient_medium_dft(p.N, p.timesteps, p.speed2, obs, f, weights=weights,
+                                                      dft_every=every, wavelet=self.wavelet, taper=self.taper,
+                                                      L=(p.Lx, p.Ly, p.Lz), T=p.T, pi=p.pi, dtype=p.torch_dtype,
+                                                      order=p.space_order, density=p.density, **self._points_kw())
+        return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr,
+                              total_ms=(time.perf_counter() - t0) * 1e3,
+                              extra=dict(**self._gradient_dft_extra(f, every, None), **self._points_extra()))
+
+    def _gradient_dft_hip(self, obs, f, weights, every: int) -> "MediumGradient":
+        import time
+
+        from ..ops import kernels, reference
+
+        p = self.problem
+        N, K, dt = p.N, p.timesteps, p.torch_dtype
+        F = f.numel()
+        s = _HipSetup(self)
+        dev, c, M, box, wrap, h2, level = s.dev, s.c, s.M, s.box, s.wrap, s.h2, s.level
+        with torch.cuda.device(dev):
+            nlev = gradient_dft_levels(F, density=p.density is not None)
+            s.require_levels(nlev, f"gradient_dft() with {F} frequencies")
+            t0 = time.perf_counter()
+            lv = [level() for _ in range(3)]  # the forward ring, then the adjoint's
+            m, ql = level(), level()          # ql: the q^p of the step at hand
+            spec = [[level() for _ in range(F)] for _ in range(4)]  # Qre, Qim, Mre, Mim
+            mc = s.medium(m, lv[0])
+            step_kw, tt, taper, gsrc, g = s.step_kw, s.tt, s.taper, s.gsrc, s.g
+            ctab, stab = (t.contiguous().to(dev) for t in reference.dft_tables(f, range(K), c["tau"], dt))
+            traces = torch.zeros(K + 1, self.nrec, dtype=dt, device=dev)
+            stat = kernels.new_err(K + 1, device=dev)
+
+            # forward pass: run()'s steps; step n >= 2 saves q^{n-1}, the Laplacian it used
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record()
+            s.record(lv[0], traces[0])
+            for n in range(1, K + 1):
+                u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
+                kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=stat[3 * n:3 * n + 3],
+                                    stat_i=(M, N + M), wrap=wrap, taper=taper, lap_out=ql if n >= 2 else None,
+                                    **step_kw)
+                s.inject(u, m, g[n - 1])
+                s.record(u, traces[n])
+                if n >= 2 and (n - 1) % every == 0:
+                    kernels.dft_accumulate(ql, spec[0], spec[1], box, ctab[n - 1], stab[n - 1])
+            ev[1].record()
+            _require_finite(stat, "gradient_dft()", "forward pass")
+            tr = traces.cpu()
+            J, res = reference.misfit_medium(tr, obs)
+            finish_level = s.adjoint_points(res, lv[0], m)  # injects G rho^n, samples mu^n at the sources
+            a_dev = torch.zeros(K, self.nsrc, dtype=dt, device=dev)
+            astat = kernels.new_err(K + 1, device=dev)
+
+            # reverse pass in the same ring: mu^K into zero levels, then mu^n for n = K-1 .. 1 in lv[n % 3]
+            ev[2].record()
+            lv[(K + 1) % 3].zero_()
+            lv[K % 3].zero_()
+            finish_level(lv[K % 3], K, a_dev[K - 1])
+            for n in range(K - 1, 0, -1):
+                u1, u2, u = lv[(n + 1) % 3], lv[(n + 2) % 3], lv[n % 3]
+                if n % every == 0:  # u1 = mu^{n+1}, injected and wrapped
+                    kernels.dft_accumulate(u1, spec[2], spec[3], box, ctab[n], stab[n])
+                kernels.step_medium(u1, u2, m, u, box, first=False, h2=h2, stat=astat[3 * n:3 * n + 3],
+                                    stat_i=(M, N + M), wrap=wrap, taper=taper, **step_kw)
+                finish_level(u, n, a_dev[n - 1])
+            ev[3].record()
+            _require_finite(astat, "gradient_dft()", "adjoint pass")
+            acc = reference.finish_gradient_dft(*([t.cpu() for t in ts] for ts in spec), weights, dt)
+            gs, gw = reference.finish_gradient_medium(acc, a_dev.cpu(), gsrc, mc, tt, self.sources, N, c["tau"],
+                                                      c["hx"], c["hy"], c["hz"], M, p.density, s.source_rows_host())
+            torch.cuda.synchronize(dev)
+            ms = (time.perf_counter() - t0) * 1e3
+            return MediumGradient(misfit=J, grad_speed2=gs, grad_wavelet=gw, traces=tr, total_ms=ms,
+                                  extra=dict(**self._gradient_dft_extra(f, every, nlev),
+                                             forward_ms=ev[0].elapsed_time(ev[1]),
+                                             reverse_ms=ev[2].elapsed_time(ev[3]), **s.points_extra()))
 
     # ---- Born (linearised) modelling and Gauss-Newton products -------------------------------
 
@@ -1023,6 +1228,17 @@ def gradient_levels(K: int, segment: int, density: bool = False, wrt_density: bo
     nq = min(segment, K - 1)
     return (5 + bool(density) + bool(illumination) + nq + (nq + 1 if wrt_density else 0)
             + (2 * (nseg - 1) + 3 if nseg > 1 else 0))
+
+
+def gradient_dft_levels(F: int, density: bool = False) -> int:
+    """Number of grid levels the "hip" schedule of :meth:`MediumSolver.gradient_dft` holds for F
+    frequencies, whatever K is: one ring (3) that the forward and then the adjoint field run in, m, the
+    scratch level of q, and the real and imaginary parts of the spectra of q and of mu (4 F).
+    ``density``: one more level, the buoyancy."""
+    F = int(F)
+    if F < 1:
+        raise ValueError(f"need F >= 1 frequencies, not {F}")
+    return 5 + 4 * F + bool(density)
 
 
 def best_gradient_segment(K: int, wrt_density: bool = False, illumination: bool = False) -> int:

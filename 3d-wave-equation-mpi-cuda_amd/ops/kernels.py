@@ -5,7 +5,7 @@ device; they are passed to the native kernels as raw pointers on torch's current
 Shapes are validated here *before* any launch (the kernels index with the boxes given).
 The solver itself uses an aligned, padded layout (``csrc/hip_kernels.hpp``); these entry
 points use pitch = nz, which the kernels accept as well; the medium ops (``step_medium``,
-``face_correlation``, ``inject``, ``record``, ``inject_rows``, ``record_weighted``, ``rows_dot``) also take
+``face_correlation``, ``dft_accumulate``, ``inject``, ``record``, ``inject_rows``, ``record_weighted``, ``rows_dot``) also take
 views in that padded layout (``alloc_level``).
 
 The sweep kernels behind ``step``, ``tb3_sweep`` and ``tbn_sweep`` are tested bit for bit, stored values and
@@ -616,6 +616,54 @@ def face_correlation(a, v, acc, boxes, *, h2, chunk: int = 0) -> None:
         raise ValueError("h2 = (hx2, hy2, hz2), all > 0")
     getattr(_C(), "k_face_corr_" + _sfx(a))(a.data_ptr(), v.data_ptr(), acc.data_ptr(), gv, bl,
                                            [float(x) for x in h2], int(chunk), _stream())
+
+
+def dft_frequencies_per_launch() -> int:
+    """NF, the number of frequencies one ``k_dft_acc`` launch carries on a single read of ``u``."""
+    return int(_C().dft_nf)
+
+
+def dft_accumulate(u, re, im, boxes, c_row, s_row, *, chunk: int = 0) -> None:
+    """On-the-fly Fourier accumulation (``k_dft_acc``): ``re[f] = re[f] + u c_row[f]`` and
+    ``im[f] = im[f] + u s_row[f]`` at the nodes of ``boxes`` for every frequency f, each product rounded
+    before its add (``ops.reference.dft_accumulate`` has the scheme; fp64 and fp32 results are bitwise
+    equal to it). ``re`` / ``im``: lists of F levels; ``c_row`` / ``s_row``: contiguous 1-D device tensors of
+    exactly F values of the levels' dtype, one row of the ``ops.reference.dft_tables`` uploaded once (a
+    row of a ``[rows, F]`` table is such a tensor), so nothing synchronises. A launch carries up to
+    :func:`dft_frequencies_per_launch` frequencies on one read of ``u``; a longer list is split.
+
+    The grids are dense ``[nx][ny][nz]`` tensors or :func:`alloc_level` views with identical shapes,
+    dtypes, devices and strides; the boxes lie inside the owned region (``step_medium``'s contract).
+    ``u`` is never written, the accumulators only at the box nodes, and none of them may share memory
+    with ``u`` or with another of them. Every violation is a ``ValueError`` before any launch."""
+    if not isinstance(u, torch.Tensor) or not isinstance(re, (list, tuple)) or not isinstance(im, (list, tuple)):
+        raise ValueError("u must be a tensor, re and im lists of tensors")
+    re, im = list(re), list(im)
+    if len(re) != len(im):
+        raise ValueError(f"re and im must have one level per frequency each, not {len(re)} and {len(im)}")
+    F = len(re)
+    if F == 0:
+        raise ValueError("dft_accumulate needs at least one frequency")
+    if not all(isinstance(t, torch.Tensor) for t in re + im):
+        raise ValueError("re and im must be lists of tensors")
+    gv = _check_grid_strided(u, *re, *im)
+    for t, name in ((c_row, "c_row"), (s_row, "s_row")):
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != u.device or t.dtype != u.dtype
+                or t.dim() != 1 or not t.is_contiguous() or t.numel() != F):
+            raise ValueError(f"{name} must be a contiguous 1-D {u.dtype} tensor of {F} values on {u.device}")
+    spans = [("u", _grid_span(u))] + [(f"{n}[{f}]", _grid_span(t)) for n, ts in (("re", re), ("im", im))
+                                      for f, t in enumerate(ts)]
+    for q, (name, (t0, t1)) in enumerate(spans):
+        for other, (o0, o1) in spans[:q]:
+            if t0 < o1 and o0 < t1:
+                raise ValueError(f"{name} shares memory with {other}")
+    if isinstance(boxes[0], int):
+        boxes = [boxes]
+    if not 1 <= len(boxes) <= 7:
+        raise ValueError("1..7 boxes per launch")
+    bl = [_check_box(b, gv) for b in boxes]
+    getattr(_C(), "k_dft_acc_" + _sfx(u))(u.data_ptr(), [t.data_ptr() for t in re], [t.data_ptr() for t in im],
+                                         c_row.data_ptr(), s_row.data_ptr(), gv, bl, int(chunk), _stream())
 
 
 def inject(u, m, nodes, g, wrap=None) -> None:

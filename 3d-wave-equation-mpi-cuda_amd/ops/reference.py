@@ -1082,10 +1082,83 @@ class _Points:
         return torch.stack([u[nd] for nd in self.rec]) if self.rec else torch.zeros(0, dtype=u.dtype, device=u.device)
 
 
+# ---- on-the-fly discrete Fourier transform (csrc/hip_medium_dft.hip) -------------------------
+#
+# While a time loop runs, a few monochromatic components of a field are summed up level by level:
+# U_f = sum_p u^p exp(-i 2 pi f p tau) over the sampled indices p, as the two real sums
+#   re_f = re_f + u c[p, f],   im_f = im_f + u s[p, f],   c = cos(2 pi f p tau),  s = -sin(2 pi f p tau),
+# every product rounded before its add. The twiddle tables are formed in float64 and cast once.
+
+def check_frequencies(frequencies) -> torch.Tensor:
+    """The frequencies in Hz as a float64 tensor: a non-empty 1-D list of finite values >= 0."""
+    try:
+        f = torch.as_tensor(frequencies, dtype=torch.float64).cpu()
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"frequencies must be a 1-D list of numbers: {e}") from None
+    if f.dim() != 1 or f.numel() == 0:
+        raise ValueError(f"frequencies must be a non-empty 1-D list, not shape {tuple(f.shape)}")
+    bad = ~(torch.isfinite(f) & (f >= 0))
+    if bool(bad.any()):
+        raise ValueError(f"frequencies must be finite and >= 0, found {f[bad][0].item()}")
+    return f
+
+
+def check_dft_every(dft_every) -> int:
+    if isinstance(dft_every, bool) or not isinstance(dft_every, int) or dft_every < 1:
+        raise ValueError(f"dft_every must be an integer >= 1, not {dft_every!r}")
+    return dft_every
+
+
+def dft_tables(frequencies, indices, tau: float, dtype) -> tuple[torch.Tensor, torch.Tensor]:
+    """Twiddle tables ``(c, s)``, ``[len(indices), F]`` each: ``c[r, f] = cos(a)``, ``s[r, f] = -sin(a)`` with
+    ``a = ((2 pi f) p) tau`` for the integer sample index ``p = indices[r]``, evaluated in float64 and then
+    cast once to ``dtype``."""
+    f = check_frequencies(frequencies)
+    p = torch.as_tensor(list(indices), dtype=torch.int64)
+    if p.dim() != 1:
+        raise ValueError("indices must be a 1-D list of integers")
+    a = ((2 * math.pi * f)[None, :] * p.to(torch.float64)[:, None]) * float(tau)
+    return torch.cos(a).to(dtype), (-torch.sin(a)).to(dtype)
+
+
+def dft_accumulate(re, im, u: torch.Tensor, box, c_row, s_row) -> None:
+    """One accumulation, in place on the lists ``re`` / ``im`` of F tensors shaped like ``u``: at the
+    nodes of ``box`` = (i0, i1, j0, j1, k0, k1), for f ascending, ``re[f] = re[f] + u c_row[f]`` and
+    ``im[f] = im[f] + u s_row[f]``, the product rounded before the add. ``u`` is never written and the
+    nodes outside the box keep their values (``k_dft_acc``)."""
+    if len(re) != len(im) or len(re) == 0 or len(c_row) != len(re) or len(s_row) != len(re):
+        raise ValueError("re, im, c_row and s_row must have one entry per frequency, at least one")
+    i0, i1, j0, j1, k0, k1 = box
+    sl = (slice(i0, i1 + 1), slice(j0, j1 + 1), slice(k0, k1 + 1))
+    for f in range(len(re)):
+        if re[f].shape != u.shape or im[f].shape != u.shape or re[f].dtype != u.dtype or im[f].dtype != u.dtype:
+            raise ValueError("re and im levels must match u in shape and dtype")
+        re[f][sl] = re[f][sl] + u[sl] * torch.as_tensor(c_row[f]).to(u.dtype)
+        im[f][sl] = im[f][sl] + u[sl] * torch.as_tensor(s_row[f]).to(u.dtype)
+
+
+def finish_gradient_dft(Qre, Qim, Mre, Mim, weights, dtype) -> torch.Tensor:
+    """``acc = sum_f w_f (Qre_f Mre_f + Qim_f Mim_f)``, the correlation of the spectra of q and mu that
+    takes the place of ``sum_n mu^{n+1} q^n``: from ``acc = 0``, for f ascending ``t = Qre_f Mre_f``,
+    ``t = t + Qim_f Mim_f``, ``acc = acc + w_f t``, every operation rounded on its own in ``dtype``.
+    ``weights`` None: ones. The host-side step shared by both backends (CPU tensors)."""
+    F = len(Qre)
+    w = torch.ones(F, dtype=torch.float64) if weights is None else torch.as_tensor(weights, dtype=torch.float64)
+    if w.dim() != 1 or w.numel() != F or not bool(torch.isfinite(w).all()):
+        raise ValueError(f"weights must be {F} finite values, one per frequency")
+    w = w.to(dtype)
+    acc = torch.zeros_like(Qre[0], dtype=dtype)
+    for f in range(F):
+        t = Qre[f] * Mre[f]
+        t = t + Qim[f] * Mim[f]
+        acc = acc + w[f] * t
+    return acc
+
+
 def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, receivers=(),
                  L=("pi", "pi", "pi"), T: float = 1.0, pi: str = "ref", dtype=torch.float64, device="cpu",
                  taper=None, order: int = 2, density=None, source_positions=None, receiver_positions=None,
-                 interp: str = "sinc8"):
+                 interp: str = "sinc8", frequencies=None, dft_every: int = 1):
     """Whole single-domain solve of ``(1/c^2) u_tt = lap u + f`` from rest in PyTorch, in
     ``solve()``'s storage (x ghosts, local = global + 1).
 
@@ -1111,10 +1184,28 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
     ``sources`` / ``receivers`` (each side exclusive with its node list; CPU only), acting through the
     ``interp`` slots ("sinc8" or "linear"; ``interp_tables``): step n adds ``m[p] val_p(g[n-1])`` at every
     touched node p (``inject_rows``) and a trace is the weighted gather ``record_weighted``.
+
+    frequencies (Hz; a non-empty list of finite values >= 0) / dft_every = e >= 1: the on-the-fly Fourier
+    transform. For n = 0, e, 2e, ... <= K the level u^n, after its source term and the x wrap (n = 0: the
+    initial field), is accumulated with the twiddle row p = n (``dft_tables``, ``dft_accumulate``) on the
+    step box. The result then has a fourth entry, the spectra ``sum_n u^n exp(-i 2 pi f n tau)`` as a
+    complex ``[F, N+1, N+1, N+1]`` tensor (the Dirichlet faces 0); the first three do not change by a bit.
     """
     c = tables(N, K, L, T, pi)[4]
     M, box, mirror = _medium_layout(N, order)
     pts = _Points(N, M, dtype, sources, receivers, source_positions, receiver_positions, interp)
+    spec = None
+    if frequencies is not None:
+        e = check_dft_every(dft_every)
+        ctab, stab = dft_tables(frequencies, range(K + 1), c["tau"], dtype)
+        F = ctab.shape[1]
+        spec = tuple([torch.zeros(N + 1 + 2 * M, N + 1, N + 1, dtype=dtype, device=device) for _ in range(F)]
+                     for _ in range(2))
+
+    def transform(n, u):
+        if spec is not None and n % e == 0:
+            dft_accumulate(spec[0], spec[1], u, box, ctab[n], stab[n])
+
     if (pts.rows is not None or pts.rtab is not None) and torch.device(device).type != "cpu":
         raise ValueError("positions exist on the CPU oracle only")
     if taper is not None:
@@ -1141,6 +1232,7 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
         traces[n] = pts.sample(u)
 
     sample(0, lv[0])
+    transform(0, lv[0])
     mx = [max_abs_field(lv[0][M:N + 1 + M, 1:N, 1:N])]
     for n in range(1, K + 1):
         u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
@@ -1152,7 +1244,18 @@ def solve_medium(N: int, K: int, speed2, *, u0=None, sources=(), wavelet=None, r
         pts.inject(u, m, g[n - 1])
         wrap(u)
         sample(n, u)
-    return traces, lv[K % 3][M:N + 1 + M].clone(), mx
+        transform(n, u)
+    out = (traces, lv[K % 3][M:N + 1 + M].clone(), mx)
+    if spec is not None:
+        out += (spectra_tensor(spec[0], spec[1], N, M),)
+    return out
+
+
+def spectra_tensor(re, im, N: int, ghost: int = 1) -> torch.Tensor:
+    """The storage-shaped accumulators of ``dft_accumulate`` as one complex ``[F, N+1, N+1, N+1]`` tensor
+    on the CPU: the planes ``ghost .. N + ghost`` of every level."""
+    return torch.complex(torch.stack([t[ghost:N + 1 + ghost].cpu() for t in re]),
+                         torch.stack([t[ghost:N + 1 + ghost].cpu() for t in im]))
 
 
 # ---- misfit gradients of the medium solver (adjoint state) ---------------------------------
@@ -1380,7 +1483,7 @@ def finish_illumination(h, tt, N: int, tau: float, ghost: int = 1, density=None)
 
 def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, receivers, taper, L, T, pi, dtype,
                     order: int, density, wrt_density: bool, illumination: bool = False, source_positions=None,
-                    receiver_positions=None, interp: str = "sinc8"):
+                    receiver_positions=None, interp: str = "sinc8", dft=None):
     """The forward run and the adjoint loop shared by ``gradient_medium`` and
     ``gradient_medium_density``: everything their host-side ends need, as a dict. ``illumination``: also
     ``h = h + q^n q^n`` over the forward run's q^1 .. q^{K-1} in that order, the product rounded before
@@ -1389,7 +1492,13 @@ def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, recei
     Off-grid receivers: the residuals ``[K+1, R]`` are injected through ``point_rows(.., tt)``, whose
     weights carry G. Off-grid sources: ``a[n-1, s]`` is the weighted gather of mu^n with the
     ``receiver_tables(over_taper=tt)`` and ``sacc = sacc + mu^n[p] val_p(g[n-1])`` is accumulated per
-    unique source row in the loop's order, n = K .. 1 (``rows_dot``)."""
+    unique source row in the loop's order, n = K .. 1 (``rows_dot``).
+
+    ``dft = (frequencies, dft_every)`` (``gradient_medium_dft``): no ``acc``; the spectra of q and mu at the
+    indices p = e, 2e, ... <= K - 1 instead, as ``spectra = (Qre, Qim, Mre, Mim)``, lists of F levels in
+    storage. q^p goes into Q with the twiddle row p in ascending p, after the forward run; mu^{n+1},
+    injected and wrapped, goes into M with the row n before the step that produces mu^n, in the loop's
+    descending order (``dft_accumulate`` on the step box)."""
     M0 = _medium_layout(N, order)[0]
     pts = _Points(N, M0, dtype, sources, receivers, source_positions, receiver_positions, interp)
     fwd = forward_medium_autograd(N, K, speed2, wavelet=wavelet, taper=taper, L=L, T=T, pi=pi, dtype=dtype,
@@ -1435,22 +1544,35 @@ def _adjoint_medium(N: int, K: int, speed2, observed, *, sources, wavelet, recei
         for s, nd in enumerate(snodes):
             a[n - 1, s] = mu[nd]
 
+    spectra = None
+    if dft is not None:
+        every = check_dft_every(dft[1])
+        ctab, stab = dft_tables(dft[0], range(K), c["tau"], dtype)
+        spectra = tuple([torch.zeros(shape, dtype=dtype) for _ in range(ctab.shape[1])] for _ in range(4))
+        ql = torch.zeros(shape, dtype=dtype)
+        for p in range(every, K, every):  # q^p = laps[p - 1], what forward step p + 1 used
+            ql[own] = laps[p - 1]
+            dft_accumulate(spectra[0], spectra[1], ql, box, ctab[p], stab[p])
+
     mu2 = torch.zeros(shape, dtype=dtype)
     mu1 = torch.zeros(shape, dtype=dtype)
     finish_level(mu1, K)
-    acc = torch.zeros(shape, dtype=dtype)
+    acc = torch.zeros(shape, dtype=dtype) if dft is None else None
     accb = torch.zeros(shape, dtype=dtype) if wrt_density else None
     for n in range(K - 1, 0, -1):
         vals = step_medium(mu1, mu2, m, box, first=False, hx2=c["hx2"], hy2=c["hy2"], hz2=c["hz2"], taper=tt,
                            order=order, mirror=mirror, buoyancy=bu)
-        acc[own] = acc[own] + mu1[own] * laps[n - 1]
+        if dft is None:
+            acc[own] = acc[own] + mu1[own] * laps[n - 1]
+        elif n % every == 0:
+            dft_accumulate(spectra[2], spectra[3], mu1, box, ctab[n], stab[n])
         if wrt_density:  # mu1 = mu^{n+1}, injected and wrapped; fwd[2][n - 1] = u^n
             accb[own] = accb[own] + face_correlation(mu1, fwd[2][n - 1], box, c["hx2"], c["hy2"], c["hz2"])
         mu = torch.zeros(shape, dtype=dtype)
         mu[own] = vals
         finish_level(mu, n)
         mu2, mu1 = mu1, mu
-    return dict(J=J, traces=traces, acc=acc, accb=accb, a=a, g=g, m=m, tt=tt, c=c, M=M, h=h,
+    return dict(J=J, traces=traces, acc=acc, accb=accb, a=a, g=g, m=m, tt=tt, c=c, M=M, h=h, spectra=spectra,
                 source_rows=None if gtab is None else (pts.rows, sacc))
 
 
@@ -1494,6 +1616,39 @@ def gradient_medium(N: int, K: int, speed2, observed, *, sources=(), wavelet=Non
         if illumination:
             out += finish_illumination(r["h"], r["tt"], N, c["tau"], r["M"], density)
         return out
+
+
+def gradient_medium_dft(N: int, K: int, speed2, observed, frequencies, *, weights=None, dft_every: int = 1,
+                        sources=(), wavelet=None, receivers=(), taper=None, L=("pi", "pi", "pi"), T: float = 1.0,
+                        pi: str = "ref", dtype=torch.float64, order: int = 2, density=None, source_positions=None,
+                        receiver_positions=None, interp: str = "sinc8"):
+    """``gradient_medium`` with the time sum ``sum_n mu^{n+1} q^n`` replaced by a sum over frequencies of the
+    on-the-fly spectra of q and mu: (J, dJ/dspeed2, dJ/dwavelet, traces), J, dJ/dwavelet and the traces
+    those of ``gradient_medium`` bit for bit.
+
+    With e = ``dft_every`` the pairs p = e, 2e, ... <= K - 1 are transformed: Q_f = sum_p q^p w_p and
+    M_f = sum_p mu^{p+1} w_p with w_p = exp(-i 2 pi f p tau) (``_adjoint_medium``'s ``dft``), and
+    ``acc = sum_f weights_f (Re Q_f Re M_f + Im Q_f Im M_f)`` (``finish_gradient_dft``) goes through
+    ``finish_gradient_medium`` unchanged. With every bin of the half spectrum of the P = (K - 1) // e pairs,
+    f_k = k / (P e tau) for k = 0 .. P // 2 and the weights 2 / P (1 / P for k = 0 and, P even, k = P / 2),
+    Parseval's identity makes ``acc`` the time sum over those pairs up to rounding: ``gradient_medium``'s
+    for e = 1. Fewer bins give the band-limited gradient. Neither pass keeps a level of the other: the
+    memory is that of 4 F levels whatever K is."""
+    f = check_frequencies(frequencies)
+    every = check_dft_every(dft_every)
+    if every > K - 1:
+        raise ValueError(f"dft_every = {every} leaves no pair to correlate: the pairs are p = e, 2e, ... <= K - 1 = "
+                         f"{K - 1}")
+    with torch.no_grad():
+        r = _adjoint_medium(N, K, speed2, observed, sources=sources, wavelet=wavelet, receivers=receivers,
+                            taper=taper, L=L, T=T, pi=pi, dtype=dtype, order=order, density=density,
+                            wrt_density=False, source_positions=source_positions,
+                            receiver_positions=receiver_positions, interp=interp, dft=(f, every))
+        c = r["c"]
+        acc = finish_gradient_dft(*r["spectra"], weights, dtype)
+        grad, gw = finish_gradient_medium(acc, r["a"], r["g"], r["m"], r["tt"], sources, N, c["tau"], c["hx"],
+                                          c["hy"], c["hz"], r["M"], density, r["source_rows"])
+        return r["J"], grad, gw, r["traces"]
 
 
 def gradient_medium_density(N: int, K: int, speed2, observed, *, sources=(), wavelet=None, receivers=(), taper=None,

@@ -11,6 +11,8 @@
                                  [--kernels-only] [--density]
     python tools/bench_medium.py --born --density --ddensity [--N 512] [--steps 100] [--kernels-only]
     python tools/bench_medium.py --positions R [--N 256] [--steps 100] [--dtypes fp64,fp32] [--repeat 3]
+    python tools/bench_medium.py --dft F[,F...] [--N 512] [--steps 100] [--dtypes fp64,fp32] [--segment 10]
+                                 [--kernels-only]
 
 For each dtype: a random smooth speed2, one source, one receiver; per variant one warm-up run()
 and `--repeat` timed ones (device events around the time loop: step + inject + record per layer),
@@ -80,6 +82,15 @@ gradient() (every q stored, so the reverse pass recomputes nothing) of the two a
 ms per step of run()'s time loop (step + inject + record) and of gradient()'s reverse pass (image step
 + the injection of R residuals + the record at the source, with positions also the row dot), the
 difference positions - nodes, and that difference over the node-list step.
+
+`--dft F[,F...]` (frequencies in Hz) measures the on-the-fly Fourier transform, per dtype in one process:
+ms per call of k_dft_acc with one frequency (u read, re and im read and written: 40 B per node in fp64)
+and with a full launch of NF (8 + 32 NF B), beside the plain step k_march_m and k_face_corr (32 B each),
+`--repeat` rounds of 20 launches each, the four alternating inside each round. Then run() without
+frequencies, with them, and with them at dft_every = 4, alternating inside each repeat: the device time of
+the time loop. Then gradient_dft() with the frequencies beside gradient(segment=`--segment`) and gradient()
+with every q stored, alternating as well: the levels held, their size, and the device time of the two
+passes. `--kernels-only` skips the runs.
 """
 import argparse
 import json
@@ -168,6 +179,134 @@ def positions_bench(a) -> int:
         row.update({k: extra["positions"][k] for k in ("interp", "source_rows", "source_entries", "receiver_rows",
                                                       "receiver_entries")})
         out["runs"].append(row)
+    print(json.dumps(out))
+    return 0
+
+
+def dft_bench(a) -> int:
+    import math
+
+    import torch
+
+    import wave3d
+    from wave3d.ops import kernels, reference
+
+    N, K = a.N, a.steps
+    freqs = [float(v) for v in a.dft.split(",")]
+    F = len(freqs)
+    h = 3.1415926535 / N
+    hi = (0.9 * wave3d.cfl_limit(2) * h * K) ** 2
+    speed2 = smooth_speed2(N, 0.5 * hi, hi)
+    nodes = float(N + 1) ** 3
+    NF = kernels.dft_frequencies_per_launch()
+    out = {"N": N, "steps": K, "device": torch.cuda.get_device_name(0), "frequencies": freqs,
+           "frequencies_per_launch": NF, "kernels": [], "run": [], "gradient": []}
+    dev = torch.device("cuda", 0)
+    for dtype in a.dtypes.split(","):
+        es = 8 if dtype == "fp64" else 4
+        prob = wave3d.MediumProblem(N, speed2, timesteps=K, dtype=dtype)
+        dt = prob.torch_dtype
+        c = reference.tables(N, K)[4]
+        h2 = (c["hx2"], c["hy2"], c["hz2"])
+        box, wrap = (1, N + 1, 1, N - 1, 1, N - 1), [N, 0, 2, N + 2]
+
+        # the kernels on one set of levels (smooth values, nothing denormal)
+        g = torch.Generator().manual_seed(1)
+        seed = torch.rand(N + 1, N + 1, generator=g, dtype=torch.float64).to(dt).to(dev)
+        u1, u2, m, u, acc = (kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(5))
+        re = [kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(NF)]
+        im = [kernels.alloc_level(N + 3, N + 1, N + 1, dt, dev) for _ in range(NF)]
+        m.copy_(reference.medium_coefficient(speed2, c["tau"], N, dt))
+        for t in (u1, u2):
+            t[:, 1:N, 1:N] = seed[1:N, 1:N]
+        ctab, stab = (t.contiguous().to(dev) for t in reference.dft_tables([1.0 + f for f in range(NF)], range(K), c["tau"], dt))
+        stat = kernels.new_err(1, device=dev)
+        step = dict(first=False, h2=h2, stat=stat, stat_i=(1, N + 1), wrap=wrap)
+        # (bytes per node / element size, call); k_dft_acc with 1 and with NF frequencies per launch
+        arms = {"k_march_m": (4, lambda: kernels.step_medium(u1, u2, m, u, box, **step)),
+                "k_face_corr": (4, lambda: kernels.face_correlation(u1, u2, acc, box, h2=h2)),
+                "k_dft_acc_1": (5, lambda: kernels.dft_accumulate(u1, re[:1], im[:1], box, ctab[7, :1], stab[7, :1])),
+                f"k_dft_acc_{NF}": (1 + 4 * NF, lambda: kernels.dft_accumulate(u1, re, im, box, ctab[7], stab[7]))}
+        reps = 20
+        ms = {k: [] for k in arms}
+        for rnd in range(a.repeat + 1):  # round 0 warms up
+            for name, (_, fn) in arms.items():  # the arms alternate inside each round
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                acc.zero_()
+                for t in re + im:
+                    t.zero_()
+                e0.record()
+                for _ in range(reps):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                if rnd:
+                    ms[name].append(e0.elapsed_time(e1) / reps)
+        for name, (bpn, _) in arms.items():
+            best = min(ms[name])
+            out["kernels"].append({"dtype": dtype, "kernel": name, "ms_per_call": round(best, 4),
+                                   "all_ms": [round(v, 4) for v in ms[name]], "bytes_per_node": bpn * es,
+                                   "eff_tb_per_s": round(bpn * es * nodes / (best * 1e-3) / 1e12, 3),
+                                   "vs_k_march_m": round(best / min(ms["k_march_m"]), 4),
+                                   "expected_vs_k_march_m": bpn / 4})
+            print(f"bench_medium: {dtype} {name}: {best:.4f} ms/call", file=sys.stderr, flush=True)
+        del u1, u2, m, u, acc, re, im, arms, step
+        torch.cuda.empty_cache()
+        if a.kernels_only:
+            continue
+
+        w = wave3d.ricker(4.0, 0.25, K, prob.tau).reshape(K, 1)
+        mid = N // 2
+        sol = wave3d.MediumSolver(prob, "hip", sources=[(mid, mid, mid)], wavelet=w,
+                                  receivers=[(mid - K // 5, mid, mid), (mid, mid - K // 4, mid + 3)],
+                                  taper=wave3d.sponge_taper(prob, 16))
+        obs = 0.9 * sol.run().traces  # warm-up
+        lb = kernels.level_bytes(N + 3, N + 1, N + 1, dt)
+
+        # run() with and without the frequencies, at dft_every 1 and 4, alternating inside each repeat
+        runs = {"plain": {}, "dft_every_1": dict(frequencies=freqs), "dft_every_4": dict(frequencies=freqs, dft_every=4)}
+        loop = {k: [] for k in runs}
+        for rnd in range(a.repeat + 1):  # round 0 warms up
+            for name, kw in runs.items():
+                r = sol.run(**kw)
+                assert not r.aborted and math.isfinite(max(r.max_abs_u)), "the benchmark run diverged"
+                assert (r.spectra is not None) == bool(kw)
+                if rnd:
+                    loop[name].append(round(r.total_ms, 2))
+                print(f"bench_medium: {dtype} run {name}: {r.total_ms:.2f} ms", file=sys.stderr, flush=True)
+                del r
+                torch.cuda.empty_cache()
+        for name in runs:
+            best = min(loop[name])
+            out["run"].append({"dtype": dtype, "run": name, "loop_ms": best, "ms_per_step": round(best / K, 4),
+                               "vs_plain": round(best / min(loop["plain"]), 3), "loop_ms_all": loop[name],
+                               "levels": 4 + (2 * F if name != "plain" else 0)})
+
+        # gradient_dft beside gradient(segment) and gradient() with every q stored
+        cfgs = {"gradient_dft": lambda: sol.gradient_dft(obs, freqs),
+                f"segment_{a.segment}": lambda: sol.gradient(obs, segment=a.segment),
+                "all_q": lambda: sol.gradient(obs, segment=K)}
+        rows = {n: [] for n in cfgs}
+        for _ in range(a.repeat):
+            for name, fn in cfgs.items():
+                r = fn()
+                assert math.isfinite(r.misfit) and r.misfit > 0 and float(r.grad_speed2.abs().max()) > 0
+                rows[name].append({"wall_ms": round(r.total_ms, 1), "forward_ms": round(r.extra["forward_ms"], 2),
+                                   "reverse_ms": round(r.extra["reverse_ms"], 2), "levels": r.extra["levels"],
+                                   "gb": round(r.extra["levels"] * lb / 1e9, 1),
+                                   "recomputed_steps": r.extra["recomputed_steps"]})
+                print(f"bench_medium: {dtype} {name}: {rows[name][-1]}", file=sys.stderr, flush=True)
+                del r
+                torch.cuda.empty_cache()
+        run_ms = min(loop["plain"])
+        for name in cfgs:
+            best = min(rows[name], key=lambda v: v["forward_ms"] + v["reverse_ms"])
+            passes = best["forward_ms"] + best["reverse_ms"]
+            out["gradient"].append({"dtype": dtype, "schedule": name, **best, "passes_ms": round(passes, 2),
+                                    "run_loop_ms": run_ms, "passes_vs_run": round(passes / run_ms, 3),
+                                    "wall_ms_all": [v["wall_ms"] for v in rows[name]]})
+        del sol
+        torch.cuda.empty_cache()
     print(json.dumps(out))
     return 0
 
@@ -599,6 +738,8 @@ def main(argv=None) -> int:
                     help="--born --density: time the scatter and Born-add steps and born(ddensity=...) instead")
     ap.add_argument("--positions", type=int, default=0, metavar="R",
                     help="time off-grid sources and receivers instead: R receivers and one source, run() and gradient()")
+    ap.add_argument("--dft", default="", metavar="F[,F...]",
+                    help="time k_dft_acc, run(frequencies=...) and gradient_dft() with these frequencies (Hz) instead")
     a = ap.parse_args(argv)
     if a.N is None:
         a.N = 256 if a.positions else 512
@@ -620,6 +761,10 @@ def main(argv=None) -> int:
         ap.error("--density: order 2 must be among the orders")
     if a.illum and (not a.gradient or a.wrt_density):
         ap.error("--illum goes with --gradient (without --wrt-density)")
+    if a.dft:
+        if a.gradient or a.born or a.density or a.positions or orders != [2]:
+            ap.error("--dft is a measurement of its own (order 2, no other mode)")
+        return dft_bench(a)
     if a.positions:
         if a.positions < 1 or a.gradient or a.born or a.density or orders != [2]:
             ap.error("--positions R >= 1 is a measurement of its own (order 2, no other mode)")
