@@ -326,32 +326,30 @@ void k_zero_faces(uintptr_t u, const std::vector<i64>& g, int mask, uintptr_t st
     launch_zero_faces<T>(P<T>(u), gview(g), mask, (hipStream_t)stream);
 }
 
-// Heterogeneous-medium step (k_march_m): m = c^2 tau^2 per node, h2 = (hx2, hy2, hz2); the grid
-// view carries explicit strides (dense tensors or the padded views of ops.kernels.alloc_level).
-// gx, gy, gz: the sponge tables (nx, ny, nz device values), all 0 for the undamped step.
-// lap_out / (q, acc): the grids of the save / image modes, all 0 for the plain step.
-// b: the buoyancy grid 1 / rho of the variable-density step (k_march_mb), 0 for constant density.
-// dm: the coefficient perturbation of the Born step (with q; lap_out and acc 0), 0 otherwise.
-// db: the buoyancy perturbation of the scatter step (with lap_out = s_out, dm and b); sadd: the
-// scattering term of the Born-add step (with b alone); 0 otherwise.
-// illum: the illumination grid of the illum / save+illum steps (alone or with lap_out), 0 otherwise.
+// Heterogeneous-medium step: fills a MediumStep (hip_medium.hpp describes it and the modes). mode: a value of
+// medium_modes; a pointer is 0 where the step has no such grid; mirror: empty, or four entries (no_mirror: no face).
 template <class T>
 void k_step_medium(bool first, uintptr_t u1, uintptr_t u2, uintptr_t m, uintptr_t u, const std::vector<i64>& g,
                    const std::vector<std::vector<int>>& boxes, int ei0, int ei1, const std::vector<int>& wrap,
-                   const std::vector<double>& h2, uintptr_t err, int chunk, uintptr_t stream, int variant,
-                   uintptr_t gx, uintptr_t gy, uintptr_t gz, uintptr_t lap_out, uintptr_t q, uintptr_t acc, int order,
-                   const std::vector<int>& mirror, uintptr_t b, uintptr_t dm, uintptr_t db, uintptr_t sadd,
-                   uintptr_t illum) {
+                   const std::vector<double>& h2, uintptr_t err, int chunk, uintptr_t stream, int mode, int variant,
+                   int order, const std::vector<int>& mirror, uintptr_t gx, uintptr_t gy, uintptr_t gz, uintptr_t b,
+                   uintptr_t lap_out, uintptr_t q, uintptr_t acc, uintptr_t dm, uintptr_t db, uintptr_t s_out,
+                   uintptr_t sadd, uintptr_t illum) {
     std::vector<Box> bx;
     for (auto& e : boxes) bx.push_back(tobox(e));
     W3D_REQUIRE(h2.size() == 3, "h2 = (hx2, hy2, hz2)");
-    const double h[3] = {h2[0], h2[1], h2[2]};
-    // mirror: empty = none, or (j_lo, j_hi, k_lo, k_hi) with no_mirror for a side without a face
     W3D_REQUIRE(mirror.empty() || mirror.size() == 4, "mirror = (j_lo, j_hi, k_lo, k_hi)");
-    launch_step_medium<T>(first, P<T>(u1), P<T>(u2), P<T>(m), P<T>(u), gview(g), bx.data(), int(bx.size()), ei0,
-                          ei1, towrap(wrap), h, P<u64>(err), chunk, (hipStream_t)stream, variant, P<T>(gx), P<T>(gy),
-                          P<T>(gz), P<T>(lap_out), P<T>(q), P<T>(acc), order, mirror.empty() ? nullptr : mirror.data(),
-                          P<T>(b), P<T>(dm), P<T>(db), P<T>(sadd), P<T>(illum));
+    MediumStep<T> st;
+    st.first = first, st.u1 = P<T>(u1), st.u2 = P<T>(u2), st.m = P<T>(m), st.u = P<T>(u), st.gv = gview(g);
+    st.boxes = bx.data(), st.nbox = int(bx.size()), st.ei0 = ei0, st.ei1 = ei1, st.wrap = towrap(wrap);
+    std::copy(h2.begin(), h2.end(), st.h2);
+    st.err = P<u64>(err), st.chunk = chunk, st.variant = variant, st.order = order;
+    st.mirror = mirror.empty() ? nullptr : mirror.data();
+    st.gx = P<T>(gx), st.gy = P<T>(gy), st.gz = P<T>(gz), st.b = P<T>(b);
+    st.mode = static_cast<MarchMode>(mode);  // the launcher rejects a value that names no mode
+    st.lap_out = P<T>(lap_out), st.q = P<T>(q), st.acc = P<T>(acc), st.dm = P<T>(dm), st.db = P<T>(db);
+    st.s_out = P<T>(s_out), st.sadd = P<T>(sadd), st.illum = P<T>(illum);
+    launch_step_medium<T>(st, (hipStream_t)stream);
 }
 
 // Face correlation (k_face_corr): acc = acc + C(a, v) at the box nodes; grid view as above
@@ -678,16 +676,20 @@ PYBIND11_MODULE(_wave3d_C, m) {
     m.def("tb_supported", [](int depth, int rows, int waves, bool fm) {
         return depth == 3 && tb3_supported(rows, waves, fm);
     }, py::arg("depth"), py::arg("rows"), py::arg("waves"), py::arg("fm") = false);
-    // order and mirror are optional (order 2, no faces): every earlier positional call still binds
+    // the grids of the step's mode go by keyword alone
 #define W3D_STEP_MEDIUM_ARGS                                                                                      \
     py::arg("first"), py::arg("u1"), py::arg("u2"), py::arg("m"), py::arg("u"), py::arg("grid"), py::arg("boxes"), \
         py::arg("ei0"), py::arg("ei1"), py::arg("wrap"), py::arg("h2"), py::arg("err"), py::arg("chunk"),          \
-        py::arg("stream"), py::arg("variant"), py::arg("gx"), py::arg("gy"), py::arg("gz"), py::arg("lap_out"),    \
-        py::arg("q"), py::arg("acc"), py::arg("order") = 2, py::arg("mirror") = std::vector<int>{},         \
-        py::arg("b") = 0, py::arg("dm") = 0, py::arg("db") = 0, py::arg("sadd") = 0, py::arg("illum") = 0
+        py::arg("stream"), py::arg("mode"), py::arg("variant") = -1, py::arg("order") = 2,                         \
+        py::arg("mirror") = std::vector<int>{}, py::arg("gx") = 0, py::arg("gy") = 0, py::arg("gz") = 0,           \
+        py::arg("b") = 0, py::kw_only(), py::arg("lap_out") = 0, py::arg("q") = 0, py::arg("acc") = 0,             \
+        py::arg("dm") = 0, py::arg("db") = 0, py::arg("s_out") = 0, py::arg("sadd") = 0, py::arg("illum") = 0
     m.def("k_step_medium_f64", &k_step_medium<double>, W3D_STEP_MEDIUM_ARGS);
     m.def("k_step_medium_f32", &k_step_medium<float>, W3D_STEP_MEDIUM_ARGS);
 #undef W3D_STEP_MEDIUM_ARGS
+    py::dict medium_modes;  // name -> MarchMode value
+    for (int q = 0; q < kMarchModes; ++q) medium_modes[march_mode_name(q)] = q;
+    m.attr("medium_modes") = medium_modes;
     m.def("k_face_corr_f64", &k_face_corr<double>);
     m.def("k_face_corr_f32", &k_face_corr<float>);
     m.def("k_dft_acc_f64", &k_dft_acc<double>);

@@ -19,9 +19,9 @@
 //    the kernel). It alone has the scatter and Born-add modes of Born modelling with a density
 //    perturbation.
 //  * all three march kernels have the save, image and Born modes of the adjoint-state gradient and
-//    of Born modelling and the two illumination modes (MarchMode below; hip_medium.hpp has the
-//    contract), and are built from the
-//    tile skeleton of march_tile.hpp and the per-mode pieces below, each written once.
+//    of Born modelling and the two illumination modes (MarchMode; hip_medium.hpp describes them), and
+//    are built from the tile skeleton of march_tile.hpp and the per-mode pieces below, each written once.
+//    The launcher checks a step against one table of per-mode rules (kMediumModes).
 //  * k_inject / k_record: one thread per source entry / receiver.
 //
 // FP contraction is off (-ffp-contract=off + the pragmas in stencil_math.hpp and in every helper
@@ -61,32 +61,13 @@ struct MediumParams : TileParams<T> {
     T* illum;               // kIllum, kSaveIllum: h = h + lap * lap at the box nodes (strides of u)
 };
 
-// Modes of the march kernels: the plain step; kSave also stores the Laplacian that entered the
-// update; kImage also accumulates acc = acc + u1 * q (the imaging condition of the adjoint-state
-// gradient); kBorn adds the scattering term dm * q to the update itself (Born / linearised
-// modelling, image mode's transpose): u = G (((2 u1 - G u2) + m lap) + dm q).
-// A MODE other than kPlain (FIRST = false only) adds, behind `if constexpr`, one write-once stream
-// (kSave: lap_out), or a read-once stream (q) and a read-modify-write one (kImage: acc), or two
-// read-once streams (kBorn: q and dm, no store beside u's); all at the lane's own nodes, masked
-// like the stores of u and without the periodic wrap.
-// Born modelling with a density perturbation (k_march_mb only) splits Born mode's work differently:
-// kScatter is the background step that also stores the whole scattering term s = dm lap + m r,
-// r = D_db u1 with the buoyancy perturbation db in b's place (a read-once stream dm, a write-once
-// stream lap_out = s, and db handled like b: described at the kernel); kBornAdd is the step of the
-// perturbation field that adds it, u = G (((2 u1 - G u2) + m lap) + s) (one read-once stream, q = s).
-// Source illumination (the diagonal of the pseudo-Hessian): kIllum is the plain step, kSaveIllum the
-// save step, that also does h = h + lap * lap at the lane's own nodes, the product rounded before the
-// add: one more read-modify-write stream (h), like image mode's acc without its q.
-enum MarchMode {
-    kPlain = 0,
-    kSave = 1,
-    kImage = 2,
-    kBorn = 3,
-    kScatter = 4,
-    kBornAdd = 5,
-    kIllum = 6,
-    kSaveIllum = 7
-};
+// The streams of a MODE (MarchMode; hip_medium.hpp describes the modes) other than kPlain (FIRST = false
+// only), each behind `if constexpr`, at the lane's own nodes, masked like the stores of u and without the
+// periodic wrap: one write-once stream (kSave: lap_out); a read-once stream (q) and a read-modify-write one
+// (kImage: acc); two read-once streams (kBorn: q and dm, no store beside u's); a read-once stream dm, a
+// write-once stream lap_out = s_out, and db handled like b, described at the kernel (kScatter); one
+// read-once stream, q = s (kBornAdd); one more read-modify-write stream, like image mode's acc without its
+// q (kIllum, kSaveIllum: illum).
 constexpr bool saves_lap(int mode) { return mode == kSave || mode == kSaveIllum; }
 constexpr bool illuminates(int mode) { return mode == kIllum || mode == kSaveIllum; }
 
@@ -825,7 +806,7 @@ void (*march_m_kernel(bool first, bool taper, int mode, int variant))(const Medi
         constexpr bool FIRST = decltype(fi)::value, TAPER = decltype(ta)::value;
         constexpr int MODE = decltype(mo)::value;
         constexpr int RD = 4;  // march_rows_per_thread()
-        if constexpr (MODE == kScatter || MODE == kBornAdd) return nullptr;  // k_march_mb only (the launcher checks)
+        if constexpr (MODE == kScatter || MODE == kBornAdd) return nullptr;  // k_march_mb only (kMediumModes rejects the call)
         else if constexpr (MODE != kPlain) return k_march_m<T, FIRST, RD, true, TAPER, MODE>;
         else switch (variant & 3) {
                 case 1: return k_march_m<T, FIRST, RD, true, TAPER>;
@@ -840,7 +821,7 @@ template <class T, int M>
 void (*march_mh_kernel(bool first, bool taper, int mode))(const MediumParamsH<T>) {
     return select_march(first, taper, mode, [](auto fi, auto ta, auto mo) -> void (*)(const MediumParamsH<T>) {
         constexpr int MODE = decltype(mo)::value;
-        if constexpr (MODE == kScatter || MODE == kBornAdd) return nullptr;  // k_march_mb only (the launcher checks)
+        if constexpr (MODE == kScatter || MODE == kBornAdd) return nullptr;  // k_march_mb only (kMediumModes rejects the call)
         else return k_march_mh<T, M, decltype(fi)::value, 4, decltype(ta)::value, MODE>;
     });
 }
@@ -874,72 +855,97 @@ double medium_weight(int order, int d) {
     return star_weight(order / 2, d);
 }
 
+namespace {
+
+// The rules of the modes, one row each, in MarchMode's order: all that launch_step_medium checks of a
+// step's mode. The grids of a step, as bits: the levels a mode grid may have to stay clear of, then the
+// mode grids in MediumStep's order.
+enum : unsigned {
+    gU = 1u << 0, gU1 = 1u << 1, gU2 = 1u << 2, gM = 1u << 3, gB = 1u << 4,
+    gLapOut = 1u << 5, gQ = 1u << 6, gAcc = 1u << 7, gDm = 1u << 8, gDb = 1u << 9, gSOut = 1u << 10,
+    gSAdd = 1u << 11, gIllum = 1u << 12
+};
+constexpr int kFirstModeGrid = 5, kStepGrids = 13;
+constexpr const char* kGridNames[kStepGrids] = {"u", "u1", "u2", "m", "b", "lap_out", "q", "acc", "dm", "db",
+                                                "s_out", "sadd", "illum"};
+enum : unsigned { kFamM = 1, kFamMH = 2, kFamMB = 4, kFamAll = 7 };  // k_march_m, k_march_mh, k_march_mb
+struct ModeRule {
+    const char* name;
+    unsigned grids;        // the mode grids it takes: each of them non-null, every other mode grid null
+    bool on_first;         // runs on the Taylor start
+    unsigned families;     // the kernel families that have it
+    bool default_variant;  // at order 2: instantiated for variant 1 alone (nt, 4 rows per lane)
+    // a grid (one bit) that the step writes, and the grids read or written beside it (its own plane and, for u,
+    // the wrap planes) that it must not share memory with; a null one does not count. 0: no such rule
+    unsigned apart, from;
+};
+constexpr unsigned kLevels = gU | gU1 | gU2 | gM | gB;
+constexpr ModeRule kMediumModes[kMarchModes] = {
+    {"plain", 0, true, kFamAll, false, 0, 0},
+    {"save", gLapOut, false, kFamAll, true, 0, 0},
+    {"image", gQ | gAcc, false, kFamAll, true, 0, 0},
+    {"born", gQ | gDm, false, kFamAll, true, gU, gQ | gDm},
+    {"scatter", gSOut | gDm | gDb, false, kFamMB, true, gSOut, kLevels | gDm | gDb},
+    {"born_add", gSAdd, false, kFamMB, true, gU, gSAdd},
+    {"illum", gIllum, false, kFamAll, true, gIllum, kLevels},
+    {"save_illum", gLapOut | gIllum, false, kFamAll, true, gIllum, kLevels | gLapOut},
+};
+
+// The mode checks of a step that runs in kernel family `family` with the (resolved) variant; span: the
+// elements a grid covers.
 template <class T>
-void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
-                        const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
-                        const double h2[3], u64* err, int chunk, hipStream_t s, int variant, const T* gx,
-                        const T* gy, const T* gz, T* lap_out, const T* q, T* acc, int order, const int* mirror,
-                        const T* b, const T* dm, const T* db, const T* sadd, T* illum) {
+void check_mode(const MediumStep<T>& st, unsigned family, int variant, i64 span) {
+    W3D_REQUIRE(st.mode >= kPlain && st.mode < kMarchModes, "no such mode: " + std::to_string(int(st.mode)));
+    const ModeRule& r = kMediumModes[st.mode];
+    const std::string mode = std::string(r.name) + " mode";
+    const T* grid[kStepGrids] = {st.u,  st.u1, st.u2, st.m,     st.b,    st.lap_out, st.q,
+                                 st.acc, st.dm, st.db, st.s_out, st.sadd, st.illum};
+    for (int g = kFirstModeGrid; g < kStepGrids; ++g) {
+        const bool takes = r.grids >> g & 1;
+        W3D_REQUIRE(takes == (grid[g] != nullptr),
+                    mode + (takes ? " needs " : " cannot be combined with ") + kGridNames[g]);
+    }
+    W3D_REQUIRE(r.on_first || !st.first, mode + ": not on the Taylor start (first)");
+    W3D_REQUIRE(r.families & family, mode + (family == kFamMH ? " exists for space order 2 only"
+                                                              : " needs the buoyancy b (variable density)"));
+    W3D_REQUIRE(!r.default_variant || variant == 1 || st.order != 2,
+                mode + " is instantiated for the default variant only (nt, 4 rows per lane)");
+    const int g = r.apart ? __builtin_ctz(r.apart) : 0;
+    for (int o = 0; o < kStepGrids; ++o)
+        W3D_REQUIRE(!(r.from >> o & 1) || !grid[o] || !overlaps<T>(grid[g], grid[o], span),
+                    mode + ": " + kGridNames[g] + " shares memory with " + kGridNames[o]);
+}
+
+}  // namespace
+
+const char* march_mode_name(int mode) {
+    W3D_REQUIRE(mode >= kPlain && mode < kMarchModes, "no such mode: " + std::to_string(mode));
+    return kMediumModes[mode].name;
+}
+
+template <class T>
+void launch_step_medium(const MediumStep<T>& st, hipStream_t s) {
+    const bool first = st.first;
+    const GridView& gv = st.gv;
+    const Box* boxes = st.boxes;
+    const int nbox = st.nbox, order = st.order;
+    const int* mirror = st.mirror;
+    const T* b = st.b;
     W3D_REQUIRE(order == 2 || order == 4 || order == 8, "space order must be 2, 4 or 8, not " + std::to_string(order));
     W3D_REQUIRE(!b || order == 2, "variable density (b) exists for space order 2 only");
     const int M = order / 2;
-    const bool taper = gx || gy || gz;
-    W3D_REQUIRE(!taper || (gx && gy && gz), "the sponge needs all three tables");
+    const bool taper = st.gx || st.gy || st.gz;
+    W3D_REQUIRE(!taper || (st.gx && st.gy && st.gz), "the sponge needs all three tables");
     W3D_REQUIRE(!taper || gv.G == 1, "sponge tables: one ghost layer");
     W3D_REQUIRE(nbox >= 1 && nbox <= kMaxBoxes, "bad box count");
     W3D_REQUIRE(march_rows_per_thread() == 4, "k_march_m is instantiated for 4 rows per lane");
     W3D_REQUIRE(gv.si > 0 && gv.si * i64(sizeof(T)) < (1ll << 31), "plane larger than a buffer descriptor's range");
     W3D_REQUIRE(gv.sj >= gv.Z + 2 * gv.G && gv.si >= i64(gv.Y + 2 * gv.G) * gv.sj, "strides smaller than the grid");
-    if (variant < 0) variant = medium_variant();
+    const int variant = st.variant < 0 ? medium_variant() : st.variant;
     W3D_REQUIRE(!b || variant == 1, "variable density (b) is instantiated for the default variant only (nt, 4 rows per lane)");
-    // Scatter mode (db, with lap_out = s_out and dm) and Born-add mode (sadd = s): k_march_mb only
-    const bool scatter = db != nullptr, born_add = sadd != nullptr;
     const i64 span = i64(gv.X + 2 * gv.G - 1) * gv.si + i64(gv.Y + 2 * gv.G - 1) * gv.sj + gv.Z + 2 * gv.G;
-    if (scatter || born_add) {
-        W3D_REQUIRE(!(scatter && born_add), "scatter mode (db) and Born-add mode (s) cannot be combined");
-        W3D_REQUIRE(b, "scatter / Born-add modes need the buoyancy b (variable density, order 2, default variant)");
-        W3D_REQUIRE(!first, "scatter / Born-add modes: not on the Taylor start (first)");
-        W3D_REQUIRE(!q && !acc, "scatter / Born-add modes cannot be combined with image or Born mode");
-        if (scatter) {
-            W3D_REQUIRE(lap_out && dm, "scatter mode needs s_out (lap_out) and dm beside db");
-            for (const T* o : {(const T*)u, u1, u2, m, b, dm, db})
-                W3D_REQUIRE(!overlaps<T>(lap_out, o, span), "scatter mode: s_out shares memory with another grid");
-        } else {
-            W3D_REQUIRE(!lap_out && !dm, "Born-add mode cannot be combined with save or Born mode");
-            W3D_REQUIRE(!overlaps<T>(u, sadd, span), "Born-add mode: s shares memory with u");
-        }
-    }
-    // Born mode: q and dm without acc; q with neither acc nor dm stays an incomplete image mode
-    const bool born = dm != nullptr && !scatter;
-    W3D_REQUIRE(!born || q, "Born mode needs q beside dm");
-    W3D_REQUIRE(!born || (!lap_out && !acc), "Born mode (q, dm) cannot be combined with save or image mode");
-    const bool save = lap_out != nullptr && !scatter, image = !born && (q || acc);
-    W3D_REQUIRE(!image || (q && acc), "image mode needs both q and acc");
-    W3D_REQUIRE(!(save && image), "save mode (lap_out) and image mode (q, acc) cannot be combined");
-    W3D_REQUIRE(!(save || image || born) || !first, "save / image / Born modes: not on the Taylor start (first)");
-    W3D_REQUIRE(!(save || image || born) || variant == 1 || M > 1,
-                "save / image / Born modes are instantiated for the default variant only (nt, 4 rows per lane)");
-    if (born) {
-        // q and dm are read while u is written (own plane and wrap planes): no shared memory
-        W3D_REQUIRE(!overlaps<T>(u, q, span) && !overlaps<T>(u, dm, span), "Born mode: q or dm shares memory with u");
-    }
-    // Illumination modes (illum, alone or with lap_out): leapfrog steps of the default variant only
-    if (illum) {
-        W3D_REQUIRE(!first, "illumination modes (illum): not on the Taylor start (first)");
-        W3D_REQUIRE(!q && !acc && !dm && !db && !sadd,
-                    "illumination modes (illum) cannot be combined with image, Born, scatter or Born-add mode");
-        W3D_REQUIRE(variant == 1 || M > 1,
-                    "illumination modes (illum) are instantiated for the default variant only (nt, 4 rows per lane)");
-        for (const T* o : {(const T*)u, u1, u2, m, b, (const T*)lap_out})
-            W3D_REQUIRE(!o || !overlaps<T>(illum, o, span), "illumination modes: illum shares memory with another grid");
-    }
-    const int mode = illum     ? (save ? kSaveIllum : kIllum)
-                     : scatter ? kScatter
-                     : born_add ? kBornAdd
-                     : save     ? kSave
-                     : image    ? kImage
-                     : born     ? kBorn
-                                : kPlain;
+    check_mode(st, M > 1 ? kFamMH : b ? kFamMB : kFamM, variant, span);
+    const int mode = st.mode;
     // reflecting faces of k_march_mh: (j_lo, j_hi, k_lo, k_hi), +-2^29 where there is none
     int mir[4] = {kNoMirror, -kNoMirror, kNoMirror, -kNoMirror};
     bool has[4] = {false, false, false, false};
@@ -960,26 +966,28 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
                         "mirror faces nearer than the stencil's half-width");
     }
     MediumParams<T> p{};
-    fill_tile_params(p, gv, h2);
-    p.u1 = u1;
-    p.u2 = u2;
-    p.m = m;
-    p.u = u;
-    p.ei0 = ei0;
-    p.ei1 = ei1;
+    fill_tile_params(p, gv, st.h2);
+    p.u1 = st.u1;
+    p.u2 = st.u2;
+    p.m = st.m;
+    p.u = st.u;
+    p.ei0 = st.ei0;
+    p.ei1 = st.ei1;
+    const Wrap& wrap = st.wrap;
     for (int q = 0; q < kMaxWrap; ++q)
         W3D_REQUIRE(wrap.src[q] < 1 || (wrap.src[q] <= gv.X && wrap.dst[q] >= 1 - gv.G && wrap.dst[q] <= gv.X + gv.G),
                     "wrap plane outside the grid");
     wrap_ranges(wrap, p.w_lo, p.w_hi, p.w_sh);
-    p.err = err;
-    p.gx = gx;
-    p.gy = gy;
-    p.gz = gz;
-    p.lap_out = lap_out;
-    p.q = born_add ? sadd : scatter ? db : q;
-    p.acc = acc;
-    p.dm = dm;
-    p.illum = illum;
+    p.err = st.err;
+    p.gx = st.gx;
+    p.gy = st.gy;
+    p.gz = st.gz;
+    // the kernels' slots: lap_out doubles as kScatter's s_out, q as kScatter's db and kBornAdd's s
+    p.lap_out = mode == kScatter ? st.s_out : st.lap_out;
+    p.q = mode == kBornAdd ? st.sadd : mode == kScatter ? st.db : st.q;
+    p.acc = st.acc;
+    p.dm = st.dm;
+    p.illum = st.illum;
     for (int q = 0; q < nbox; ++q) {
         const Box& bx = boxes[q];
         if (bx.empty()) continue;
@@ -1000,7 +1008,7 @@ void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, 
     }
     // 4 rows per lane in every kernel but k_march_m's two-row variants
     const int tj_rows = kWaves * (M == 1 && (variant & 2) ? 2 : 4);
-    const int total = plan_boxes(p, boxes, nbox, tj_rows, chunk);
+    const int total = plan_boxes(p, boxes, nbox, tj_rows, st.chunk);
     if (p.nbox == 0) return;
     if (M > 1) {
         MediumParamsH<T> ph{};
@@ -1038,12 +1046,8 @@ void launch_record(const T* u, const GridView& gv, const int* nodes, T* out, int
     HIP_OK(hipGetLastError());
 }
 
-#define W3D_MEDIUM_INST(T)                                                                              \
-    template void launch_step_medium<T>(bool, const T*, const T*, const T*, T*, const GridView&,       \
-                                        const Box*, int, int, int, const Wrap&, const double[3], u64*, \
-                                        int, hipStream_t, int, const T*, const T*, const T*, T*,       \
-                                        const T*, T*, int, const int*, const T*, const T*, const T*,   \
-                                        const T*, T*);                                                  \
+#define W3D_MEDIUM_INST(T)                                                                             \
+    template void launch_step_medium<T>(const MediumStep<T>&, hipStream_t);                            \
     template void launch_inject<T>(T*, const T*, const GridView&, const int*, const T*, int,           \
                                    const Wrap&, hipStream_t);                                          \
     template void launch_record<T>(const T*, const GridView&, const int*, T*, int, hipStream_t);

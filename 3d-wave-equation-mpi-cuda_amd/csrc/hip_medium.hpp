@@ -9,9 +9,9 @@
 
 namespace wave3d {
 
-// One time layer n >= 1 over `nbox` boxes: u = (2 u1 - u2) + m lap(u1), or on the Taylor start
-// (`first`) u = u1 + (0.5 m) lap(u1), rounded operation by operation in that order (a uniform
-// m == coef reproduces launch_step's march kernel bit for bit). h2 = (hx*hx, hy*hy, hz*hz).
+// One time layer n >= 1 over `nbox` boxes (launch_step_medium, a MediumStep): u = (2 u1 - u2) + m lap(u1),
+// or on the Taylor start (`first`) u = u1 + (0.5 m) lap(u1), rounded operation by operation in that order
+// (a uniform m == coef reproduces launch_step's march kernel bit for bit). h2 = (hx*hx, hy*hy, hz*hz).
 // err[0] = key of max |u| over the planes [ei0, ei1] (NaN ignored), err[1] untouched,
 // err[2] = non-finite flag. variant: -1 = WAVE3D_MEDIUM_VARIANT or the default; bit 0 =
 // non-temporal loads of m, bit 1 = 2 rows per lane instead of march_rows_per_thread().
@@ -22,18 +22,22 @@ namespace wave3d {
 // start u = G (u1 + (0.5 m) lap(u1)). Tables of ones give the undamped bits; err as above, of the
 // damped values.
 //
-// Modes for the adjoint-state gradient (leapfrog steps with variant 1 only; every other
-// combination is rejected; q alone is an incomplete image mode): save (lap_out non-null) also stores lap(u1), the value that entered
-// the update, at the box nodes of lap_out; image (q and acc non-null) also does
-// acc = acc + u1 * q at the box nodes, the product rounded before the add. lap_out, q and acc
-// have the strides of u; nothing outside the boxes is written and the wrap applies to u alone.
-// u and err are those of the plain step bit for bit. Per node in fp64: 40 B (save), 56 B (image).
+// Modes. A step runs in one MarchMode, named in MediumStep::mode; this is the one description of what
+// each mode computes. A mode takes its own grids and no others (kMediumModes in hip_medium.hip has the
+// set, and the rules below, one row per mode): every grid of the set non-null, every other mode grid
+// null. All mode grids have the strides of u, are touched at the box nodes alone and never through the
+// wrap, which applies to u alone. Every mode but kPlain is a leapfrog step (not `first`) and, at order 2,
+// of variant 1 alone; every violation is rejected before the launch.
 //
-// Born mode (q and dm non-null, lap_out and acc null; leapfrog steps with variant 1 only, like
-// save / image): the step of linearised (Born) modelling, image mode's transpose. u1 and u2 are
+// kSave and kImage serve the adjoint-state gradient; u and err are those of the plain step bit for bit.
+// kSave (lap_out) also stores lap(u1), the value that entered the update: one write-once stream.
+// kImage (q, acc) also does acc = acc + u1 * q, the product rounded before the add (the imaging
+// condition): a read-once stream and a read-modify-write one. Per node in fp64: 40 B (save), 56 B (image).
+//
+// kBorn (q, dm): the step of linearised (Born) modelling, image mode's transpose. u1 and u2 are
 // levels of the perturbation field, q = lap of the background field (what save mode stored) and dm
-// the perturbation of the coefficient, both read once at the box nodes with the strides of u and
-// never written: u = ((2 u1 - u2) + m lap(u1)) + dm q, with the sponge
+// the perturbation of the coefficient, both read once and never written:
+// u = ((2 u1 - u2) + m lap(u1)) + dm q, with the sponge
 // u = G (((2 u1 - G u2) + m lap(u1)) + dm q), the product dm q rounded before its add. The wrap,
 // err[0] and the non-finite flag are those of the plain step, of the Born-updated values; no store
 // beside u's. q and dm must not share memory with u. Per node in fp64: 48 B (56 B with b).
@@ -61,28 +65,24 @@ namespace wave3d {
 // laplace_density). Save mode stores D_b u1. b is read
 // at the box nodes and their six neighbours, never written. Per node in fp64: 40 B (20 B in fp32).
 //
-// Born modelling with a density perturbation: two more modes of k_march_mb (b non-null, so order 2 and
-// variant 1; leapfrog steps only; every other combination is rejected before the launch).
-// Scatter mode (db non-null, with lap_out = s_out and dm; q and acc null): the background step that
-// also stores the whole scattering term. db is the buoyancy perturbation, a level like b (x ghost
-// planes filled), read at the box nodes and their six neighbours; r = D_db u1 is formed by D_b's
-// operations with db's values in b's place, and s_out = dm D_b u1 + m r at the box nodes, both products
-// rounded, then the add. u and err are those of the plain step bit for bit; s_out must not share
-// memory with u, u1, u2, m, b, dm or db. Per node in fp64: 64 B.
-// Born-add mode (sadd non-null; lap_out, q, acc, dm and db null): the step of the perturbation field
-// with the scattering term read back, u = ((2 u1 - u2) + m D_b u1) + s, with the sponge
-// u = G (((2 u1 - G u2) + m D_b u1) + s); s is read once at the box nodes with the strides of u and
-// must not share memory with it. The wrap, err[0] and the non-finite flag are those of the updated
-// values, as in Born mode. Per node in fp64: 48 B.
+// Born modelling with a density perturbation splits Born mode's work differently, in two modes that
+// k_march_mb alone has (b non-null, so order 2 and variant 1).
+// kScatter (s_out, dm, db): the background step that also stores the whole scattering term. db is the
+// buoyancy perturbation, a level like b (x ghost planes filled), read at the box nodes and their six
+// neighbours; r = D_db u1 is formed by D_b's operations with db's values in b's place, and
+// s_out = dm D_b u1 + m r at the box nodes, both products rounded, then the add. u and err are those of
+// the plain step bit for bit; s_out must not share memory with u, u1, u2, m, b, dm or db. Per node in
+// fp64: 64 B.
+// kBornAdd (sadd): the step of the perturbation field with the scattering term s = sadd read back,
+// u = ((2 u1 - u2) + m D_b u1) + s, with the sponge u = G (((2 u1 - G u2) + m D_b u1) + s); s is read
+// once and must not share memory with u. The wrap, err[0] and the non-finite flag are those of the
+// updated values, as in Born mode. Per node in fp64: 48 B.
 //
-// Source illumination (illum non-null; all three march kernels, leapfrog steps only, variant 1 at
-// order 2): the plain step (illum mode), or with lap_out the save step (save+illum mode), that also does
-// illum = illum + lap * lap at the box nodes, lap being the value that entered the update (D_b u1 with
-// b), the product rounded before the add. One read-modify-write stream with the strides of u; nothing
-// outside the boxes is written and the wrap does not apply to it. u, the wrap, err and lap_out are
-// those of the plain step and of save mode bit for bit. Rejected before the launch: illum with first,
-// with a non-default variant at order 2, with q, acc, dm, db or sadd (image, Born, scatter and Born-add
-// modes), and an illum that shares memory with u, u1, u2, m, b or lap_out. Per node in fp64: 48 B
+// Source illumination (the diagonal of the pseudo-Hessian; all three march kernels): kIllum (illum) is the
+// plain step, kSaveIllum (lap_out, illum) the save step, that also does illum = illum + lap * lap, lap being
+// the value that entered the update (D_b u1 with b), the product rounded before the add: one more
+// read-modify-write stream. u, the wrap, err and lap_out are those of the plain step and of save mode
+// bit for bit. illum must not share memory with u, u1, u2, m, b or lap_out. Per node in fp64: 48 B
 // (illum), 56 B (save+illum); with b 56 B and 64 B.
 //
 // Division by h^2. All four march kernels and k_face_corr divide a numerator t by h^2 with div_const
@@ -102,14 +102,53 @@ namespace wave3d {
 // ahead of a wave front decays through the lower bound; there the two backends may differ in the last
 // place of a quotient (tests/test_gpu_medium_bits.py bounds it).
 constexpr int kNoMirror = -(1 << 29);
+// The modes of a step (above); the march kernels take one as their `int MODE` template argument.
+enum MarchMode : int {
+    kPlain = 0,
+    kSave = 1,
+    kImage = 2,
+    kBorn = 3,
+    kScatter = 4,
+    kBornAdd = 5,
+    kIllum = 6,
+    kSaveIllum = 7
+};
+constexpr int kMarchModes = 8;
+// its name in messages and in the Python binding: "plain", "save", "image", "born", "scatter", "born_add",
+// "illum", "save_illum"
+const char* march_mode_name(int mode);
+
+// One step: what launch_step_medium runs. The mode's own grids are named members; the rest stay null.
 template <class T>
-void launch_step_medium(bool first, const T* u1, const T* u2, const T* m, T* u, const GridView& gv,
-                        const Box* boxes, int nbox, int ei0, int ei1, const Wrap& wrap,
-                        const double h2[3], u64* err, int chunk, hipStream_t s, int variant = -1,
-                        const T* gx = nullptr, const T* gy = nullptr, const T* gz = nullptr,
-                        T* lap_out = nullptr, const T* q = nullptr, T* acc = nullptr, int order = 2,
-                        const int* mirror = nullptr, const T* b = nullptr, const T* dm = nullptr,
-                        const T* db = nullptr, const T* sadd = nullptr, T* illum = nullptr);
+struct MediumStep {
+    bool first = false;
+    const T *u1 = nullptr, *u2 = nullptr, *m = nullptr;
+    T* u = nullptr;
+    GridView gv;
+    const Box* boxes = nullptr;
+    int nbox = 0;
+    int ei0 = 0, ei1 = 0;
+    Wrap wrap;
+    double h2[3] = {1, 1, 1};
+    u64* err = nullptr;
+    int chunk = 0;
+    int variant = -1;
+    int order = 2;
+    const int* mirror = nullptr;                           // 4 entries, or null: no faces
+    const T *gx = nullptr, *gy = nullptr, *gz = nullptr;   // the sponge tables
+    const T* b = nullptr;                                  // the buoyancy 1 / rho
+    MarchMode mode = kPlain;
+    T* lap_out = nullptr;     // kSave, kSaveIllum
+    const T* q = nullptr;     // kImage, kBorn
+    T* acc = nullptr;         // kImage
+    const T* dm = nullptr;    // kBorn, kScatter
+    const T* db = nullptr;    // kScatter
+    T* s_out = nullptr;       // kScatter
+    const T* sadd = nullptr;  // kBornAdd
+    T* illum = nullptr;       // kIllum, kSaveIllum
+};
+template <class T>
+void launch_step_medium(const MediumStep<T>& st, hipStream_t s);
 
 // Central second-derivative weight c_d of the star stencil of `order` (2, 4, 8), d = 0 .. order / 2:
 // the double quotient of its two integers (order 4: -5/2, 4/3, -1/12; order 8: -205/72, 8/5, -1/5,

@@ -422,7 +422,7 @@ class MediumSolver:
         p = self.problem
         N, K, dt = p.N, p.timesteps, p.torch_dtype
         s = _HipSetup(self)
-        dev, M, box, wrap, h2 = s.dev, s.M, s.box, s.wrap, s.h2
+        dev, M, box = s.dev, s.M, s.box
         with torch.cuda.device(dev):
             if dft is not None:
                 F = dft[0].numel()
@@ -430,7 +430,7 @@ class MediumSolver:
             lv = [s.level() for _ in range(3)]
             m = s.level()
             s.medium(m, lv[0])
-            step_kw, taper, g = s.step_kw, s.taper, s.g
+            step, g = s.bind_step(m), s.g
             if self.u0 is not None:
                 lv[0][M:N + 1 + M] = self.u0.to(dt).to(dev)
                 reference._wrap_x(lv[0], N, M)
@@ -456,8 +456,7 @@ class MediumSolver:
                     u[:, N, :] = 0
                     u[:, :, 0] = 0
                     u[:, :, N] = 0
-                kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=stat[3 * n:3 * n + 3],
-                                    stat_i=(M, N + M), wrap=wrap, variant=self.variant, taper=taper, **step_kw)
+                step(u1, u2, u, first=n == 1, stat=stat[3 * n:3 * n + 3], variant=self.variant)
                 s.inject(u, m, g[n - 1])
                 s.record(u, traces[n])
                 if dft is not None and n % every == 0:
@@ -579,7 +578,7 @@ class MediumSolver:
         p = self.problem
         N, K, dt = p.N, p.timesteps, p.torch_dtype
         s = _HipSetup(self)
-        dev, c, M, box, wrap, h2, level = s.dev, s.c, s.M, s.box, s.wrap, s.h2, s.level
+        dev, c, M, box, h2, level = s.dev, s.c, s.M, s.box, s.h2, s.level
         with torch.cuda.device(dev):
             if segment is None:
                 segment = best_gradient_segment(K, wrt_density=wrt_density, illumination=illumination)
@@ -605,7 +604,7 @@ class MediumSolver:
             hl = level() if illumination else None  # h = sum q^n q^n, added to by the forward pass proper alone
             ck = [(level(), level()) for _ in segs[:-1]]
             mc = s.medium(m, lv[0])
-            step_kw, tt, taper, gsrc, g = s.step_kw, s.tt, s.taper, s.gsrc, s.g
+            step, tt, gsrc, g = s.bind_step(m), s.tt, s.gsrc, s.g
             traces = torch.zeros(K + 1, self.nrec, dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
             scratch = kernels.new_err(1, device=dev)  # statistics of the recomputed steps (those of `stat` again)
@@ -616,9 +615,8 @@ class MediumSolver:
 
             def forward_step(n, slot, save, illum=None):
                 u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
-                kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=slot, stat_i=(M, N + M), wrap=wrap,
-                                    variant=None if save is not None else self.variant, taper=taper, lap_out=save,
-                                    illum=illum, **step_kw)
+                step(u1, u2, u, first=n == 1, stat=slot, variant=None if save is not None else self.variant,
+                     lap_out=save, illum=illum)
                 s.inject(u, m, g[n - 1])
 
             # forward pass: run()'s steps; checkpoints before the segments, q of the last segment
@@ -666,9 +664,7 @@ class MediumSolver:
                     recomputed += b - a + 1
                 for n in range(b - 1, a - 2, -1):  # q^n is what forward step n + 1 saved
                     u1, u2, u = ad[(n + 1) % 3], ad[(n + 2) % 3], ad[n % 3]
-                    kernels.step_medium(u1, u2, m, u, box, first=False, h2=h2, stat=astat[3 * n:3 * n + 3],
-                                        stat_i=(M, N + M), wrap=wrap, taper=taper, image=(qb[n + 1 - a], acc),
-                                        **step_kw)
+                    step(u1, u2, u, first=False, stat=astat[3 * n:3 * n + 3], image=(qb[n + 1 - a], acc))
                     finish_level(u, n, a_dev[n - 1])
                     if wrt_density:  # u1 = mu^{n+1}, injected and wrapped; its level is reused two steps on
                         kernels.face_correlation(u1, ub[n - (a - 1)], accb, box, h2=h2)
@@ -779,7 +775,7 @@ class MediumSolver:
         N, K, dt = p.N, p.timesteps, p.torch_dtype
         F = f.numel()
         s = _HipSetup(self)
-        dev, c, M, box, wrap, h2, level = s.dev, s.c, s.M, s.box, s.wrap, s.h2, s.level
+        dev, c, M, box, level = s.dev, s.c, s.M, s.box, s.level
         with torch.cuda.device(dev):
             nlev = gradient_dft_levels(F, density=p.density is not None)
             s.require_levels(nlev, f"gradient_dft() with {F} frequencies")
@@ -788,7 +784,7 @@ class MediumSolver:
             m, ql = level(), level()          # ql: the q^p of the step at hand
             spec = [[level() for _ in range(F)] for _ in range(4)]  # Qre, Qim, Mre, Mim
             mc = s.medium(m, lv[0])
-            step_kw, tt, taper, gsrc, g = s.step_kw, s.tt, s.taper, s.gsrc, s.g
+            step, tt, gsrc, g = s.bind_step(m), s.tt, s.gsrc, s.g
             ctab, stab = (t.contiguous().to(dev) for t in reference.dft_tables(f, range(K), c["tau"], dt))
             traces = torch.zeros(K + 1, self.nrec, dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
@@ -799,9 +795,7 @@ class MediumSolver:
             s.record(lv[0], traces[0])
             for n in range(1, K + 1):
                 u1, u2, u = lv[(n + 2) % 3], lv[(n + 1) % 3], lv[n % 3]
-                kernels.step_medium(u1, u2, m, u, box, first=n == 1, h2=h2, stat=stat[3 * n:3 * n + 3],
-                                    stat_i=(M, N + M), wrap=wrap, taper=taper, lap_out=ql if n >= 2 else None,
-                                    **step_kw)
+                step(u1, u2, u, first=n == 1, stat=stat[3 * n:3 * n + 3], lap_out=ql if n >= 2 else None)
                 s.inject(u, m, g[n - 1])
                 s.record(u, traces[n])
                 if n >= 2 and (n - 1) % every == 0:
@@ -823,8 +817,7 @@ class MediumSolver:
                 u1, u2, u = lv[(n + 1) % 3], lv[(n + 2) % 3], lv[n % 3]
                 if n % every == 0:  # u1 = mu^{n+1}, injected and wrapped
                     kernels.dft_accumulate(u1, spec[2], spec[3], box, ctab[n], stab[n])
-                kernels.step_medium(u1, u2, m, u, box, first=False, h2=h2, stat=astat[3 * n:3 * n + 3],
-                                    stat_i=(M, N + M), wrap=wrap, taper=taper, **step_kw)
+                step(u1, u2, u, first=False, stat=astat[3 * n:3 * n + 3])
                 finish_level(u, n, a_dev[n - 1])
             ev[3].record()
             _require_finite(astat, "gradient_dft()", "adjoint pass")
@@ -914,7 +907,7 @@ class MediumSolver:
         p = self.problem
         N, K, dt = p.N, p.timesteps, p.torch_dtype
         s = _HipSetup(self)
-        dev, c, M, box, wrap, h2, level = s.dev, s.c, s.M, s.box, s.wrap, s.h2, s.level
+        dev, c, M, level = s.dev, s.c, s.M, s.level
         with torch.cuda.device(dev):
             nlev = born_levels(density=p.density is not None, ddensity=dr is not None)
             s.require_levels(nlev, "born(): the schedule")
@@ -924,7 +917,7 @@ class MediumSolver:
             m, dm, q = level(), level(), level()  # with ddensity, q holds s = dm q + m D_db u instead
             db = None if dr is None else level()
             s.medium(m, lv[0], dwavelet=dw)
-            step_kw, taper, g, dg = s.step_kw, s.taper, s.g, s.dg
+            step, g, dg = s.bind_step(m), s.g, s.dg
             if ds is not None:  # None: dm = 0, the scattering term adds zeros
                 dm.copy_(reference.medium_coefficient(ds, c["tau"], N, dt, M, p.density))
             if dr is not None:  # born_medium's dm and db
@@ -937,7 +930,6 @@ class MediumSolver:
             dtraces = torch.zeros(K + 1, self.nrec, dtype=dt, device=dev)
             stat = kernels.new_err(K + 1, device=dev)
             dstat = kernels.new_err(K + 1, device=dev)
-            common = dict(h2=h2, stat_i=(M, N + M), wrap=wrap, taper=taper, **step_kw)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
             for n in range(1, K + 1):
@@ -952,12 +944,11 @@ class MediumSolver:
                     save, read = dict(lap_out=q), dict(born=(q, dm))
                 else:
                     save, read = dict(scatter=(q, dm, db)), dict(born_add=q)
-                kernels.step_medium(u1, u2, m, u, box, first=first, stat=stat[3 * n:3 * n + 3],
-                                    variant=self.variant if first else None, **save, **common)
+                variant = self.variant if first else None
+                step(u1, u2, u, first=first, stat=stat[3 * n:3 * n + 3], variant=variant, **save)
                 s.inject(u, m, g[n - 1])
                 # the step of du with the scattering term, then the perturbed source terms
-                kernels.step_medium(d1, d2, m, d, box, first=first, stat=dstat[3 * n:3 * n + 3],
-                                    variant=self.variant if first else None, **read, **common)
+                step(d1, d2, d, first=first, stat=dstat[3 * n:3 * n + 3], variant=variant, **read)
                 s.inject(d, dm, g[n - 1])
                 if dg is not None:
                     s.inject(d, m, dg[n - 1])
@@ -1080,6 +1071,22 @@ class _HipSetup:
             self.rec_tab = kernels.point_tables(*reference.receiver_tables(sv.receiver_positions, N, dt, sv.interp, M),
                                                 lv0)
         return mc
+
+    def bind_step(self, m):
+        """``step(u1, u2, u, *, first, stat, variant=None, **mode)``: ``ops.kernels.step_medium`` on the coefficient
+        level ``m`` with what every step of a driver shares bound (the box, ``h2``, the statistic's planes, the
+        wrap, the sponge and ``step_kw``), so that a call names what varies: the three levels, ``first``, the
+        stat slot, the variant and the mode keyword. Call it after :meth:`medium`, which completes
+        ``step_kw`` and ``taper``."""
+        from ..ops import kernels
+
+        N, box = self.solver.problem.N, self.box
+        bound = dict(h2=self.h2, stat_i=(self.M, N + self.M), wrap=self.wrap, taper=self.taper, **self.step_kw)
+
+        def step(u1, u2, u, **varies):
+            kernels.step_medium(u1, u2, m, u, box, **bound, **varies)
+
+        return step
 
     def inject(self, u, m, g) -> None:
         """The source terms of one step into ``u``: ``g`` = the step's row of ``self.g`` / ``self.dg``."""

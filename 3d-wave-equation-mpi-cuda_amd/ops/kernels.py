@@ -16,6 +16,9 @@ against fp64.
 """
 from __future__ import annotations
 
+import functools
+from typing import NamedTuple
+
 import torch
 
 from .._native import load
@@ -55,11 +58,20 @@ def _check_grid(*ts: torch.Tensor) -> list[int]:
 
 
 def _check_box(box, gv) -> list[int]:
-    i0, i1, j0, j1, k0, k1 = (int(v) for v in box)
+    i0, i1, j0, j1, k0, k1 = map(int, box)
     nx, ny, nz = gv[0], gv[1], gv[2]
     if not (1 <= i0 and i1 <= nx - 2 and 1 <= j0 and j1 <= ny - 2 and 1 <= k0 and k1 <= nz - 2):
         raise ValueError(f"box {box} outside the owned region of a {nx}x{ny}x{nz} grid")
     return [i0, i1, j0, j1, k0, k1]
+
+
+def _check_boxes(boxes, gv) -> list[list[int]]:
+    """``boxes``: a single box or 1..7 of them, each inside the owned region of the grid view ``gv``."""
+    if isinstance(boxes[0], int):
+        boxes = [boxes]
+    if not 1 <= len(boxes) <= 7:
+        raise ValueError("1..7 boxes per launch")
+    return [_check_box(b, gv) for b in boxes]
 
 
 def _check_tables(u, tx, ty, tz):
@@ -94,11 +106,7 @@ def step(u1, u2, u, boxes, *, first: bool, err_i, tx, ty, tz, coefs, err,
     ybuf0, ybuf1] tensors or None, [zk0, zk1, yj0, yj1]).
     """
     gv = _check_grid(u1, u2, u)
-    if isinstance(boxes[0], int):
-        boxes = [boxes]
-    if not 1 <= len(boxes) <= 7:
-        raise ValueError("1..7 boxes per launch")
-    bl = [_check_box(b, gv) for b in boxes]
+    bl = _check_boxes(boxes, gv)
     _check_tables(u, tx, ty, tz)
     if err.dtype != torch.int64 or err.numel() < 3 or not err.is_cuda:
         raise ValueError("err must be >= 3 int64 device slots (new_err())")
@@ -369,11 +377,72 @@ def _check_taper(taper, u) -> list[int]:
     return [t.data_ptr() for t in taper]
 
 
+class _MediumMode(NamedTuple):
+    """One row of the mode table of :func:`step_medium` (``csrc/hip_medium.hpp`` describes the modes)."""
+    name: str                  # its key in the binding's ``medium_modes``
+    grids: dict                # the keywords that select it -> the name(s) of the grid(s) each one carries
+    taylor: bool = False       # runs on the Taylor start (``first``)
+    any_variant: bool = False  # every variant has it; otherwise, at order 2, the default one alone
+    buoyancy: bool = False     # needs a buoyancy (k_march_mb alone has it)
+    apart: tuple = ()          # (grid, the grids it must not share memory with): written, or read while u is
+
+
+_LEVELS = ("u", "u1", "u2", "m", "buoyancy")
+_MEDIUM_MODES = (
+    _MediumMode("plain", {}, taylor=True, any_variant=True),
+    _MediumMode("save", dict(lap_out="lap_out")),
+    _MediumMode("image", dict(image=("q", "acc"))),
+    _MediumMode("born", dict(born=("q", "dm")), apart=(("q", ("u",)), ("dm", ("u",)))),
+    _MediumMode("scatter", dict(scatter=("s_out", "dm", "dbuoyancy")), buoyancy=True,
+                apart=(("s_out", _LEVELS + ("dm", "dbuoyancy")),)),
+    _MediumMode("born_add", dict(born_add="s"), buoyancy=True, apart=(("s", ("u",)),)),
+    _MediumMode("illum", dict(illum="illum"), apart=(("illum", _LEVELS),)),
+    _MediumMode("save_illum", dict(lap_out="lap_out", illum="illum"), apart=(("illum", _LEVELS + ("lap_out",)),)),
+)
+_MODE_KEYWORDS = ("lap_out", "image", "born", "scatter", "born_add", "illum")
+_MODE_OF_KEYWORDS = {frozenset(r.grids): r for r in _MEDIUM_MODES}
+_NATIVE_NAMES = dict(dbuoyancy="db", s="sadd")  # where the native entry point names a mode grid differently
+
+
+@functools.lru_cache(maxsize=None)  # small-N runs are host-bound; measured in profiles/medium_step_modes.txt
+def medium_mode(present: tuple, first: bool, order: int, variant: str | None, buoyancy: bool):
+    """The mode of a :func:`step_medium` call and the variant it runs. ``present``: one flag per mode
+    keyword, in the order ``lap_out``, ``image``, ``born``, ``scatter``, ``born_add``, ``illum``, saying
+    whether it is given; ``buoyancy``: whether one is given. Returns ``(row of the mode table, variant)``
+    or raises ``ValueError``. Pure: no tensor and no native module is touched."""
+    given = [k for k, flag in zip(_MODE_KEYWORDS, present) if flag]
+    if order not in (2, 4, 8):
+        raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
+    if variant not in _MEDIUM_VARIANTS:
+        raise ValueError(f"unknown variant {variant!r}")
+    if order != 2 and variant is not None:
+        raise ValueError("the ablation variants exist for order 2 only")
+    if buoyancy:
+        if order != 2:
+            raise ValueError(f"variable density (buoyancy) exists for space order 2 only, not {order!r}")
+        if variant not in (None, "nt"):
+            raise ValueError(f"variable density (buoyancy) exists for the default variant only, not {variant!r}")
+    mode = _MODE_OF_KEYWORDS.get(frozenset(given))
+    if mode is None:
+        raise ValueError(f"{', '.join(sorted(given))} cannot be combined: a step runs in one mode, selected by "
+                         "no mode keyword, by one of them, or by lap_out with illum")
+    if mode.buoyancy and not buoyancy:
+        raise ValueError(f"{mode.name} mode needs a buoyancy (variable density)")
+    if first and not mode.taylor:
+        raise ValueError(f"{mode.name} mode: not on the Taylor start (first=True)")
+    if not mode.any_variant and variant not in (None, "nt"):
+        raise ValueError(f"{mode.name} mode exists for the default variant only, not {variant!r}")
+    if order == 2 and (buoyancy or not mode.any_variant):
+        variant = "nt"  # by name: the default may have been changed for an ablation run
+    return mode, variant
+
+
 def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None, chunk: int = 0,
                 variant: str | None = None, taper=None, lap_out=None, image=None, order: int = 2,
                 mirror=None, buoyancy=None, born=None, scatter=None, born_add=None, illum=None) -> None:
     """One layer of ``u_tt = c^2 (lap u + f)`` over ``boxes``: ``u = (2 u1 - u2) + m lap(u1)``, on
     the Taylor start (``first``) ``u = u1 + (0.5 m) lap(u1)``, with ``m = c^2 tau^2`` per node.
+    ``csrc/hip_medium.hpp`` has the arithmetic of every form named here, operation by operation.
 
     The grids are dense ``[nx][ny][nz]`` tensors or :func:`alloc_level` views with identical
     strides. h2 = (hx2, hy2, hz2); stat = >= 3 int64 slots (``new_err()``): slot 0 receives the
@@ -383,176 +452,69 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
     the same with 2 rows per lane.
 
     ``taper`` = (gx, gy, gz): the absorbing sponge, 1-D device tensors of exactly nx, ny, nz factors
-    in (0, 1] (storage indexing). With ``G = gx[i] (gy[j] gz[k])`` the step is the damped leapfrog
-    ``u = G ((2 u1 - G u2) + m lap(u1))``, on the Taylor start ``u = G (u1 + (0.5 m) lap(u1))``;
-    tables of ones give the undamped bits. None: the undamped kernels.
+    in (0, 1] (storage indexing); tables of ones give the undamped bits. None: the undamped kernels.
 
-    Two modes serve the adjoint-state gradient; ``u`` and ``stat`` stay those of the plain step bit
-    for bit. ``lap_out`` (save mode): a grid that receives ``lap(u1)``, the value that entered the
-    update, at the box nodes. ``image = (q, acc)`` (image mode): ``acc = acc + u1 * q`` at the box
-    nodes, the product rounded before the add. These grids match ``u`` in shape, dtype, device and
-    strides; nothing outside the boxes is written and the wrap applies to ``u`` alone. Both modes
-    exist for leapfrog steps (``first=False``) of the default variant only and cannot be combined.
+    ``order`` = 2 (the 7-point Laplacian; ``mirror`` is not used), 4 or 8: the star stencil of half-width
+    M = order / 2 (``ops.reference.laplace_star`` has the scheme); ``variant`` must then be None. The box
+    and mirror contract, checked here before any launch: the boxes keep M planes from both ends of the
+    storage in x. ``mirror = (j_lo, j_hi, k_lo, k_hi)`` names the storage indices of reflecting (Dirichlet)
+    faces in y and z, an entry or the whole tuple may be None. The boxes lie strictly inside their faces,
+    a pair of faces is at least M apart, every reflected node exists in storage, and on a side without a
+    face the boxes keep M nodes from the storage edge.
 
-    ``born = (q, dm)`` (Born mode, image mode's transpose): the step of linearised modelling on the
-    levels ``u1``, ``u2`` of a perturbation field, ``u = ((2 u1 - u2) + m lap(u1)) + dm q``, with the
-    sponge ``u = G (((2 u1 - G u2) + m lap(u1)) + dm q)``; ``q`` is the Laplacian of the background
-    field (what ``lap_out`` received) and ``dm`` the perturbation of ``m``, the product rounded before
-    its add. Both are read at the box nodes and never written; the wrap and ``stat`` are those of the
-    plain step, of the updated values. They match ``u`` in shape, dtype, device and strides and must
-    not share memory with it. For leapfrog steps of the default variant only, and not together with
-    ``lap_out`` or ``image``.
+    ``buoyancy``: a grid ``b = 1 / rho`` (variable density): ``lap(u1)`` becomes ``div(b grad u1)``
+    (``ops.reference.laplace_density`` has the scheme) in every form and mode, and ``m = rho c^2 tau^2``.
+    Its ghost planes are filled like those of ``u1``; it is never written. For ``order`` 2 and the default
+    variant only.
 
-    ``order`` = 2 (the 7-point Laplacian: the kernels above, ``mirror`` is not used), 4 or 8: the star
-    stencil of half-width M = order / 2 (``k_march_mh``; ``ops.reference.laplace_star`` has the
-    scheme), every mode and the sponge as above; ``variant`` must then be None. The box and mirror
-    contract, checked here before any launch (``ValueError``): the boxes keep M planes from both
-    ends of the storage in x, whose neighbours always come from storage. ``mirror = (j_lo, j_hi,
-    k_lo, k_hi)`` names the storage indices of reflecting (Dirichlet) faces in y and z, an entry or
-    the whole tuple may be None: a neighbour beyond a face f is read as ``-u1[2 f - j]``, the face
-    itself as stored. The boxes lie strictly inside their faces, a pair of faces is at least M
-    apart, every reflected node exists in storage, and on a side without a face the boxes keep M
-    nodes from the storage edge.
+    The mode keywords: a step runs in one mode, selected by none of them (the plain step), by one of them,
+    or by ``lap_out`` together with ``illum``. Every mode but the plain one is a leapfrog step
+    (``first=False``) of the default variant.
+      * ``lap_out`` (save): a grid that receives the Laplacian that entered the update, at the box nodes.
+      * ``image = (q, acc)``: ``acc = acc + u1 * q`` at the box nodes (the adjoint-state imaging condition).
+      * ``born = (q, dm)``: the step of linearised modelling, ``u`` also receives ``+ dm q``; ``q`` is what
+        ``lap_out`` received in the background step, ``dm`` the perturbation of ``m``.
+      * ``scatter = (s_out, dm, dbuoyancy)`` (needs ``buoyancy``): the background step that also stores the
+        scattering term ``s_out = dm D_b u1 + m D_db u1`` of a density perturbation.
+      * ``born_add = s`` (needs ``buoyancy``): the step of the perturbation field, ``u`` also receives ``+ s``.
+      * ``illum = h``, alone or with ``lap_out``: also ``h = h + lap * lap`` (the source illumination).
+    In save, image, scatter and the illum modes ``u`` and ``stat`` are those of the plain step bit for bit.
+    Mode grids match ``u`` in shape, dtype, device and strides; they are read or written at the box nodes
+    alone and the wrap applies to ``u`` alone. ``q`` and ``dm`` of ``born`` and ``s`` must not share memory with
+    ``u``; ``s_out`` not with any other grid of the call; ``h`` not with ``u``, ``u1``, ``u2``, ``m``, ``buoyancy``
+    or ``lap_out``.
 
-    ``buoyancy``: a grid ``b = 1 / rho`` (variable density, ``k_march_mb``): ``lap(u1)`` becomes
-    ``div(b grad u1)`` (``ops.reference.laplace_density`` has the scheme) in every form above, the
-    sponge and both modes included (``lap_out`` then receives that value), and ``m = rho c^2 tau^2``. It
-    matches ``u`` in shape, dtype, device and strides, its ghost planes filled like those of ``u1``;
-    it is read at the box nodes and their six neighbours and never written. For ``order`` 2 and the
-    default variant only (``ValueError`` before any launch otherwise).
-
-    Two more modes of the density step serve Born modelling with a density perturbation; both need
-    ``buoyancy`` (so order 2 and the default variant), exist for leapfrog steps only and cannot be
-    combined with each other or with ``lap_out``, ``image`` or ``born``. ``scatter = (s_out, dm,
-    dbuoyancy)``: the background step, ``u`` and ``stat`` those of the plain step bit for bit, that also
-    stores the scattering term ``s_out = dm D_b u1 + m D_db u1`` at the box nodes (both products rounded,
-    then the add), ``D_db`` being ``D_b``'s operations with the buoyancy perturbation ``dbuoyancy`` in
-    b's place: a grid like ``buoyancy``, read at the box nodes and their six neighbours. ``s_out`` must
-    not share memory with any other grid of the call. ``born_add = s``: the step of the perturbation
-    field that adds it, ``u = ((2 u1 - u2) + m D_b u1) + s``, with the sponge
-    ``u = G (((2 u1 - G u2) + m D_b u1) + s)``; ``s`` is read at the box nodes and must not share memory
-    with ``u``; the wrap and ``stat`` are those of the updated values. All these grids match ``u`` in
-    shape, dtype, device and strides.
-
-    ``illum = h`` (illum mode; with ``lap_out`` save+illum mode): the step also does ``h = h + lap * lap``
-    at the box nodes, ``lap`` being the value that entered the update (``div(b grad u1)`` with
-    ``buoyancy``), the product rounded before the add: the source illumination of
-    ``MediumSolver.gradient(illumination=True)``. ``u``, the wrap, ``stat`` and ``lap_out`` stay those of
-    the plain step and of save mode bit for bit; nothing outside the boxes is written and the wrap does
-    not apply to ``h``. It matches ``u`` in shape, dtype, device and strides and must not share memory
-    with ``u``, ``u1``, ``u2``, ``m``, ``buoyancy`` or ``lap_out``. For leapfrog steps of the default
-    variant only, at every order and with a buoyancy; combinable with ``lap_out`` alone, not with
-    ``image``, ``born``, ``scatter`` or ``born_add``.
-    """
-    if order not in (2, 4, 8):
-        raise ValueError(f"space order must be 2, 4 or 8, not {order!r}")
-    if order != 2 and variant is not None:
-        raise ValueError("the ablation variants exist for order 2 only")
-    extra = []
-    if buoyancy is not None:
-        if order != 2:
-            raise ValueError(f"variable density (buoyancy) exists for space order 2 only, not {order!r}")
-        if variant not in (None, "nt"):
-            raise ValueError(f"variable density (buoyancy) exists for the default variant only, not {variant!r}")
-        if not isinstance(buoyancy, torch.Tensor):
-            raise ValueError("buoyancy must be a tensor")
-        variant = "nt"
-    if scatter is not None or born_add is not None:
-        if scatter is not None and born_add is not None:
-            raise ValueError("scatter mode (scatter) and Born-add mode (born_add) cannot be combined")
-        if lap_out is not None or image is not None or born is not None:
-            raise ValueError("scatter / Born-add modes cannot be combined with save mode (lap_out), image mode "
-                             "(image) or Born mode (born)")
-        if buoyancy is None:
-            raise ValueError("scatter / Born-add modes need a buoyancy (variable density)")
-        if first:
-            raise ValueError("scatter / Born-add modes: not on the Taylor start (first=True)")
-        if scatter is not None:
-            if len(scatter) != 3:
-                raise ValueError("scatter = (s_out, dm, dbuoyancy)")
-            extra = list(scatter)
+    Every violation is a ``ValueError`` before any launch."""
+    values = (lap_out, image, born, scatter, born_add, illum)  # in the order of _MODE_KEYWORDS
+    mode, variant = medium_mode((lap_out is not None, image is not None, born is not None, scatter is not None,
+                                 born_add is not None, illum is not None), first, order, variant, buoyancy is not None)
+    grids, native = {}, {}  # the mode's grids by name; their pointers under the native entry point's names
+    for key, names in mode.grids.items():
+        value = values[_MODE_KEYWORDS.index(key)]
+        if isinstance(names, str):
+            grids[names] = value
+        elif len(value) != len(names):
+            raise ValueError(f"{key} = ({', '.join(names)})")
         else:
-            extra = [born_add]
-        if not all(isinstance(t, torch.Tensor) for t in extra):
-            raise ValueError("s_out, dm, dbuoyancy and s must be tensors")
-    if born is not None:
-        if lap_out is not None or image is not None:
-            raise ValueError("Born mode (born) cannot be combined with save mode (lap_out) or image mode (image)")
-        if first:
-            raise ValueError("Born mode: not on the Taylor start (first=True)")
-        if variant not in (None, "nt"):
-            raise ValueError(f"Born mode exists for the default variant only, not {variant!r}")
-        if order == 2:
-            variant = "nt"
-        if len(born) != 2:
-            raise ValueError("born = (q, dm)")
-        if not all(isinstance(t, torch.Tensor) for t in born):
-            raise ValueError("q and dm must be tensors")
-        extra = list(born)
-    if lap_out is not None or image is not None:
-        if lap_out is not None and image is not None:
-            raise ValueError("save mode (lap_out) and image mode (image) cannot be combined")
-        if first:
-            raise ValueError("save / image modes: not on the Taylor start (first=True)")
-        if variant not in (None, "nt"):
-            raise ValueError(f"save / image modes exist for the default variant only, not {variant!r}")
-        if order == 2:
-            variant = "nt"
-        if image is not None:
-            if len(image) != 2:
-                raise ValueError("image = (q, acc)")
-            extra = list(image)
-        else:
-            extra = [lap_out]
-        if not all(isinstance(t, torch.Tensor) for t in extra):
-            raise ValueError("lap_out, q and acc must be tensors")
-    if illum is not None:
-        if image is not None or born is not None or scatter is not None or born_add is not None:
-            raise ValueError("illumination modes (illum) cannot be combined with image mode (image), Born mode "
-                             "(born), scatter mode (scatter) or Born-add mode (born_add)")
-        if first:
-            raise ValueError("illumination modes (illum): not on the Taylor start (first=True)")
-        if variant not in (None, "nt"):
-            raise ValueError(f"illumination modes (illum) exist for the default variant only, not {variant!r}")
-        if order == 2:
-            variant = "nt"
-        if not isinstance(illum, torch.Tensor):
-            raise ValueError("illum must be a tensor")
-        extra = extra + [illum]
-    if buoyancy is not None:
-        extra = extra + [buoyancy]
-    gv = _check_grid_strided(u1, u2, m, u, *extra)
-    if illum is not None:
-        h_0, h_1 = _grid_span(illum)
-        for t, name in zip((u, u1, u2, m, buoyancy, lap_out), ("u", "u1", "u2", "m", "buoyancy", "lap_out")):
-            if t is None:
-                continue
-            t0, t1 = _grid_span(t)
-            if h_0 < t1 and t0 < h_1:
-                raise ValueError(f"illumination modes: illum shares memory with {name}")
-    if born is not None:
-        u_0, u_1 = _grid_span(u)
-        for t, name in zip(born, ("q", "dm")):
-            t0, t1 = _grid_span(t)
-            if u_0 < t1 and t0 < u_1:
-                raise ValueError(f"Born mode: {name} shares memory with u")
-    if scatter is not None:
-        s_0, s_1 = _grid_span(scatter[0])
-        for t, name in zip((u, u1, u2, m, buoyancy, scatter[1], scatter[2]),
-                           ("u", "u1", "u2", "m", "buoyancy", "dm", "dbuoyancy")):
-            t0, t1 = _grid_span(t)
-            if s_0 < t1 and t0 < s_1:
-                raise ValueError(f"scatter mode: s_out shares memory with {name}")
-    if born_add is not None:
-        u_0, u_1 = _grid_span(u)
-        t0, t1 = _grid_span(born_add)
-        if u_0 < t1 and t0 < u_1:
-            raise ValueError("Born-add mode: s shares memory with u")
-    if isinstance(boxes[0], int):
-        boxes = [boxes]
-    if not 1 <= len(boxes) <= 7:
-        raise ValueError("1..7 boxes per launch")
-    bl = [_check_box(b, gv) for b in boxes]
+            grids.update(zip(names, value))
+    for name, t in grids.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor")
+        native[_NATIVE_NAMES.get(name, name)] = t.data_ptr()
+    if buoyancy is None:
+        gv = _check_grid_strided(u1, u2, m, u, *grids.values())
+    elif not isinstance(buoyancy, torch.Tensor):
+        raise ValueError("buoyancy must be a tensor")
+    else:
+        gv = _check_grid_strided(u1, u2, m, u, buoyancy, *grids.values())
+    if mode.apart:
+        named = dict(grids, u=u, u1=u1, u2=u2, m=m)
+        if buoyancy is not None:
+            named["buoyancy"] = buoyancy
+        for name, others in mode.apart:
+            _check_spans_apart(name, _grid_span(named[name]), [(o, _grid_span(named[o])) for o in others if o in named],
+                               mode.name)
+    bl = _check_boxes(boxes, gv)
     mir = []
     if order != 2:
         from .reference import _check_star_box
@@ -560,32 +522,34 @@ def step_medium(u1, u2, m, u, boxes, *, first: bool, h2, stat, stat_i, wrap=None
         no = _C().no_mirror
         for b in bl:
             mir = [no if f is None else int(f) for f in _check_star_box(gv[:3], b, order // 2, mirror)]
-    if len(h2) != 3 or not all(float(v) > 0 for v in h2):
+    h2 = [float(v) for v in h2]
+    if len(h2) != 3 or not all(v > 0 for v in h2):
         raise ValueError("h2 = (hx2, hy2, hz2), all > 0")
     if stat.dtype != torch.int64 or stat.numel() < 3 or not stat.is_cuda or not stat.is_contiguous():
         raise ValueError("stat must be >= 3 contiguous int64 device slots (new_err())")
     w = _check_wrap(wrap, gv)
-    if variant not in _MEDIUM_VARIANTS:
-        raise ValueError(f"unknown variant {variant!r}")
-    gp = _check_taper(taper, u)
-    fn = getattr(_C(), "k_step_medium_" + _sfx(u))
-    fn(bool(first), u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, bl, int(stat_i[0]),
-       int(stat_i[1]), w, [float(v) for v in h2], stat.data_ptr(), int(chunk), _stream(),
-       _MEDIUM_VARIANTS[variant], *gp,
-       lap_out.data_ptr() if lap_out is not None else scatter[0].data_ptr() if scatter is not None else 0,
-       *((image[0].data_ptr(), image[1].data_ptr()) if image is not None
-         else (born[0].data_ptr(), 0) if born is not None else (0, 0)), int(order), mir,
-       buoyancy.data_ptr() if buoyancy is not None else 0,
-       born[1].data_ptr() if born is not None else scatter[1].data_ptr() if scatter is not None else 0,
-       scatter[2].data_ptr() if scatter is not None else 0,
-       born_add.data_ptr() if born_add is not None else 0,
-       illum.data_ptr() if illum is not None else 0)
+    C = _C()
+    getattr(C, "k_step_medium_" + _sfx(u))(
+        bool(first), u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, bl, int(stat_i[0]),
+        int(stat_i[1]), w, h2, stat.data_ptr(), int(chunk), _stream(), C.medium_modes[mode.name],
+        _MEDIUM_VARIANTS[variant], int(order), mir, *_check_taper(taper, u),
+        0 if buoyancy is None else buoyancy.data_ptr(), **native)
 
 
 def _grid_span(t: torch.Tensor) -> tuple[int, int]:
     """[first byte, one past the last byte) of the memory a grid view covers."""
     n = sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1
     return t.data_ptr(), t.data_ptr() + n * t.element_size()
+
+
+def _check_spans_apart(name: str, span, others, mode: str | None = None) -> None:
+    """Raises if the grid ``name`` with the :func:`_grid_span` ``span`` shares memory with one of ``others``,
+    (name, span) pairs; ``mode`` names the mode of :func:`step_medium` in the message."""
+    t0, t1 = span
+    for other, (o0, o1) in others:
+        if t0 < o1 and o0 < t1:
+            where = "" if mode is None else f"{mode} mode: "
+            raise ValueError(f"{where}{name} shares memory with {other}")
 
 
 def face_correlation(a, v, acc, boxes, *, h2, chunk: int = 0) -> None:
@@ -602,16 +566,8 @@ def face_correlation(a, v, acc, boxes, *, h2, chunk: int = 0) -> None:
     if not all(isinstance(t, torch.Tensor) for t in (a, v, acc)):
         raise ValueError("a, v and acc must be tensors")
     gv = _check_grid_strided(a, v, acc)
-    c0, c1 = _grid_span(acc)
-    for t, name in ((a, "a"), (v, "v")):
-        t0, t1 = _grid_span(t)
-        if c0 < t1 and t0 < c1:
-            raise ValueError(f"acc shares memory with {name}")
-    if isinstance(boxes[0], int):
-        boxes = [boxes]
-    if not 1 <= len(boxes) <= 7:
-        raise ValueError("1..7 boxes per launch")
-    bl = [_check_box(b, gv) for b in boxes]
+    _check_spans_apart("acc", _grid_span(acc), (("a", _grid_span(a)), ("v", _grid_span(v))))
+    bl = _check_boxes(boxes, gv)
     if len(h2) != 3 or not all(float(x) > 0 for x in h2):
         raise ValueError("h2 = (hx2, hy2, hz2), all > 0")
     getattr(_C(), "k_face_corr_" + _sfx(a))(a.data_ptr(), v.data_ptr(), acc.data_ptr(), gv, bl,
@@ -653,15 +609,9 @@ def dft_accumulate(u, re, im, boxes, c_row, s_row, *, chunk: int = 0) -> None:
             raise ValueError(f"{name} must be a contiguous 1-D {u.dtype} tensor of {F} values on {u.device}")
     spans = [("u", _grid_span(u))] + [(f"{n}[{f}]", _grid_span(t)) for n, ts in (("re", re), ("im", im))
                                       for f, t in enumerate(ts)]
-    for q, (name, (t0, t1)) in enumerate(spans):
-        for other, (o0, o1) in spans[:q]:
-            if t0 < o1 and o0 < t1:
-                raise ValueError(f"{name} shares memory with {other}")
-    if isinstance(boxes[0], int):
-        boxes = [boxes]
-    if not 1 <= len(boxes) <= 7:
-        raise ValueError("1..7 boxes per launch")
-    bl = [_check_box(b, gv) for b in boxes]
+    for q, (name, span) in enumerate(spans):
+        _check_spans_apart(name, span, spans[:q])
+    bl = _check_boxes(boxes, gv)
     getattr(_C(), "k_dft_acc_" + _sfx(u))(u.data_ptr(), [t.data_ptr() for t in re], [t.data_ptr() for t in im],
                                          c_row.data_ptr(), s_row.data_ptr(), gv, bl, int(chunk), _stream())
 

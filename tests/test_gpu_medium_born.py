@@ -212,22 +212,23 @@ def test_born_step_rejected_calls(C):
     args = [u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, [list(box)], 1, 4, [], list(H2),
             kw["stat"].data_ptr(), 0, torch.cuda.current_stream().cuda_stream]
     Q, D, X, U = q.data_ptr(), dm.data_ptr(), x.data_ptr(), u.data_ptr()
-    # (first, variant, lap_out, q, acc, dm)
-    for first, variant, lap, qq, acc, dd in ((False, 1, 0, 0, 0, D),      # dm without q
-                                             (True, 1, 0, Q, 0, D),       # the Taylor start
-                                             (False, 0, 0, Q, 0, D),      # another variant
-                                             (False, 3, 0, Q, 0, D),
-                                             (False, 1, X, Q, 0, D),      # with save
-                                             (False, 1, 0, Q, X, D),      # with image
-                                             (False, 1, 0, U, 0, D),      # q is u
-                                             (False, 1, 0, Q, 0, U),      # dm is u
-                                             (False, 1, 0, Q, 0, 0)):     # q alone: still an incomplete image mode
+    born, image = C.medium_modes["born"], C.medium_modes["image"]
+    for first, mode, variant, grids in ((False, born, 1, dict(dm=D)),                  # dm without q
+                                        (True, born, 1, dict(q=Q, dm=D)),              # the Taylor start
+                                        (False, born, 0, dict(q=Q, dm=D)),             # another variant
+                                        (False, born, 3, dict(q=Q, dm=D)),
+                                        (False, born, 1, dict(q=Q, dm=D, lap_out=X)),  # with save
+                                        (False, born, 1, dict(q=Q, dm=D, acc=X)),      # with image
+                                        (False, born, 1, dict(q=U, dm=D)),             # q is u
+                                        (False, born, 1, dict(q=Q, dm=U)),             # dm is u
+                                        (False, born, 1, dict(q=Q)),                   # q alone: an incomplete Born mode
+                                        (False, image, 1, dict(q=Q))):                 # and an incomplete image mode
         with pytest.raises(C.Wave3dError):
-            C.k_step_medium_f64(first, *args, variant, 0, 0, 0, lap, qq, acc, 2, [], 0, dd)
+            C.k_step_medium_f64(first, *args, mode, variant=variant, **grids)
     torch.cuda.synchronize()
     assert bool((u == SENT).all()) and not bool(x.any())  # nothing was launched
-    # the positional callers from before the dm argument keep working
-    C.k_step_medium_f64(False, *args, 1, 0, 0, 0, 0, 0, 0)
+    # the plain step of the same arguments runs
+    C.k_step_medium_f64(False, *args, C.medium_modes["plain"], variant=1)
     torch.cuda.synchronize()
     assert not bool((_at(u, box) == SENT).any())
 

@@ -321,33 +321,39 @@ def test_rejected_calls(C):
     args = [u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, [list(box)], 1, 4, [], list(H2),
             kw["stat"].data_ptr(), 0, torch.cuda.current_stream().cuda_stream]
     B, SO, D, DB, S, X, U = (t.data_ptr() for t in (b, so, dm, db, s, x, u))
-    # (first, variant, lap_out, q, acc, order, b, dm, db, sadd)
-    for first, variant, lap, qq, acc, order, bb, dd, dbb, sa in (
-            (False, 1, SO, 0, 0, 2, 0, D, DB, 0),     # scatter without b
-            (False, 1, 0, 0, 0, 2, 0, 0, 0, S),       # Born-add without b
-            (False, 1, SO, 0, 0, 4, B, D, DB, 0),     # another order
-            (False, 1, 0, 0, 0, 8, B, 0, 0, S),
-            (False, 0, SO, 0, 0, 2, B, D, DB, 0),     # another variant
-            (False, 3, 0, 0, 0, 2, B, 0, 0, S),
-            (True, 1, SO, 0, 0, 2, B, D, DB, 0),      # the Taylor start
-            (True, 1, 0, 0, 0, 2, B, 0, 0, S),
-            (False, 1, 0, 0, 0, 2, B, D, DB, 0),      # scatter without s_out
-            (False, 1, SO, 0, 0, 2, B, 0, DB, 0),     # scatter without dm
-            (False, 1, SO, X, 0, 2, B, D, DB, 0),     # with q (Born / image)
-            (False, 1, SO, X, X, 2, B, D, DB, 0),
-            (False, 1, X, 0, 0, 2, B, 0, 0, S),       # Born-add with save
-            (False, 1, 0, X, X, 2, B, 0, 0, S),       # with image
-            (False, 1, 0, X, 0, 2, B, D, 0, S),       # with Born
-            (False, 1, SO, 0, 0, 2, B, D, DB, S),     # both modes
-            (False, 1, U, 0, 0, 2, B, D, DB, 0),      # s_out is u, u1, m, b, dm, db
-            (False, 1, u1.data_ptr(), 0, 0, 2, B, D, DB, 0),
-            (False, 1, m.data_ptr(), 0, 0, 2, B, D, DB, 0),
-            (False, 1, B, 0, 0, 2, B, D, DB, 0),
-            (False, 1, D, 0, 0, 2, B, D, DB, 0),
-            (False, 1, DB, 0, 0, 2, B, D, DB, 0),
-            (False, 1, 0, 0, 0, 2, B, 0, 0, U)):      # s is u
+    SC, AD = C.medium_modes["scatter"], C.medium_modes["born_add"]
+    scg, adg = dict(b=B, s_out=SO, dm=D, db=DB), dict(b=B, sadd=S)  # the grids of the two modes, with b
+
+    def without(grids, name):
+        return {k: v for k, v in grids.items() if k != name}
+
+    for first, mode, variant, order, grids in (
+            (False, SC, 1, 2, without(scg, "b")),            # scatter without b
+            (False, AD, 1, 2, without(adg, "b")),            # Born-add without b
+            (False, SC, 1, 4, scg),                          # another order
+            (False, AD, 1, 8, adg),
+            (False, SC, 0, 2, scg),                          # another variant
+            (False, AD, 3, 2, adg),
+            (True, SC, 1, 2, scg),                           # the Taylor start
+            (True, AD, 1, 2, adg),
+            (False, SC, 1, 2, without(scg, "s_out")),        # scatter without s_out
+            (False, SC, 1, 2, without(scg, "dm")),           # scatter without dm
+            (False, SC, 1, 2, dict(scg, q=X)),               # with q (Born / image)
+            (False, SC, 1, 2, dict(scg, q=X, acc=X)),
+            (False, AD, 1, 2, dict(adg, lap_out=X)),         # Born-add with save
+            (False, AD, 1, 2, dict(adg, q=X, acc=X)),        # with image
+            (False, AD, 1, 2, dict(adg, q=X, dm=D)),         # with Born
+            (False, SC, 1, 2, dict(scg, sadd=S)),            # both modes
+            (False, AD, 1, 2, dict(scg, sadd=S)),
+            (False, SC, 1, 2, dict(scg, s_out=U)),           # s_out is u, u1, m, b, dm, db
+            (False, SC, 1, 2, dict(scg, s_out=u1.data_ptr())),
+            (False, SC, 1, 2, dict(scg, s_out=m.data_ptr())),
+            (False, SC, 1, 2, dict(scg, s_out=B)),
+            (False, SC, 1, 2, dict(scg, s_out=D)),
+            (False, SC, 1, 2, dict(scg, s_out=DB)),
+            (False, AD, 1, 2, dict(adg, sadd=U))):           # s is u
         with pytest.raises(C.Wave3dError):
-            C.k_step_medium_f64(first, *args, variant, 0, 0, 0, lap, qq, acc, order, [], bb, dd, dbb, sa)
+            C.k_step_medium_f64(first, *args, mode, variant=variant, order=order, **grids)
     torch.cuda.synchronize()
     assert bool((u == SENT).all()) and bool((so == SENT).all()) and not bool(x.any())  # nothing was launched
     # both modes do run with these grids

@@ -136,12 +136,15 @@ def test_step_medium_modes_rejected_combinations(C):
     gv = [*shape, shape[2], shape[1] * shape[2]]
     args = [u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, [list(box)], 1, 4, [], list(H2),
             kw["stat"].data_ptr(), 0, torch.cuda.current_stream().cuda_stream]
-    for first, variant, ptrs in ((True, 1, (x.data_ptr(), 0, 0)), (False, 0, (x.data_ptr(), 0, 0)),
-                                 (False, 3, (0, q.data_ptr(), x.data_ptr())),
-                                 (False, 1, (x.data_ptr(), q.data_ptr(), x.data_ptr())),
-                                 (False, 1, (0, q.data_ptr(), 0))):
+    X, Q = x.data_ptr(), q.data_ptr()
+    for first, mode, variant, grids in ((True, "save", 1, dict(lap_out=X)),               # the Taylor start
+                                        (False, "save", 0, dict(lap_out=X)),              # another variant
+                                        (False, "image", 3, dict(q=Q, acc=X)),
+                                        (False, "save", 1, dict(lap_out=X, q=Q, acc=X)),  # both modes' grids
+                                        (False, "image", 1, dict(lap_out=X, q=Q, acc=X)),
+                                        (False, "image", 1, dict(q=Q))):                  # q without acc
         with pytest.raises(C.Wave3dError):
-            C.k_step_medium_f64(first, *args, variant, 0, 0, 0, *ptrs)
+            C.k_step_medium_f64(first, *args, C.medium_modes[mode], variant=variant, **grids)
     torch.cuda.synchronize()
     assert not bool(u.any()) and not bool(x.any())  # nothing was launched
 

@@ -138,27 +138,32 @@ def test_rejected_combinations(C):
     args = [u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, [list(box)], 1, 4, [], list(H2),
             kw["stat"].data_ptr(), 0, torch.cuda.current_stream().cuda_stream]
     P = torch.Tensor.data_ptr
+    IL, SI = C.medium_modes["illum"], C.medium_modes["save_illum"]
     native = [
-        (True, 1, (0, 0, 0), dict(illum=P(h))),                                        # first
-        (True, 1, (P(x), 0, 0), dict(illum=P(h))),
-        (False, 0, (0, 0, 0), dict(illum=P(h))),                                       # variants
-        (False, 2, (0, 0, 0), dict(illum=P(h))),
-        (False, 3, (P(x), 0, 0), dict(illum=P(h))),
-        (False, 1, (0, P(q), P(x)), dict(illum=P(h))),                                 # image
-        (False, 1, (0, P(q), 0), dict(illum=P(h), dm=P(dm))),                          # Born
-        (False, 1, (P(x), 0, 0), dict(illum=P(h), b=P(b), dm=P(dm), db=P(db))),        # scatter
-        (False, 1, (0, 0, 0), dict(illum=P(h), b=P(b), sadd=P(q))),                    # Born-add
-        (False, 1, (0, 0, 0), dict(illum=P(u))),                                       # shared memory
-        (False, 1, (0, 0, 0), dict(illum=P(u1))),
-        (False, 1, (0, 0, 0), dict(illum=P(u2))),
-        (False, 1, (0, 0, 0), dict(illum=P(m))),
-        (False, 1, (0, 0, 0), dict(illum=P(b), b=P(b))),
-        (False, 1, (P(x), 0, 0), dict(illum=P(x))),
-        (False, 1, (0, 0, 0), dict(illum=P(u1) + 8 * shape[2])),                       # partly
+        (True, IL, 1, dict(illum=P(h))),                                               # first
+        (True, SI, 1, dict(illum=P(h), lap_out=P(x))),
+        (False, IL, 0, dict(illum=P(h))),                                              # variants
+        (False, IL, 2, dict(illum=P(h))),
+        (False, SI, 3, dict(illum=P(h), lap_out=P(x))),
+        (False, IL, 1, dict(illum=P(h), q=P(q), acc=P(x))),                            # image
+        (False, IL, 1, dict(illum=P(h), q=P(q), dm=P(dm))),                            # Born
+        (False, IL, 1, dict(illum=P(h), b=P(b), s_out=P(x), dm=P(dm), db=P(db))),      # scatter
+        (False, IL, 1, dict(illum=P(h), b=P(b), sadd=P(q))),                           # Born-add
+        (False, C.medium_modes["image"], 1, dict(illum=P(h), q=P(q), acc=P(x))),       # the same under their modes
+        (False, C.medium_modes["born"], 1, dict(illum=P(h), q=P(q), dm=P(dm))),
+        (False, C.medium_modes["scatter"], 1, dict(illum=P(h), b=P(b), s_out=P(x), dm=P(dm), db=P(db))),
+        (False, C.medium_modes["born_add"], 1, dict(illum=P(h), b=P(b), sadd=P(q))),
+        (False, IL, 1, dict(illum=P(u))),                                              # shared memory
+        (False, IL, 1, dict(illum=P(u1))),
+        (False, IL, 1, dict(illum=P(u2))),
+        (False, IL, 1, dict(illum=P(m))),
+        (False, IL, 1, dict(illum=P(b), b=P(b))),
+        (False, SI, 1, dict(illum=P(x), lap_out=P(x))),
+        (False, IL, 1, dict(illum=P(u1) + 8 * shape[2])),                              # partly
     ]
-    for first, variant, ptrs, more in native:
+    for first, mode, variant, grids in native:
         with pytest.raises(C.Wave3dError):
-            C.k_step_medium_f64(first, *args, variant, 0, 0, 0, *ptrs, **more)
+            C.k_step_medium_f64(first, *args, mode, variant=variant, **grids)
     torch.cuda.synchronize()
     assert not bool(u.any()) and not bool(x.any()) and not bool(h.any())  # nothing was launched
 

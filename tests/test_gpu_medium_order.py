@@ -234,8 +234,8 @@ def test_rejected_calls(C):
 
     def native(box, order, mirror, wrap=()):
         C.k_step_medium_f64(False, u1.data_ptr(), u2.data_ptr(), m.data_ptr(), u.data_ptr(), gv, [list(box)], 4, 9,
-                            list(wrap), list(H2), stat.data_ptr(), 0, torch.cuda.current_stream().cuda_stream, -1,
-                            0, 0, 0, 0, 0, 0, order, mirror)
+                            list(wrap), list(H2), stat.data_ptr(), 0, torch.cuda.current_stream().cuda_stream,
+                            C.medium_modes["plain"], order=order, mirror=mirror)
 
     for box, order, mirror, wrap in (
             (good["box"], 6, [3, no, no, 70], ()),
